@@ -19,10 +19,14 @@ ranks by longest-processing-time first on their DAG sizes
 [s*2^20, (s+1)*2^20) at step s, and nothing is exchanged on the data path
 (still weak scaling: per-rank work is one corpus).
 
-Prints ONE JSON line on rank 0 (contract in the task statement).  Extra
-fields: roofline (INT32 VALU bound, see mythril_amd/roofline.py) and
-cpu_baseline (oracle/evalref.c, the C restatement of z3 model evaluation —
-z3 itself is not installed — on host cores, bounded sample).
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain
+run sets up, warms up, times the steps and prints the line; its extra field
+roofline (INT32 VALU bound, see mythril_amd/roofline.py) is arithmetic on the
+timed steps' own event times.  ``--dump-outputs DIR`` also writes what the
+last timed step computed (``dump_outputs``).  ``--full`` adds the legs that
+take runs of their own: cpu_baseline (oracle/evalref.c, the C restatement of
+z3 model evaluation — z3 itself is not installed — on host cores, bounded
+sample), the self-check of the last step against it, and vs_cpu.
 """
 
 import argparse
@@ -157,20 +161,56 @@ def kernel_key(lib_digest, workload, dags, assign_log2, jit, corpus=None, nreg=N
     return key
 
 
-def node_image(workload, corpus, workers, world):
+# where build() (__graft_entry__.py) leaves the default configuration's
+# compiled-program image (``bench.py --jit-build-only``), next to the library
+PREBUILT_JIT_CACHE = os.path.join(ROOT, "mythril_amd", "lib", "jit_cache")
+
+
+def prebuilt_cache(workload, ids):
+    """The in-tree image cache for the default configuration (every DAG of
+    the 4096-DAG C2 corpus: the headline run, whose image build() assembles
+    ahead of time so the run itself does not), None for any other."""
+    if workload == "c2" and list(ids) == list(range(default_units("c2"))):
+        return PREBUILT_JIT_CACHE
+    return None
+
+
+def prebuilt_path(key):
+    """The file jit.cached_image keeps ``key``'s image in under the in-tree
+    cache (its naming: the key, then the digest of the sources the image
+    depends on)."""
+    import re
+    from mythril_amd import jit
+    return os.path.join(PREBUILT_JIT_CACHE,
+                        "%s_%s.hsaco" % (re.sub(r"[^\w.-]", "_", key), jit.source_digest()))
+
+
+def node_image(workload, corpus, workers, world, store=False):
     """(compiled-program image of ``corpus``, was it cached).  At world > 1
     the ranks of a node share ONE build (jit.cached_image: the first rank to
     take the file lock assembles with up to 64 host workers, the others wait
     and read it), in ``$MYTHGPU_JIT_CACHE`` or a per-user directory under the
-    node's temp dir; at world 1 the image is built in process (timed as
-    ``jit_s``) unless ``$MYTHGPU_JIT_CACHE`` is set."""
+    node's temp dir.  At world 1 the image is built in process (timed as
+    ``jit_s``) unless ``$MYTHGPU_JIT_CACHE`` is set, except that the default
+    configuration first looks for the image ``build()`` left in the tree
+    (``prebuilt_cache``): a run only reads that file (no lock, nothing
+    written: the tree may belong to another user, and the file is put in
+    place whole), and only ``store`` (``--jit-build-only``) writes it.  The
+    key names the programs themselves (``programs_digest``), so an image is
+    never reused for programs another compiler knob produced."""
     import tempfile
     from mythril_amd import jit
     ids = [d for d, _, _, _ in corpus]
-    key = "%s_%d_%d_%d_%d_lds%d_r%d" % (workload, len(ids), ids[0], ids[-1], sum(ids), LDS_SLOTS,
-                                        corpus[0][1].nreg)
+    key = "%s_%d_%d_%d_%d_lds%d_r%d_%s" % (workload, len(ids), ids[0], ids[-1], sum(ids), LDS_SLOTS,
+                                           corpus[0][1].nreg, programs_digest(corpus))
     cache = os.environ.get("MYTHGPU_JIT_CACHE") or (
         os.path.join(tempfile.gettempdir(), "mythgpu_jit_%d" % os.getuid()) if world > 1 else None)
+    if cache is None and prebuilt_cache(workload, ids):
+        try:
+            with open(prebuilt_path(key), "rb") as fh:
+                return fh.read(), True
+        except OSError:                   # not built (or not ours to read): build it
+            cache = PREBUILT_JIT_CACHE if store else None
     nw = max(workers, min(os.cpu_count() or 1, 64)) if world > 1 else workers
     return jit.cached_image(key, lambda: jit.compile_batch(
         [(p, None, d) for d, p, _, _ in corpus], workers=nw, lds_slots=LDS_SLOTS), cache)
@@ -332,6 +372,50 @@ def cpu_baseline(corpus, budget_s=20.0, workload="c2", check=None):
     return base, sc
 
 
+# float64 bytes the sampled root-bit words of a dump may take (the whole dump
+# stays under 64 MB)
+DUMP_SAMPLE_BYTES = 48 << 20
+
+
+def dump_outputs(path, d_bits, d_first, n_assign):
+    """``--dump-outputs``: what the last timed step left in the caller's
+    buffers, as float64 ``.npy`` files two builds can be compared by (the
+    inputs are a function of the arguments alone: corpus seed, step index).
+
+    * ``first_sat.npy`` (units,): every unit's first satisfying candidate
+      index, -1 where no candidate of the step satisfied it;
+    * ``root_bits_rowsum.npy`` (units,): the sum of the 32-bit halves of the
+      unit's whole root-bit row (exact: < 2^53), so a flipped bit anywhere in
+      the step's output changes a figure;
+    * ``root_bits_cols.npy`` (cols,) and ``root_bits_sample.npy`` (units,
+      cols, 2): a fixed seeded sample of 64-candidate word columns (every
+      column when they fit) and, for every unit, the low and high 32-bit half
+      of those root-bit words.
+
+    Bits of the last word past ``n_assign`` are cleared first."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    units, words = d_bits.shape
+    if n_assign % 64:
+        d_bits[:, -1] &= (1 << (n_assign % 64)) - 1
+    first = d_first.cpu().numpy()
+    from mythril_amd import shard
+    np.save(os.path.join(path, "first_sat.npy"),
+            np.where(first == shard.NONE, -1, first).astype(np.float64))
+    rowsum = np.empty(units, dtype=np.float64)
+    rows_at_once = max(1, (64 << 20) // (words * 16))
+    for r in range(0, units, rows_at_once):
+        halves = d_bits[r:r + rows_at_once].view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+        rowsum[r:r + rows_at_once] = halves.sum(dim=1).cpu().numpy()
+    np.save(os.path.join(path, "root_bits_rowsum.npy"), rowsum)
+    n_cols = max(1, min(words, DUMP_SAMPLE_BYTES // (units * 16)))
+    cols = np.sort(np.random.default_rng(SEED).choice(words, size=n_cols, replace=False))
+    idx = torch.as_tensor(cols, dtype=torch.long, device=d_bits.device)
+    sample = d_bits.index_select(1, idx).cpu().numpy().view("<u4").reshape(units, n_cols, 2)
+    np.save(os.path.join(path, "root_bits_cols.npy"), cols.astype(np.float64))
+    np.save(os.path.join(path, "root_bits_sample.npy"), sample.astype(np.float64))
+
+
 def waves_per_simd(nreg: int) -> int:
     """Waves per SIMD the layout's VGPR budget allows (512 per lane)."""
     from mythril_amd import asmgen
@@ -357,7 +441,15 @@ def main():
                     help="DAGs per step (default 4096 for c2, %d distinct queries for c3/c4, "
                          "%d for c5)" % (STREAM_QUERIES, 2 * STREAM_QUERIES))
     ap.add_argument("--assign-log2", type=int, default=20)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the CPU baseline (oracle/evalref.c on "
+                         "host cores) and the bit-exact self-check of the last step against it "
+                         "(cpu_baseline, selfcheck, vs_cpu in the result line)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: leave the CPU baseline and self-check out")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (first satisfying index and "
+                         "root bits per DAG) as DIR/<name>.npy (see dump_outputs)")
     ap.add_argument("--shard", choices=("assign", "corpus"), default="assign",
                     help="assignment axis (default, C2) or corpus axis (C5)")
     ap.add_argument("--traffic-json", default=os.path.join(ROOT, "profiles", "traffic.json"))
@@ -369,6 +461,8 @@ def main():
                     help="compile the corpus and its code object into $MYTHGPU_JIT_CACHE and "
                          "exit (no GPU): profiling runs then load it")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     args.jit = not args.interp
     if args.dags is None:
         args.dags = default_units(args.workload)
@@ -405,7 +499,8 @@ def main():
     image, t_jit, jit_cached = None, 0.0, False
     if args.jit:                      # code generation + assembly, still before the GPU
         t0 = time.time()
-        image, jit_cached = node_image(args.workload, corpus, workers, world)
+        image, jit_cached = node_image(args.workload, corpus, workers, world,
+                                        store=args.jit_build_only)
         t_jit = time.time() - t0
     if args.jit_build_only:
         print("jit image %.1f MB in %.1f s (cached: %s)" % (len(image or b"") / 1e6, t_jit,
@@ -466,6 +561,8 @@ def main():
     sat_dags = int(sat_all)
 
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, d_bits, d_first, n_assign)
         from mythril_amd.roofline import VALU_PEAK_OPS
         ms_step = elapsed * 1000.0 / args.steps
         evals = nodes_all * n_assign * args.steps
@@ -553,7 +650,7 @@ def main():
             "jit_cached": jit_cached if args.jit else None,
             "jit_image_digest": image_digest,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             last = step_first(args.shard, args.warmup + args.steps - 1, rank, world, n_assign)
             pos = sample_indices(corpus)
             idx = torch.tensor(pos, dtype=torch.long, device="cuda")

@@ -20,7 +20,7 @@ def test_c2_four_wave_layout_self_check():
     for k in ("MYTHGPU_NREG", "MYTHGPU_LDS_SLOTS", "MYTHGPU_LIB", "MYTHGPU_JIT_CACHE"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, "-u", "bench.py", "--workload", "c2", "--dags", "256",
-                        "--steps", "1", "--warmup", "0", "--assign-log2", "16"],
+                        "--steps", "1", "--warmup", "0", "--assign-log2", "16", "--full"],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=280)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
     d = json.loads(r.stdout[r.stdout.rindex('{"metric"'):])

@@ -126,7 +126,7 @@ def test_fingerprint_tells_opcode_twins_apart():
     assert fa != fx
 
 
-def test_jit_image_entries_point_at_each_program():
+def test_jit_image_entries_point_at_each_program(tmp_path):
     """compile_batch links chunk objects and the table: entry i (relative
     to mg_jit_table) is the first instruction of program i, and its
     fingerprint is that of program i's records."""
@@ -136,13 +136,14 @@ def test_jit_image_entries_point_at_each_program():
         p = compile_constraints(roots)
         items.append((p, default_leafgen(p), d))
     image = jit.compile_batch(items, chunk=2)
-    with open("/tmp/_mg_jit_test.hsaco", "wb") as fh:
+    hsaco = str(tmp_path / "jit_test.hsaco")
+    with open(hsaco, "wb") as fh:
         fh.write(image)
-    syms = subprocess.run([jit.LLVM_BIN + "/llvm-readelf", "-s", "/tmp/_mg_jit_test.hsaco"],
+    syms = subprocess.run([jit.LLVM_BIN + "/llvm-readelf", "-s", hsaco],
                           capture_output=True, text=True, check=True).stdout
     tab = int(re.search(r"([0-9a-f]+)\s+96 OBJECT\s+GLOBAL\s+\w+\s+\d+ mg_jit_table", syms).group(1), 16)
     data = subprocess.run([jit.LLVM_BIN + "/llvm-objdump", "-s", "-j", ".data",
-                           "/tmp/_mg_jit_test.hsaco"], capture_output=True, text=True,
+                           hsaco], capture_output=True, text=True,
                           check=True).stdout
     words = {}
     for line in data.splitlines():
@@ -151,7 +152,7 @@ def test_jit_image_entries_point_at_each_program():
             base = int(m.group(1), 16)
             for k, wd in enumerate(m.group(2).split()):
                 words[base + 4 * k] = int.from_bytes(bytes.fromhex(wd), "little")
-    dis = subprocess.run([jit.LLVM_BIN + "/llvm-objdump", "-d", "/tmp/_mg_jit_test.hsaco"],
+    dis = subprocess.run([jit.LLVM_BIN + "/llvm-objdump", "-d", hsaco],
                          capture_output=True, text=True, check=True).stdout
     at = {}
     for line in dis.splitlines():

@@ -3,7 +3,8 @@
 #   tools/gpu_measure.sh <tag> <steps> [workloads]
 # <steps>: comma list of tests,bench,profile,search
 #   tests   - the -m gpu suite
-#   bench   - the default bench line per workload (CPU leg + self-check)
+#   bench   - the bench line per workload with its CPU leg and self-check
+#             (bench.py --full), logged under $LOGDIR (default logs/)
 #   profile - tools/profile.sh per workload (kernel trace, FETCH, WRITE, SQ)
 #   search  - tools/search_bench.py
 # workloads default to "c2 c3 c4 c5".  (Settings go on the command line:
@@ -19,7 +20,8 @@ if [[ $STEPS == *,tests,* ]]; then
 fi
 if [[ $STEPS == *,bench,* ]]; then
   for W in $WL; do
-    timeout -k 10 600 python -u bench.py --workload $W > gpurun_out/${TAG}_bench_$W.log 2>&1 || { tail -20 gpurun_out/${TAG}_bench_$W.log; echo "bench $W failed"; exit 1; }
+    L=${LOGDIR:-logs}/${TAG}_bench_$W.log; mkdir -p ${LOGDIR:-logs}
+    timeout -k 10 600 python -u bench.py --full --workload $W > $L 2>&1 || { tail -20 $L; echo "bench $W failed"; exit 1; }
   done
 fi
 if [[ $STEPS == *,profile,* ]]; then
