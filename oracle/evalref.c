@@ -564,6 +564,41 @@ int ev_run_gen(const uint32_t* nodes, uint32_t n_nodes, const uint64_t* consts,
     return 0;
 }
 
+/* Per-root bits under generated candidates [first, first + n):
+ * root_out[a * n_roots + r] (ev_run_gen's conjunction, taken apart). */
+int ev_run_gen_roots(const uint32_t* nodes, uint32_t n_nodes, const uint64_t* consts,
+                     const table_desc* td, uint32_t n_tables, const uint32_t* leafidx,
+                     const uint32_t* roots, uint32_t n_roots, const uint32_t* leaf_widths,
+                     uint32_t n_leaves, const uint64_t* pool, uint32_t pool_n, const uint32_t* pct,
+                     uint64_t seed, uint64_t prog_seed, uint64_t first, uint64_t n,
+                     uint8_t* root_out, int threads) {
+    table_t tabs[64];
+    if (n_tables > 64) return -1;
+    if (too_wide(nodes, n_nodes, td, n_tables)) return -2;
+    make_tables(td, n_tables, leafidx, tabs);
+    dag_t g = {nodes, n_nodes, consts, tabs, n_tables};
+#ifdef _OPENMP
+    if (threads > 0) omp_set_num_threads(threads);
+#endif
+#pragma omp parallel
+    {
+        V* vals = (V*)malloc(sizeof(V) * (n_nodes ? n_nodes : 1));
+        V* leaves = (V*)malloc(sizeof(V) * (n_leaves ? n_leaves : 1));
+#pragma omp for schedule(dynamic, 64)
+        for (int64_t a = 0; a < (int64_t)n; ++a) {
+            for (uint32_t l = 0; l < n_leaves; ++l)
+                gen_leaf(seed, prog_seed, l, first + (uint64_t)a, leaf_widths[l], pool, pool_n, pct,
+                         &leaves[l]);
+            eval_dag(&g, leaves, vals);
+            for (uint32_t r = 0; r < n_roots; ++r)
+                root_out[(uint64_t)a * n_roots + r] = (uint8_t)(vals[roots[r]].w[0] & 1);
+        }
+        free(vals);
+        free(leaves);
+    }
+    return 0;
+}
+
 /* Per-root bits under explicit leaf values: root_out[a * n_roots + r]. */
 int ev_run_leaves_roots(const uint32_t* nodes, uint32_t n_nodes, const uint64_t* consts,
                         const table_desc* td, uint32_t n_tables, const uint32_t* leafidx,

@@ -173,6 +173,7 @@ def lib(wide: bool = False):
         L.ev_run_gen.argtypes = [p, C.c_uint32, p, p, C.c_uint32, p, p, C.c_uint32, p, C.c_uint32,
                                  p, C.c_uint32, p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64,
                                  p, C.c_int]
+        L.ev_run_gen_roots.argtypes = L.ev_run_gen.argtypes
         L.ev_run_leaves.argtypes = [p, C.c_uint32, p, p, C.c_uint32, p, p, C.c_uint32, C.c_uint32,
                                     p, C.c_uint64, p, p]
         L.ev_run_leaves_roots.argtypes = [p, C.c_uint32, p, p, C.c_uint32, p, p, C.c_uint32,
@@ -208,7 +209,9 @@ def _p(a):
 
 
 def run_gen(S: Serialized, program, seed: int, prog_seed: int, first: int, n: int,
-            threads: int = 0, pct=(50, 70, 85)) -> np.ndarray:
+            threads: int = 0, pct=(50, 70, 85), per_root: bool = False) -> np.ndarray:
+    """Root bits of candidates [first, first + n) from the oracle's own
+    generator (``per_root``: (n, n_constraints) bits of every constraint)."""
     L, nl, nodes, consts, tabs, leafidx, roots = _arrays(S)
     widths = np.array([l.width for l in program.leaves] or [1], dtype=np.uint32)
     pool = np.zeros((max(1, len(program.const_values)), nl), dtype=np.uint64)
@@ -216,13 +219,15 @@ def run_gen(S: Serialized, program, seed: int, prog_seed: int, first: int, n: in
         for k in range(4):
             pool[i, k] = (v >> (64 * k)) & 0xFFFFFFFFFFFFFFFF
     pctv = np.array(pct, dtype=np.uint32)
-    out = np.zeros(n, dtype=np.uint8)
-    rc = L.ev_run_gen(_p(nodes), nodes.shape[0], _p(consts), C.cast(tabs, C.c_void_p),
-                          len(S.tables), _p(leafidx), _p(roots), len(S.roots), _p(widths),
-                          len(program.leaves), _p(pool), len(program.const_values), _p(pctv),
-                          seed & (2**64 - 1), prog_seed & (2**64 - 1), first, n, _p(out), threads)
+    nr = max(1, len(S.roots))
+    out = np.zeros((max(1, n), nr) if per_root else n, dtype=np.uint8)
+    fn = L.ev_run_gen_roots if per_root else L.ev_run_gen
+    rc = fn(_p(nodes), nodes.shape[0], _p(consts), C.cast(tabs, C.c_void_p),
+            len(S.tables), _p(leafidx), _p(roots), len(S.roots), _p(widths),
+            len(program.leaves), _p(pool), len(program.const_values), _p(pctv),
+            seed & (2**64 - 1), prog_seed & (2**64 - 1), first, n, _p(out), threads)
     assert rc == 0, rc
-    return out.astype(bool)
+    return out[:n, :len(S.roots)].astype(bool) if per_root else out.astype(bool)
 
 
 def run_leaves(S: Serialized, program, leaf_vals: Sequence[Sequence[int]], want_nodes=False):
@@ -251,10 +256,7 @@ def run_leaves_soa(S: Serialized, program, leaves_soa: np.ndarray, per_root: boo
     ``Engine.eval_gen(..., want_leaves=True)``)."""
     L, _, nodes, consts, tabs, leafidx, roots = _arrays(S)
     nl, _, n = leaves_soa.shape
-    x = np.ascontiguousarray(leaves_soa.transpose(2, 0, 1)).astype(np.uint64)   # (n, nl, 8)
-    lv = np.ascontiguousarray(x[:, :, 0::2] | (x[:, :, 1::2] << np.uint64(32)))  # (n, nl, 4)
-    if nl == 0:
-        lv = np.zeros((max(1, n), 1, 4), dtype=np.uint64)
+    lv = _soa_to_lv(leaves_soa)                                                  # (n, nl, 4)
     nr = max(1, len(S.roots))
     out = np.zeros((max(1, n), nr), dtype=np.uint8)
     rc = L.ev_run_leaves_roots(_p(nodes), nodes.shape[0], _p(consts),
@@ -263,6 +265,43 @@ def run_leaves_soa(S: Serialized, program, leaves_soa: np.ndarray, per_root: boo
     assert rc == 0
     bits = out[:n, :len(S.roots)].astype(bool)
     return bits if per_root else bits.all(axis=1)
+
+
+def _soa_to_lv(leaves_soa: np.ndarray) -> np.ndarray:
+    """(n_leaves, 8, n) u32 limbs -> the C oracle's (n, n_leaves, 4) u64."""
+    nl, _, n = leaves_soa.shape
+    if nl == 0:
+        return np.zeros((max(1, n), 1, 4), dtype=np.uint64)
+    x = np.ascontiguousarray(leaves_soa.transpose(2, 0, 1)).astype(np.uint64)   # (n, nl, 8)
+    return np.ascontiguousarray(x[:, :, 0::2] | (x[:, :, 1::2] << np.uint64(32)))
+
+
+def run_nodes_soa(S: Serialized, program, leaves_soa: np.ndarray, records=None,
+                  chunk: int = 128):
+    """``(root bits, vals_out)`` under the engine's own leaf buffer
+    ((n_leaves, 8, n) u32 limbs): ``vals_out[a, r]`` is the value (the
+    build's u64 limbs, :func:`node_value`) of record ``r`` on lane ``a`` —
+    of every record, or of ``records`` (record indices, e.g.
+    ``S.node_index[node.id]``) in that order.  Lanes are evaluated ``chunk``
+    at a time, so only the kept records of all lanes are ever held."""
+    L, nl_, nodes, consts, tabs, leafidx, roots = _arrays(S)
+    nl, _, n = leaves_soa.shape
+    keep = None if records is None else np.asarray(list(records), dtype=np.int64)
+    n_keep = nodes.shape[0] if keep is None else keep.size
+    vals_out = np.zeros((n, n_keep, nl_), dtype=np.uint64)
+    out = np.zeros(max(1, n), dtype=np.uint8)
+    for a0 in range(0, n, chunk):
+        a1 = min(n, a0 + chunk)
+        lv = _soa_to_lv(leaves_soa[:, :, a0:a1])
+        part = np.zeros((a1 - a0, nodes.shape[0], nl_), dtype=np.uint64)
+        bits = np.zeros(a1 - a0, dtype=np.uint8)
+        rc = L.ev_run_leaves(_p(nodes), nodes.shape[0], _p(consts), C.cast(tabs, C.c_void_p),
+                             len(S.tables), _p(leafidx), _p(roots), len(S.roots), max(nl, 1),
+                             _p(lv), a1 - a0, _p(part), _p(bits))
+        assert rc == 0, rc
+        vals_out[a0:a1] = part if keep is None else part[:, keep, :]
+        out[a0:a1] = bits
+    return out[:n].astype(bool), vals_out
 
 
 def node_value(vals_out, a: int, rec_index: int) -> int:

@@ -11,7 +11,10 @@ The interpreter selects among up to 64 handler variants per opcode from
 static properties, so the test also asserts that every
 (family, variant) the bench configurations execute — reported by the
 translator itself (``engine.handler_variants``) — belongs to a program this
-test checked lane by lane.
+test ran, its root bit (the AND of all its roots) compared on every lane.
+That bit is false on almost every lane, so it says little about a single
+value: every node value and every root bit of a cover of the same variants
+is compared in ``tests/test_gpu_value_parity.py``.
 
 The module runs on the register layout of its process (``MYTHGPU_NREG``):
 the default 16 slots, and — from ``tests/test_gpu_layout.py``, in a fresh
