@@ -111,6 +111,7 @@ def test_batch_eval_gen_sets_its_device_and_refuses_a_foreign_batch(engine, two_
     context and launched through the other is refused (MG_E_ARG)."""
     import ctypes as C
     import threading
+    from gpu_batch import device_buffer
     from mythril_amd.ir import compile_constraints
     from mythril_amd.corpus import make_dag
     hip = C.CDLL("libamdhip64.so.7", mode=C.RTLD_GLOBAL)
@@ -121,9 +122,7 @@ def test_batch_eval_gen_sets_its_device_and_refuses_a_foreign_batch(engine, two_
 
     def run(eng, tag):
         loaded = [eng.load(p, prog_seed=k) for k, p in enumerate(progs)]
-        d_bits = C.c_void_p()
-        assert hip.hipMalloc(C.byref(d_bits), C.c_size_t(len(progs) * words * 8)) == 0
-        try:
+        with device_buffer(len(progs) * words * 8) as d_bits:
             b = eng.batch_create(loaded)
             try:
                 hip.hipSetDevice(0)
@@ -134,8 +133,6 @@ def test_batch_eval_gen_sets_its_device_and_refuses_a_foreign_batch(engine, two_
                 out[tag] = host
             finally:
                 eng.batch_free(b)
-        finally:
-            hip.hipFree(d_bits)
 
     run(e0, "main")
     t = threading.Thread(target=run, args=(e1, "thread"))

@@ -120,6 +120,7 @@ def test_device_blocks_reused_across_loads(engine):
     including after a batch ran on a caller's stream (the block is reused
     only once that launch completed)."""
     import ctypes as C
+    from gpu_batch import device_buffer
     # the caller's stream and output buffer come from the library's own HIP
     # runtime (torch bundles another one, which cannot share this process's
     # device once the engine holds it)
@@ -142,23 +143,22 @@ def test_device_blocks_reused_across_loads(engine):
             check(d, lp)
             del lp                                  # back to the block cache
     # a batch on a caller's stream, its programs freed right after the launch
-    stream, d_bits = C.c_void_p(), C.c_void_p()
+    stream = C.c_void_p()
     assert hip.hipStreamCreate(C.byref(stream)) == 0
     words = (1 << 16) // 64
-    assert hip.hipMalloc(C.byref(d_bits), C.c_size_t(4 * words * 8)) == 0
-    try:
-        loaded = [engine.load(progs[d], prog_seed=d) for d in dag_ids[:4]]
-        batch = engine.batch_create(loaded)
-        engine.batch_eval_gen(batch, seed, first, 1 << 16, d_bits.value, 0, stream.value)
-        engine.batch_free(batch)
-        del loaded
-        for d in dag_ids[4:]:
-            lp = engine.load(progs[d], prog_seed=d)
-            check(d, lp)
-    finally:
-        hip.hipStreamSynchronize(stream)
-        hip.hipFree(d_bits)
-        hip.hipStreamDestroy(stream)
+    with device_buffer(4 * words * 8) as d_bits:
+        try:
+            loaded = [engine.load(progs[d], prog_seed=d) for d in dag_ids[:4]]
+            batch = engine.batch_create(loaded)
+            engine.batch_eval_gen(batch, seed, first, 1 << 16, d_bits.value, 0, stream.value)
+            engine.batch_free(batch)
+            del loaded
+            for d in dag_ids[4:]:
+                lp = engine.load(progs[d], prog_seed=d)
+                check(d, lp)
+        finally:
+            hip.hipStreamSynchronize(stream)
+            hip.hipStreamDestroy(stream)
 
 
 def test_full_size_sampled_and_deterministic(engine):
@@ -217,12 +217,8 @@ def test_bench_entry_point_bit_exact_against_c_oracle(engine):
     smtlib_ref by tests/test_evalref.py) on every lane: 48 corpus DAGs (8 of them
     with hits) x 2^16 candidates starting at 2^20 (rank 1's slice of a
     2-GPU run), so the generator's 64-bit candidate index is exercised."""
-    import ctypes as C
-    from mythril_amd import shard
-    from mythril_amd.engine import default_leafgen, unpack_bits
+    import gpu_batch as G
     from oracle import evalref
-    # device buffers straight from the HIP runtime the library itself uses
-    hip = C.CDLL("libamdhip64.so.7")
     seed = 0x6D797468
     # 40 DAGs spread over the corpus + 8 with satisfying lanes in this slice
     # (found by tools/find_sat_slice.py), so the first-index reduction is
@@ -233,33 +229,12 @@ def test_bench_entry_point_bit_exact_against_c_oracle(engine):
     for d in dag_ids:
         roots, _ = make_dag(d, seed)
         progs.append((d, roots, compile_constraints(roots)))
-    loaded = [engine.load(p, default_leafgen(p), prog_seed=d) for d, _, p in progs]
-    batch = engine.batch_create(loaded)
     n, first = 1 << 16, 1 << 20
-    bits = np.zeros((len(progs), n // 64), dtype=np.uint64)
-    firsts = np.full(len(progs), shard.NONE, dtype=np.int64)
-    d_bits, d_first = C.c_void_p(), C.c_void_p()
-    assert hip.hipMalloc(C.byref(d_bits), C.c_size_t(bits.nbytes)) == 0
-    assert hip.hipMalloc(C.byref(d_first), C.c_size_t(firsts.nbytes)) == 0
-    try:
-        assert hip.hipMemcpy(d_first, firsts.ctypes.data_as(C.c_void_p), C.c_size_t(firsts.nbytes), 1) == 0
-        engine.batch_eval_gen(batch, seed, first, n, d_bits.value, d_first.value)
-        assert hip.hipDeviceSynchronize() == 0
-        assert hip.hipMemcpy(bits.ctypes.data_as(C.c_void_p), d_bits, C.c_size_t(bits.nbytes), 2) == 0
-        assert hip.hipMemcpy(firsts.ctypes.data_as(C.c_void_p), d_first, C.c_size_t(firsts.nbytes), 2) == 0
-    finally:
-        engine.batch_free(batch)
-        hip.hipFree(d_bits)
-        hip.hipFree(d_first)
-    firsts = firsts.tolist()
+    bits, firsts = G.run_batch(engine, [(d, p) for d, _, p in progs], seed, first, n)
     threads = int(os.environ.get("OMP_NUM_THREADS", "0")) or 8
-    n_sat = 0
-    for k, (d, roots, p) in enumerate(progs):
-        want = evalref.run_gen(evalref.serialize(roots, p), p, seed, d, first, n, threads)
-        got = unpack_bits(bits[k], n)
-        assert np.array_equal(got, want), (d, int(np.argmax(got != want)))
-        hit = np.flatnonzero(want)
-        assert firsts[k] == (first + int(hit[0]) if hit.size else shard.NONE), d
-        assert hit.size or d not in sat_ids, d
-        n_sat += int(hit.size)
+    want = [evalref.run_gen(evalref.serialize(roots, p), p, seed, d, first, n, threads)
+            for d, roots, p in progs]
+    _, n_sat = G.assert_matches_oracle(bits, firsts, want, first, "C2 batch", ids=dag_ids)
+    for d, w in zip(dag_ids, want):
+        assert w.any() or d not in sat_ids, d
     print("satisfying lanes in the slice:", n_sat)

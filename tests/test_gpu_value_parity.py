@@ -16,16 +16,15 @@ layouts, interpreter and compiled programs, C2 / C3 / C4 / C5;
 """
 
 import contextlib
-import ctypes as C
 import time
 
-import numpy as np
 import pytest
 
 import value_units as V
-from mythril_amd import jit, shard
+from gpu_batch import run_loaded
+from mythril_amd import jit
 from mythril_amd.build import LAYOUT_LDS_SLOTS
-from mythril_amd.engine import default_leafgen, get_engine, unpack_bits
+from mythril_amd.engine import default_leafgen, get_engine
 
 pytestmark = pytest.mark.gpu
 
@@ -75,27 +74,7 @@ class GpuExecutor:
                                      want_leaves=True) for _, p in items]
 
     def batch(self, items, first, n):
-        eng, hip = self.engine, C.CDLL("libamdhip64.so.7")
-        batch = eng.batch_create([self.loaded[id(p)] for _, p in items])
-        bits = np.zeros((len(items), n // 64), dtype=np.uint64)
-        firsts = np.full(len(items), shard.NONE, dtype=np.int64)
-        d_bits, d_first = C.c_void_p(), C.c_void_p()
-        assert hip.hipMalloc(C.byref(d_bits), C.c_size_t(bits.nbytes)) == 0
-        assert hip.hipMalloc(C.byref(d_first), C.c_size_t(firsts.nbytes)) == 0
-        try:
-            assert hip.hipMemcpy(d_first, firsts.ctypes.data_as(C.c_void_p),
-                                 C.c_size_t(firsts.nbytes), 1) == 0
-            eng.batch_eval_gen(batch, V.SEED, first, n, d_bits.value, d_first.value)
-            assert hip.hipDeviceSynchronize() == 0
-            assert hip.hipMemcpy(bits.ctypes.data_as(C.c_void_p), d_bits,
-                                 C.c_size_t(bits.nbytes), 2) == 0
-            assert hip.hipMemcpy(firsts.ctypes.data_as(C.c_void_p), d_first,
-                                 C.c_size_t(firsts.nbytes), 2) == 0
-        finally:
-            eng.batch_free(batch)
-            hip.hipFree(d_bits)
-            hip.hipFree(d_first)
-        return np.array([unpack_bits(b, n) for b in bits]), firsts.tolist()
+        return run_loaded(self.engine, [self.loaded[id(p)] for _, p in items], V.SEED, first, n)
 
 
 @pytest.mark.parametrize("workload", V.WORKLOADS)

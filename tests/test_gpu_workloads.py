@@ -85,37 +85,14 @@ def test_workload_every_lane_every_constraint(engine, name, const_keys):
 def test_workload_batch_entry_point(engine, name):
     """``mg_batch_eval_gen`` (the path ``bench.py --workload`` times) over 32
     queries against ``evalref.run_gen`` (same generator, same pools)."""
-    import ctypes as C
-    from mythril_amd import shard
-    from mythril_amd.engine import unpack_bits
-    hip = C.CDLL("libamdhip64.so.7")
+    import gpu_batch as G
     qs = distinct_queries(name)
     progs = [compile_constraints(q) for q in qs]
-    loaded = [engine.load(p, default_leafgen(p), prog_seed=i) for i, p in enumerate(progs)]
-    batch = engine.batch_create(loaded)
     n, first, seed = 1 << 14, 1 << 20, 0x6D797468
-    bits = np.zeros((len(progs), n // 64), dtype=np.uint64)
-    firsts = np.full(len(progs), shard.NONE, dtype=np.int64)
-    d_bits, d_first = C.c_void_p(), C.c_void_p()
-    assert hip.hipMalloc(C.byref(d_bits), C.c_size_t(bits.nbytes)) == 0
-    assert hip.hipMalloc(C.byref(d_first), C.c_size_t(firsts.nbytes)) == 0
-    try:
-        assert hip.hipMemcpy(d_first, firsts.ctypes.data_as(C.c_void_p),
-                             C.c_size_t(firsts.nbytes), 1) == 0
-        engine.batch_eval_gen(batch, seed, first, n, d_bits.value, d_first.value)
-        assert hip.hipDeviceSynchronize() == 0
-        assert hip.hipMemcpy(bits.ctypes.data_as(C.c_void_p), d_bits, C.c_size_t(bits.nbytes), 2) == 0
-        assert hip.hipMemcpy(firsts.ctypes.data_as(C.c_void_p), d_first,
-                             C.c_size_t(firsts.nbytes), 2) == 0
-    finally:
-        engine.batch_free(batch)
-        hip.hipFree(d_bits)
-        hip.hipFree(d_first)
-    for k, (q, p) in enumerate(zip(qs, progs)):
-        want = evalref.run_gen(evalref.serialize(q, p), p, seed, k, first, n, THREADS)
-        assert np.array_equal(unpack_bits(bits[k], n), want), (name, k)
-        hit = np.flatnonzero(want)
-        assert firsts[k] == (first + int(hit[0]) if hit.size else shard.NONE), (name, k)
+    bits, firsts = G.run_batch(engine, list(enumerate(progs)), seed, first, n)
+    want = [evalref.run_gen(evalref.serialize(q, p), p, seed, k, first, n, THREADS)
+            for k, (q, p) in enumerate(zip(qs, progs))]
+    G.assert_matches_oracle(bits, firsts, want, first, name)
 
 
 @pytest.mark.parametrize("name", ["c1", "c3", "c4", "c5"])

@@ -23,9 +23,9 @@ def _bench_env():
     return env
 
 
-def _run_json(code: str):
-    out = subprocess.run([sys.executable, "-c", code], cwd=ROOT, env=_bench_env(), check=True,
-                         capture_output=True, text=True, timeout=600).stdout
+def _run_json(code: str, **env):
+    out = subprocess.run([sys.executable, "-c", code], cwd=ROOT, env=dict(_bench_env(), **env),
+                         check=True, capture_output=True, text=True, timeout=600).stdout
     return json.loads(out.strip().splitlines()[-1])
 
 
@@ -73,6 +73,28 @@ def test_bench_register_layouts():
 def layout_max_scratch():
     from mythril_amd.layout import W4_MAX_SCRATCH_SLOTS
     return W4_MAX_SCRATCH_SLOTS
+
+
+def test_layout_knob_compiles_what_the_explicit_layout_compiles():
+    """``MYTHGPU_NREG=11`` (bench.py's A/B knob) makes 11 slots the process
+    default, and the programs ``bench.compile_unit`` then builds are byte for
+    byte those of ``bench.compile_unit((w, d, 11))`` without the knob — the
+    path whose GPU parity tests/test_gpu_bench_parity.py checks."""
+    code = ("import hashlib, json, bench\n"
+            "from mythril_amd import irdefs\n"
+            "out = {'nreg': irdefs.NREG}\n"
+            "for item in (('c2', 5), ('c3', 16)):\n"
+            "    p = bench.compile_unit(item + %s)[1]\n"
+            "    h = hashlib.sha256()\n"
+            "    for a in (p.code, p.consts):\n"
+            "        h.update(repr((a.dtype.str, a.shape)).encode() + a.tobytes())\n"
+            "    out[item[0]] = [p.nreg, p.n_lds, h.hexdigest()]\n"
+            "print(json.dumps(out))\n")
+    knob = _run_json(code % "()", MYTHGPU_NREG="11")
+    explicit = _run_json(code % "(11,)")
+    assert knob.pop("nreg") == 11 and explicit.pop("nreg") == 16
+    assert knob["c2"][0] == knob["c3"][0] == 11
+    assert knob == explicit
 
 
 def test_traffic_json_keyed_to_this_tree():

@@ -210,3 +210,27 @@ def test_check_values_sees_a_corrupted_reload_the_root_bit_does_not():
     finally:
         asm_sim._CACHE["lines"] = saved
     V.check_values(ex, w, 16, "sim", [d], first, n, forms=("nodes",))
+
+
+def test_batch_comparison_rejects_a_wrong_lane_and_a_wrong_first_index():
+    """``gpu_batch.assert_matches_oracle`` (the one root-bit comparison of the
+    GPU parity tests) passes on the oracle's own data and fails on one
+    flipped lane, a first index off by one, and ``shard.NONE`` where a hit
+    exists: 3 units x 128 made-up lanes, the middle one with no hit."""
+    import gpu_batch as G
+    from mythril_amd import shard
+    first = 1 << 20
+    want = np.zeros((3, 128), dtype=bool)
+    want[0, [70, 127]] = want[2, 5] = True
+    firsts = [first + 70, shard.NONE, first + 5]
+    assert G.assert_matches_oracle(want.copy(), firsts, want, first, "made up") == (2, 3)
+    for unit, lane in ((0, 3), (1, 64), (2, 5)):
+        bad = want.copy()
+        bad[unit, lane] ^= True
+        with pytest.raises(AssertionError, match=r"'made up', %d, %d\)" % (unit, lane)):
+            G.assert_matches_oracle(bad, firsts, want, first, "made up")
+    for unit, idx in ((0, first + 71), (0, first + 69), (2, shard.NONE), (1, first)):
+        wrong = list(firsts)
+        wrong[unit] = idx
+        with pytest.raises(AssertionError, match=r"'made up', %d\)" % unit):
+            G.assert_matches_oracle(want, wrong, want, first, "made up")
