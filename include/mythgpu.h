@@ -147,6 +147,38 @@ int mg_eval_gen(mg_ctx* ctx, const mg_prog* prog, const mg_gen* gen, uint64_t n_
 int mg_search(mg_ctx* ctx, const mg_prog* prog, const mg_gen* gen, uint64_t n_cand,
               int64_t* first_sat, uint32_t* witness_leaves);
 
+/* Verdict census: over the candidates [gen->first_index, gen->first_index +
+ * n_cand), per constraint ("root") k of the program, how the search failed.
+ * No reference counterpart: it serves the misses of Constraints.is_possible
+ * (reference laser/ethereum/state/constraints.py:26-45), which reports only
+ * that no model was found.
+ * The program carries its verdict mask as probes mask_probe0 ..
+ * mask_probe0 + ceil(n_roots / 256) - 1: bit k % 256 of probe mask_probe0 +
+ * k / 256 = root k holds (mythril_amd/census.py mask_probes; bits at or
+ * above n_roots are ignored).  Per chunk of `chunk` candidates (0: 2^16;
+ * else a multiple of 256) the interpreter launch and the census kernel
+ * (mg_census.hip) are queued on the context stream; the counters stay on the
+ * device until one copy at the end.  Outputs (n_roots entries unless noted):
+ *   pass[k]        candidates on which root k holds
+ *   first_block[k] candidates whose lowest failing root is k
+ *   sole_block[k]  candidates on which root k is the only failing root
+ *   sole_index[k]  the smallest such candidate index, or -1
+ *   nfail_hist[f]  f = 0..n_roots (n_roots + 1 entries): candidates with
+ *                  exactly f failing roots
+ *   best_nfail, best_index   the minimum of (failing roots, candidate index)
+ *                  in lexicographic order; n_roots + 1 and -1 when n_cand = 0
+ * Sums and minima only: identical across runs and chunk sizes.  MG_E_ARG
+ * without a launch for: a null pointer, n_roots outside 1..1024, mask probes
+ * outside the program's probes, a chunk that is not a multiple of 256, a
+ * first_index that is not a multiple of 64 (the generator's class groups),
+ * 2^53 candidates or more, and a program whose probes need more than 256 MiB
+ * per chunk (load the census view, which writes the mask probes only).
+ * mg_last_kernel_ms covers the launches. */
+int mg_census(mg_ctx* ctx, const mg_prog* prog, const mg_gen* gen, uint64_t n_cand,
+              uint32_t n_roots, uint32_t mask_probe0, uint64_t chunk, uint64_t* pass,
+              uint64_t* first_block, uint64_t* sole_block, int64_t* sole_index,
+              uint64_t* nfail_hist, uint32_t* best_nfail, int64_t* best_index);
+
 /* Corpus batches: many programs, one launch.  Device-pointer API for
  * resident benchmarking; stream is a hipStream_t (NULL = the context's own
  * stream, which the synchronous calls also use).

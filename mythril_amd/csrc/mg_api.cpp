@@ -23,6 +23,7 @@
 #include "mg_device.h"
 #include "mg_asm_handlers.h"
 #include "mg_host.h"
+#include "mg_census.h"
 
 // the interpreter of each register layout (mg_interp_asm.hip, one
 // translation unit per layout; mg_find_layout lists them)
@@ -43,6 +44,12 @@ static mg_launch_fn layout_launch(uint32_t nreg) {
 
 hipError_t mg_launch_keccak(const uint8_t* d_data, const uint64_t* d_off, const uint32_t* d_len,
                             uint32_t n, uint8_t* d_out, hipStream_t stream);
+// verdict census of one chunk's mask probes (mg_census.hip; counter block of
+// mg_census.h): rows = the first mask probe's rows, n <= stride lanes,
+// candidate indices first.., offsets offset.. from the census's first index
+hipError_t mg_launch_census(const uint32_t* d_rows, uint64_t stride, uint64_t n, uint32_t n_roots,
+                            uint64_t first, uint64_t offset, unsigned long long* d_out,
+                            hipStream_t stream);
 
 
 struct mg_ctx {
@@ -717,6 +724,99 @@ int mg_search(mg_ctx* ctx, const mg_prog* prog, const mg_gen* gen, uint64_t n_ca
         HIPCHECK(ctx, hipMemcpyAsync(witness_leaves, run.leaves_out, leaf_b,
                                      hipMemcpyDeviceToHost, ctx->stream));
         HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    return MG_OK;
+}
+
+// Candidates per census launch when the caller names none, and the largest
+// probe buffer one chunk may need (every probe of the loaded program has a
+// row set in it, written or not).
+#define MG_CENSUS_CHUNK (1ull << 16)
+#define MG_CENSUS_MAX_PROBE_BYTES ((size_t)256 << 20)
+
+int mg_census(mg_ctx* ctx, const mg_prog* prog, const mg_gen* gen, uint64_t n_cand,
+              uint32_t n_roots, uint32_t mask_probe0, uint64_t chunk, uint64_t* pass,
+              uint64_t* first_block, uint64_t* sole_block, int64_t* sole_index,
+              uint64_t* nfail_hist, uint32_t* best_nfail, int64_t* best_index) {
+    if (!ctx || !prog || !gen || !pass || !first_block || !sole_block || !sole_index ||
+        !nfail_hist || !best_nfail || !best_index)
+        return fail(ctx, MG_E_ARG, "null argument");
+    if (n_roots < 1 || n_roots > MG_CENSUS_MAX_ROOTS)
+        return fail(ctx, MG_E_ARG, "census: n_roots %u outside 1..%u", n_roots, MG_CENSUS_MAX_ROOTS);
+    const uint32_t n_mask = (n_roots + 255) / 256;
+    if (mask_probe0 >= prog->n_probes || n_mask > prog->n_probes - mask_probe0)
+        return fail(ctx, MG_E_ARG, "census: mask probes %u..%u outside the program's %u probes",
+                    mask_probe0, mask_probe0 + n_mask - 1, prog->n_probes);
+    if (chunk == 0) chunk = MG_CENSUS_CHUNK;
+    if (chunk % MG_BLOCK_LANES)
+        return fail(ctx, MG_E_ARG, "census: chunk %llu is not a multiple of %u",
+                    (unsigned long long)chunk, MG_BLOCK_LANES);
+    if (gen->first_index % 64)
+        return fail(ctx, MG_E_ARG, "census: first_index %llu is not a multiple of 64 (the "
+                    "generator draws one class per 64 indices)",
+                    (unsigned long long)gen->first_index);
+    if (n_cand >= (1ull << MG_CENSUS_OFFSET_BITS) ||
+        gen->first_index > (uint64_t)INT64_MAX - n_cand)
+        return fail(ctx, MG_E_ARG, "census: %llu candidates from %llu: at most 2^%d, indices "
+                    "below 2^63", (unsigned long long)n_cand,
+                    (unsigned long long)gen->first_index, MG_CENSUS_OFFSET_BITS);
+    if (chunk > MG_CENSUS_MAX_PROBE_BYTES / 32 / prog->n_probes)
+        return fail(ctx, MG_E_ARG, "census: %u probes x %llu candidates per chunk exceed a %zu MiB "
+                    "probe buffer; load the census view of the program (census.census_view: "
+                    "only the mask probes are written) or pass a smaller chunk", prog->n_probes,
+                    (unsigned long long)chunk, MG_CENSUS_MAX_PROBE_BYTES >> 20);
+    for (uint32_t k = 0; k < n_roots; ++k) {
+        pass[k] = first_block[k] = sole_block[k] = nfail_hist[k] = 0;
+        sole_index[k] = -1;
+    }
+    nfail_hist[n_roots] = 0;
+    *best_nfail = n_roots + 1;
+    *best_index = -1;
+    if (n_cand == 0) return MG_OK;
+    HIPCHECK(ctx, hipSetDevice(ctx->device));
+    const uint64_t lanes = n_cand < chunk ? n_cand : chunk;       // of the largest launch
+    const size_t count_b = ((size_t)mg_census_words(n_roots) * 8 + 255) & ~(size_t)255;
+    const size_t probe_b = (size_t)prog->n_probes * 8 * lanes * 4;
+    void* ws;
+    int rc = workspace(ctx, count_b + probe_b + 256, &ws);
+    if (rc) return rc;
+    unsigned long long* d_count = (unsigned long long*)ws;
+    uint32_t* d_probes = (uint32_t*)((uint8_t*)ws + count_b);
+    const size_t sums_b = (size_t)mg_census_sole_index(n_roots) * 8;
+    HIPCHECK(ctx, hipMemsetAsync(d_count, 0, sums_b, ctx->stream));
+    HIPCHECK(ctx, hipMemsetAsync((uint8_t*)d_count + sums_b, 0xFF,
+                                 (size_t)mg_census_words(n_roots) * 8 - sums_b, ctx->stream));
+    timing_begin(ctx);
+    for (uint64_t done = 0; done < n_cand; done += chunk) {
+        mg_run run = empty_run();
+        run.n_assign = n_cand - done < chunk ? n_cand - done : chunk;
+        run.stride = run.n_assign;
+        run.probes = d_probes;
+        run.seed = gen->seed;
+        run.first_index = gen->first_index + done;
+        HIPCHECK(ctx, launch(ctx, 1, prog->d_desc, 1, run, prog->n_lds, ctx->stream));
+        HIPCHECK(ctx, mg_launch_census(d_probes + (size_t)mask_probe0 * 8 * run.stride, run.stride,
+                                       run.n_assign, n_roots, run.first_index, done, d_count,
+                                       ctx->stream));
+    }
+    timing_end(ctx);
+    std::vector<unsigned long long> h(mg_census_words(n_roots));
+    HIPCHECK(ctx, hipMemcpyAsync(h.data(), d_count, h.size() * 8, hipMemcpyDeviceToHost,
+                                 ctx->stream));
+    HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
+    timing_read(ctx);
+    for (uint32_t k = 0; k < n_roots; ++k) {
+        pass[k] = h[mg_census_pass(n_roots) + k];
+        first_block[k] = h[mg_census_first(n_roots) + k];
+        sole_block[k] = h[mg_census_sole(n_roots) + k];
+        const unsigned long long si = h[mg_census_sole_index(n_roots) + k];
+        sole_index[k] = si == ~0ull ? -1 : (int64_t)si;
+    }
+    for (uint32_t f = 0; f <= n_roots; ++f) nfail_hist[f] = h[mg_census_hist(n_roots) + f];
+    const unsigned long long best = h[mg_census_best(n_roots)];
+    if (best != ~0ull) {
+        *best_nfail = (uint32_t)(best >> MG_CENSUS_OFFSET_BITS);
+        *best_index = (int64_t)(gen->first_index + (best & ((1ull << MG_CENSUS_OFFSET_BITS) - 1)));
     }
     return MG_OK;
 }

@@ -33,7 +33,7 @@ EXPORTS = ("mg_init", "mg_init_layout", "mg_layouts", "mg_free", "mg_last_error"
            "mg_search", "mg_batch_create", "mg_batch_free", "mg_batch_eval_gen", "mg_batch_search",
            "mg_batch_search_probes", "mg_keccak256", "mg_version", "mg_config", "mg_translate",
            "mg_asm_digest", "mg_asm_digest_layout", "mg_last_kernel_ms", "mg_jit_attach",
-           "mg_jit_detach", "mg_runtime_info")
+           "mg_jit_detach", "mg_runtime_info", "mg_census")
 
 
 def layouts() -> Dict[int, Tuple[int, int]]:
@@ -115,6 +115,8 @@ def load_library(path: str = _LIB_PATH, check_digest: bool = True):
         lib.mg_eval.argtypes = [p, p, p, u64, p, p]
         lib.mg_eval_gen.argtypes = [p, p, C.POINTER(Gen), u64, p, p, p]
         lib.mg_search.argtypes = [p, p, C.POINTER(Gen), u64, C.POINTER(i64), p]
+        lib.mg_census.argtypes = [p, p, C.POINTER(Gen), u64, u32, u32, u64, p, p, p, p, p,
+                                  C.POINTER(u32), C.POINTER(i64)]
         lib.mg_batch_create.argtypes = [p, C.POINTER(p), u32, C.POINTER(p)]
         lib.mg_batch_free.argtypes = [p]
         lib.mg_batch_free.restype = None
@@ -286,6 +288,32 @@ class Engine:
         if first.value < 0:
             return -1, None
         return first.value, wit[:len(prog.leaves)]
+
+    def census(self, lp: LoadedProgram, seed: int, first_index: int, n_cand: int, n_roots: int,
+               mask_probe0: int = 0, chunk: int = 0):
+        """Per-constraint verdict census (mg_census) of the candidates
+        [first_index, first_index + n_cand) of a program that carries its
+        verdict mask as probes ``mask_probe0``.. (``census.mask_probes``; load
+        the ``census.census_view`` of a search program): a
+        :class:`mythril_amd.census.Census`.  ``first_index`` is a multiple of
+        64, ``chunk`` (candidates per launch; 0: 2^16) a multiple of 256."""
+        from .census import Census
+        n_roots = int(n_roots)
+        n = max(1, min(n_roots, 1024)) if n_roots > 0 else 1     # (the library refuses the rest)
+        u = [np.zeros(n + 1, dtype=np.uint64) for _ in range(4)]
+        sole_index = np.full(n, -1, dtype=np.int64)
+        best_nfail, best_index = C.c_uint32(0), C.c_int64(-1)
+        g = Gen(seed & (2**64 - 1), first_index)
+        rc = self.lib.mg_census(self._ctx, lp.handle, C.byref(g), n_cand, max(0, n_roots),
+                                mask_probe0, chunk, _ptr(u[0]), _ptr(u[1]), _ptr(u[2]),
+                                _ptr(sole_index), _ptr(u[3]), C.byref(best_nfail),
+                                C.byref(best_index))
+        self._check(rc, "mg_census")
+        return Census(n_roots=n_roots, first_index=first_index, n_cand=n_cand,
+                      pass_=u[0][:n].astype(np.int64), first_block=u[1][:n].astype(np.int64),
+                      sole_block=u[2][:n].astype(np.int64), sole_index=sole_index,
+                      nfail_hist=u[3].astype(np.int64), best_nfail=int(best_nfail.value),
+                      best_index=int(best_index.value), kernel_ms=self.last_kernel_ms())
 
     def witness(self, lp: LoadedProgram, seed: int, index: int):
         """Leaves and probe values of candidate ``index`` (one lane): what a

@@ -1121,6 +1121,18 @@ def filter_possible(states, constraints_of=lambda s: s.world_state.constraints):
     return [s for s, k in zip(states, keep) if k]
 
 
+def explain_miss(constraints, **kw) -> dict:
+    """Why the witness search finds no model of ``constraints`` (laser.smt
+    Bools, z3 ASTs or DAG nodes, as :func:`get_model` takes them): per
+    independent group, which constraints block it — the verdict census of
+    ``mythril_amd/census.py`` (``census.explain``; keywords ``n_cand``,
+    ``form``, ``device``, ``chunk``).  A diagnostic: it changes no memo, no
+    gate and no counter of ``SolverStatistics``, and its candidate indices
+    are those of the masked program, not of the program ``get_model`` runs."""
+    from .census import explain
+    return explain(_raw_nodes(constraints), **kw)
+
+
 def _patch_statistics(cls) -> None:
     """Mythril's ``SolverStatistics`` (a singleton, logged by ``fire_lasers``
     at ``mythril_analyzer.py:181``) prints the pre-filter's counters after

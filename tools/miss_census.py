@@ -1,24 +1,40 @@
 #!/usr/bin/env python3
-"""Which stand-in queries the batched search misses, by the shape of their
-newest constraint (the module check / JUMPI a query is about): one batched
-search per workload over its first N queries, as tools/search_bench.py
-does, then the misses grouped by model.query_shape.
-usage: tools/miss_census.py [workload] [n]"""
+"""Why the witness search misses a query.
+
+Per-constraint verdict census (mythril_amd/census.py): for
+every independent group of the query, over --candidates candidates of its
+search program, the ranked blockers (constraints no candidate satisfies, then
+the constraints that alone keep candidates from being models), each with a
+depth-3 s-expression, the pass rates, the histogram of failing constraints
+per candidate, the best candidate's failing set, and the census time next to
+the time of a plain Engine.search miss over the same count on the plain
+search program.
+
+usage: tools/miss_census.py --workload {c1,c3,c3o,c4,c5} --query N
+                            [--candidates K] [--json] [--split-and]
+       tools/miss_census.py --known-misses [--candidates K] [--json] [--split-and]
+           every entry of tests/golden/recall_known_miss.json and c3o query 50
+       tools/miss_census.py [workload] [n]
+           the older census: which of a stream's first n queries the batched
+           search misses, grouped by the shape of their newest constraint
+"""
+import argparse
 import collections
 import json
 import os
 import sys
+import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
+GOLDEN = os.path.join(ROOT, "tests", "golden")
 
-def main():
+
+def by_shape(wl, n):
     import mythril_amd.model as M
     from mythril_amd import workloads as W
     from mythril_amd.engine import get_engine
-    wl = sys.argv[1] if len(sys.argv) > 1 else "c4"
-    n = int(sys.argv[2]) if len(sys.argv) > 2 else 64
     eng = get_engine(0)
     qs = W.queries(wl, n)
     progs, qmap = [], []
@@ -42,6 +58,139 @@ def main():
                       "first_index_median": idx[len(idx) // 2] if idx else None,
                       "first_index_max": idx[-1] if idx else None,
                       "missed_by_shape": census.most_common()}, indent=1))
+
+
+def stream_query(wl, i):
+    """Query ``i`` of a stream as the recall labels index it."""
+    from mythril_amd import workloads as W
+    n = json.load(open(os.path.join(GOLDEN, "recall_labels.json")))["n"]
+    return W.queries(wl, max(n, i + 1))[i]
+
+
+def plain_search_miss(group, n_cand, device=0):
+    """(first index or -1, device ms, wall ms) of Engine.search over
+    ``n_cand`` candidates of the group's plain search program."""
+    import mythril_amd.model as M
+    from mythril_amd.engine import get_engine
+    prog = group["plain_program"]
+    eng = get_engine(device, nreg=prog.nreg)
+    lp = eng.load(prog, M.search_leafgen(prog), prog_seed=0)
+    t0 = time.perf_counter()
+    idx, _ = eng.search(lp, M.SEARCH_SEED, n_cand)
+    return idx, eng.last_kernel_ms(), (time.perf_counter() - t0) * 1e3
+
+
+def report(wl, qi, n_cand, split_and=False):
+    """The JSON-able miss report of one stream query; ``split_and``: of the
+    query with every top-level ``and`` replaced by its conjuncts (which half
+    of a blocking constraint fails), ``labels`` naming each row "i.j" =
+    conjunct j of constraint i."""
+    from mythril_amd import census as CS
+    from mythril_amd.smt import node as N
+    q = stream_query(wl, qi)
+    labels = [str(i) for i in range(len(q))]
+    if split_and:
+        parts = [(list(c.args) if c.op == "and" else [c]) for c in q]
+        labels = ["%d.%d" % (i, j) if len(ps) > 1 else str(i)
+                  for i, ps in enumerate(parts) for j in range(len(ps))]
+        q = [p for ps in parts for p in ps]
+    t0 = time.perf_counter()
+    rep = CS.explain(q, n_cand=n_cand, form="search")
+    out = {"workload": wl, "query": qi, "constraints": len(q), "candidates": n_cand,
+           "split_and": split_and, "labels": labels,
+           "explain_wall_ms": round((time.perf_counter() - t0) * 1e3, 1), "groups": []}
+    for g in rep["groups"]:
+        row = {"status": g["status"], "constraints": g["constraints"]}
+        if "why" in g:
+            row["why"] = g["why"]
+        if g["status"] == CS.CENSUS:
+            c = g["census"]
+            pos = g["constraints"]
+            k_of = {p: k for k, p in enumerate(pos)}
+            row["records"] = g["records"]
+            row["plain_records"] = g["plain_records"]
+            row["n_sat"] = c.n_sat
+            row["blockers"] = [
+                {"constraint": p, "label": labels[p], "pass": int(c.pass_[k_of[p]]),
+                 "pass_rate": round(int(c.pass_[k_of[p]]) / max(1, c.n_cand), 6),
+                 "first_block": int(c.first_block[k_of[p]]),
+                 "sole_block": int(c.sole_block[k_of[p]]),
+                 "sole_index": int(c.sole_index[k_of[p]]),
+                 "sexpr": N.to_sexpr(q[p], 3)} for p in g["blockers"]]
+            row["pass_rates"] = {str(p): round(int(c.pass_[k]) / max(1, c.n_cand), 6)
+                                 for k, p in enumerate(pos)}
+            row["nfail_hist"] = {str(f): int(v) for f, v in enumerate(c.nfail_hist) if v}
+            if "best" in g:
+                a = g["best"]["assignment"]
+                row["best"] = {"index": g["best"]["index"], "nfail": g["best"]["nfail"],
+                               "failing": g["best"]["failing"],
+                               "vars": {k: hex(v) for k, v in sorted(a.vars.items())}}
+            idx, ms, wall = plain_search_miss(g, n_cand)
+            row["census_kernel_ms"] = round(c.kernel_ms, 3)
+            row["plain_search"] = {"first_index": idx, "kernel_ms": round(ms, 3),
+                                   "wall_ms": round(wall, 3)}
+        out["groups"].append(row)
+    return out
+
+
+def show(r):
+    print("== %s query %d%s: %d constraints, %d candidates per group (%.0f ms in all)" % (
+        r["workload"], r["query"], " (top-level ands split, i.j = conjunct j of constraint i)"
+        if r["split_and"] else "", r["constraints"], r["candidates"], r["explain_wall_ms"]))
+    lab = r["labels"]
+    for gi, g in enumerate(r["groups"]):
+        print(" group %d: %d constraints %s -> %s%s" % (
+            gi, len(g["constraints"]),
+            " ".join([lab[p] for p in g["constraints"][:12]] + ["..."] * (len(g["constraints"]) > 12)),
+            g["status"], (" (%s)" % g["why"]) if "why" in g else ""))
+        if "blockers" not in g:
+            continue
+        print("  program: %d records with the mask (%d plain); satisfying candidates: %d" % (
+            g["records"], g["plain_records"], g["n_sat"]))
+        print("  census %.3f ms on the device; plain search miss %.3f ms (first index %d)" % (
+            g["census_kernel_ms"], g["plain_search"]["kernel_ms"], g["plain_search"]["first_index"]))
+        print("  blockers (worst first):")
+        for b in g["blockers"]:
+            print("   #%-5s pass %8d (%.4f)  first %8d  sole %8d  %s" % (
+                b["label"], b["pass"], b["pass_rate"], b["first_block"], b["sole_block"],
+                b["sexpr"]))
+        always = [lab[int(p)] for p, v in g["pass_rates"].items() if v == 1.0]
+        print("  always hold: %s" % " ".join(always))
+        print("  failing constraints per candidate: %s" % "  ".join(
+            "%s: %d" % fv for fv in g["nfail_hist"].items()))
+        if "best" in g:
+            print("  best candidate: index %d, %d failing: %s" % (
+                g["best"]["index"], g["best"]["nfail"],
+                " ".join(lab[p] for p in g["best"]["failing"])))
+
+
+def main():
+    if len(sys.argv) > 1 and not sys.argv[1].startswith("-"):
+        return by_shape(sys.argv[1], int(sys.argv[2]) if len(sys.argv) > 2 else 64)
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--workload", choices=["c1", "c3", "c3o", "c4", "c5"])
+    ap.add_argument("--query", type=int)
+    ap.add_argument("--known-misses", action="store_true")
+    ap.add_argument("--candidates", type=int, default=1 << 16)
+    ap.add_argument("--json", action="store_true")
+    ap.add_argument("--split-and", action="store_true",
+                    help="census the query with every top-level `and` split into its conjuncts")
+    a = ap.parse_args()
+    if a.known_misses:
+        known = json.load(open(os.path.join(GOLDEN, "recall_known_miss.json")))
+        jobs = sorted({(wl, int(i)) for wl, rows in known.items() for i in rows} | {("c3o", 50)})
+    elif a.workload is not None and a.query is not None:
+        jobs = [(a.workload, a.query)]
+    elif len(sys.argv) == 1:
+        return by_shape("c4", 64)
+    else:
+        ap.error("give --workload and --query, or --known-misses")
+    reports = [report(wl, qi, a.candidates, a.split_and) for wl, qi in jobs]
+    if a.json:
+        print(json.dumps(reports, indent=1))
+    else:
+        for r in reports:
+            show(r)
 
 
 if __name__ == "__main__":
