@@ -179,6 +179,50 @@ int mg_census(mg_ctx* ctx, const mg_prog* prog, const mg_gen* gen, uint64_t n_ca
               uint64_t* first_block, uint64_t* sole_block, int64_t* sole_index,
               uint64_t* nfail_hist, uint32_t* best_nfail, int64_t* best_index);
 
+/* Local search from a nearly satisfying assignment, e.g.
+ * the census's best candidate.  No reference counterpart: like the census it
+ * serves the misses of Constraints.is_possible (reference
+ * laser/ethereum/state/constraints.py:26-45), where the candidate stream
+ * keeps landing one or two constraints short of a model and every candidate
+ * is a fresh draw.
+ * The program carries its verdict mask as probes mask_probe0 .. (as for
+ * mg_census).  Per round, on the context stream and with no host round trip:
+ * `lanes` neighbours of the base assignment are written on the device (lane 0
+ * is the base, the lower half differs from it by one move, the upper half by
+ * two; csrc/mg_repair.h is the move function, mythril_amd/repair.py its
+ * specification), the interpreter evaluates their verdict masks in eval
+ * mode, and the neighbour with the fewest failing roots (ties: the lowest
+ * lane) becomes the base when it fails strictly fewer than the base does.
+ * After every sync_every rounds (0: 8) the host reads the base's failing
+ * count and stops at 0 or after max_rounds.  Outputs:
+ *   out_leaves [n_leaves][8]  the last base
+ *   out_nfail                 its failing roots (0: it satisfies every root)
+ *   out_rounds                rounds run
+ *   trace [max_rounds] or NULL: the fewest failing roots of each round run
+ *                             (0 beyond out_rounds)
+ * A function of the arguments alone: identical across runs.  MG_E_ARG without
+ * a launch for: a null pointer other than trace, a program with no leaves,
+ * n_roots outside 1..1024, mask probes outside the program's probes, lanes
+ * outside 1..2^20, max_rounds outside 1..2^16, and a program whose probes
+ * need more than 256 MiB (load the census view).  mg_last_kernel_ms covers
+ * the rounds. */
+int mg_repair(mg_ctx* ctx, const mg_prog* prog, const uint32_t* start_leaves /*[n_leaves][8]*/,
+              uint32_t n_roots, uint32_t mask_probe0, uint64_t seed, uint32_t lanes,
+              uint32_t max_rounds, uint32_t sync_every,
+              uint32_t* out_leaves /*[n_leaves][8]*/, uint32_t* out_nfail,
+              uint32_t* out_rounds, uint32_t* trace /*[max_rounds] or NULL*/);
+/* Host-only (no GPU): the neighbours mg_repair's round r writes for lanes
+ * lane0 .. lane0 + n_lanes - 1 of `lanes`, from the same move function:
+ * out [n_leaves][8][n_lanes]; moves ([n_lanes][4] or NULL): the number of
+ * moves, kind of move 0 | kind of move 1 << 8, leaf of move 0, leaf of move
+ * 1.  MG_E_ARG for a null pointer, no leaves, a width outside 1..256, a pool
+ * outside the constants, a base value beyond its width, lanes outside
+ * 1..2^20, r at or above 2^16 and a lane range outside lanes. */
+int mg_repair_mutate_host(const mg_leafgen* leaves, uint32_t n_leaves, const uint32_t* consts,
+                          uint32_t n_consts, const uint32_t* base /*[n_leaves][8]*/,
+                          uint64_t seed, uint32_t r, uint32_t lanes, uint32_t lane0,
+                          uint32_t n_lanes, uint32_t* out, uint32_t* moves);
+
 /* Corpus batches: many programs, one launch.  Device-pointer API for
  * resident benchmarking; stream is a hipStream_t (NULL = the context's own
  * stream, which the synchronous calls also use).

@@ -24,6 +24,7 @@
 #include "mg_asm_handlers.h"
 #include "mg_host.h"
 #include "mg_census.h"
+#include "mg_repair.h"
 
 // the interpreter of each register layout (mg_interp_asm.hip, one
 // translation unit per layout; mg_find_layout lists them)
@@ -50,6 +51,19 @@ hipError_t mg_launch_keccak(const uint8_t* d_data, const uint64_t* d_off, const 
 hipError_t mg_launch_census(const uint32_t* d_rows, uint64_t stride, uint64_t n, uint32_t n_roots,
                             uint64_t first, uint64_t offset, unsigned long long* d_out,
                             hipStream_t stream);
+// one round of the local search (mg_repair.hip): the neighbours of the base
+// into the interpreter's eval-mode input; then, after the interpreter wrote
+// their verdict masks (rows = the first mask probe's rows, stride lanes), the
+// best neighbour into the base and its failing roots into trace[r]
+hipError_t mg_launch_repair_round(uint32_t* d_base, const mg_leafgen* d_gen,
+                                  const uint32_t* d_consts, uint32_t n_leaves, uint64_t seed,
+                                  uint32_t r, uint32_t lanes, uint32_t* d_leaves,
+                                  hipStream_t stream);
+hipError_t mg_launch_repair_pick(const uint32_t* d_rows, uint32_t lanes, uint32_t n_roots,
+                                 uint32_t* d_base, const mg_leafgen* d_gen,
+                                 const uint32_t* d_consts, uint32_t n_leaves, uint64_t seed,
+                                 uint32_t r, mg_repair_state* d_state, uint32_t* d_trace,
+                                 hipStream_t stream);
 
 
 struct mg_ctx {
@@ -125,6 +139,7 @@ struct mg_prog {
     mg_pdesc h_desc;                // host copy (batches copy it from here)
     uint32_t n_ins = 0, n_consts = 0, n_leaves = 0, n_lds = 0, n_probes = 0;
     uint64_t rec_fp = 0;            // records' fingerprint (rec_fingerprint)
+    std::vector<mg_leafgen> leafgen;   // as loaded (mg_repair's move function reads it)
 };
 
 // Fingerprint of a program's records with HANDLER IDS in word 0 (the
@@ -580,6 +595,7 @@ int mg_load_program(mg_ctx* ctx, const uint32_t* code, uint32_t n_ins, const uin
     p->n_leaves = n_leaves;
     p->n_lds = n_lds_slots;
     p->n_probes = n_probes;
+    p->leafgen.assign(leaves, leaves + n_leaves);
     *out = p;
     return MG_OK;
 }
@@ -817,6 +833,131 @@ int mg_census(mg_ctx* ctx, const mg_prog* prog, const mg_gen* gen, uint64_t n_ca
     if (best != ~0ull) {
         *best_nfail = (uint32_t)(best >> MG_CENSUS_OFFSET_BITS);
         *best_index = (int64_t)(gen->first_index + (best & ((1ull << MG_CENSUS_OFFSET_BITS) - 1)));
+    }
+    return MG_OK;
+}
+
+// The local search.  Rounds are queued back to back; after
+// every sync_every rounds the host reads the base's failing count (8 bytes)
+// and stops at 0.
+int mg_repair(mg_ctx* ctx, const mg_prog* prog, const uint32_t* start_leaves, uint32_t n_roots,
+              uint32_t mask_probe0, uint64_t seed, uint32_t lanes, uint32_t max_rounds,
+              uint32_t sync_every, uint32_t* out_leaves, uint32_t* out_nfail,
+              uint32_t* out_rounds, uint32_t* trace) {
+    if (!ctx || !prog || !start_leaves || !out_leaves || !out_nfail || !out_rounds)
+        return fail(ctx, MG_E_ARG, "null argument");
+    if (prog->n_leaves == 0) return fail(ctx, MG_E_ARG, "repair: the program has no leaves");
+    if (n_roots < 1 || n_roots > MG_CENSUS_MAX_ROOTS)
+        return fail(ctx, MG_E_ARG, "repair: n_roots %u outside 1..%u", n_roots, MG_CENSUS_MAX_ROOTS);
+    const uint32_t n_mask = (n_roots + 255) / 256;
+    if (mask_probe0 >= prog->n_probes || n_mask > prog->n_probes - mask_probe0)
+        return fail(ctx, MG_E_ARG, "repair: mask probes %u..%u outside the program's %u probes",
+                    mask_probe0, mask_probe0 + n_mask - 1, prog->n_probes);
+    if (lanes < 1 || lanes > MG_REPAIR_MAX_LANES)
+        return fail(ctx, MG_E_ARG, "repair: %u lanes outside 1..%u", lanes, MG_REPAIR_MAX_LANES);
+    if (max_rounds < 1 || max_rounds > MG_REPAIR_MAX_ROUNDS)
+        return fail(ctx, MG_E_ARG, "repair: %u rounds outside 1..%u", max_rounds,
+                    MG_REPAIR_MAX_ROUNDS);
+    if (lanes > MG_CENSUS_MAX_PROBE_BYTES / 32 / prog->n_probes)
+        return fail(ctx, MG_E_ARG, "repair: %u probes x %u lanes exceed a %zu MiB probe buffer; "
+                    "load the census view of the program (census.census_view: only the mask "
+                    "probes are written) or pass fewer lanes", prog->n_probes, lanes,
+                    MG_CENSUS_MAX_PROBE_BYTES >> 20);
+    if (sync_every == 0) sync_every = 8;
+    HIPCHECK(ctx, hipSetDevice(ctx->device));
+    auto align = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const uint32_t n_leaves = prog->n_leaves;
+    const uint64_t words = ((uint64_t)lanes + 63) / 64;
+    const size_t base_b = (size_t)n_leaves * 32, gen_b = (size_t)n_leaves * sizeof(mg_leafgen),
+                 trace_b = (size_t)max_rounds * 4, root_b = words * 8,
+                 leaf_b = (size_t)n_leaves * 8 * lanes * 4,
+                 probe_b = (size_t)prog->n_probes * 8 * lanes * 4;
+    const size_t off_base = 256, off_gen = off_base + align(base_b),
+                 off_trace = off_gen + align(gen_b), off_root = off_trace + align(trace_b),
+                 off_leaf = off_root + align(root_b), off_probe = off_leaf + align(leaf_b),
+                 total = off_probe + align(probe_b);
+    void* ws;
+    int rc = workspace(ctx, total + 256, &ws);
+    if (rc) return rc;
+    uint8_t* w = (uint8_t*)ws;
+    mg_repair_state* d_state = (mg_repair_state*)w;
+    uint32_t* d_base = (uint32_t*)(w + off_base);
+    mg_leafgen* d_gen = (mg_leafgen*)(w + off_gen);
+    uint32_t* d_trace = (uint32_t*)(w + off_trace);
+    uint32_t* d_leaves = (uint32_t*)(w + off_leaf);
+    uint32_t* d_probes = (uint32_t*)(w + off_probe);
+    HIPCHECK(ctx, hipMemsetAsync(d_state, 0xFF, sizeof(mg_repair_state), ctx->stream));
+    HIPCHECK(ctx, hipMemsetAsync(d_trace, 0, trace_b, ctx->stream));
+    HIPCHECK(ctx, hipMemcpyAsync(d_base, start_leaves, base_b, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHECK(ctx, hipMemcpyAsync(d_gen, prog->leafgen.data(), gen_b, hipMemcpyHostToDevice,
+                                 ctx->stream));
+    mg_run run = empty_run();
+    run.leaves = d_leaves;
+    run.root_bits = (uint64_t*)(w + off_root);
+    run.probes = d_probes;
+    run.stride = lanes;
+    run.n_assign = lanes;
+    run.words_per_prog = words;
+    const uint32_t* d_rows = d_probes + (size_t)mask_probe0 * 8 * lanes;
+    const uint32_t* d_consts = prog->h_desc.consts;       // the first n_consts entries: as loaded
+    uint32_t h_state[2] = {~0u, 0};                       // base_nfail, rounds
+    timing_begin(ctx);
+    uint32_t r = 0;
+    while (r < max_rounds && h_state[0] != 0) {
+        const uint32_t stop = max_rounds - r < sync_every ? max_rounds : r + sync_every;
+        for (; r < stop; ++r) {
+            HIPCHECK(ctx, mg_launch_repair_round(d_base, d_gen, d_consts, n_leaves, seed, r, lanes,
+                                                 d_leaves, ctx->stream));
+            HIPCHECK(ctx, launch(ctx, 0, prog->d_desc, 1, run, prog->n_lds, ctx->stream));
+            HIPCHECK(ctx, mg_launch_repair_pick(d_rows, lanes, n_roots, d_base, d_gen, d_consts,
+                                                n_leaves, seed, r, d_state, d_trace, ctx->stream));
+        }
+        timing_end(ctx);
+        HIPCHECK(ctx, hipMemcpyAsync(h_state, &d_state->base_nfail, 8, hipMemcpyDeviceToHost,
+                                     ctx->stream));
+        HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    timing_read(ctx);
+    HIPCHECK(ctx, hipMemcpyAsync(out_leaves, d_base, base_b, hipMemcpyDeviceToHost, ctx->stream));
+    if (trace)
+        HIPCHECK(ctx, hipMemcpyAsync(trace, d_trace, trace_b, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
+    *out_nfail = h_state[0];
+    *out_rounds = r;
+    return MG_OK;
+}
+
+// Host only: lanes lane0 .. lane0 + n_lanes - 1 of round r of the move
+// function (mg_repair.h), as the mutate kernel writes them.
+int mg_repair_mutate_host(const mg_leafgen* leaves, uint32_t n_leaves, const uint32_t* consts,
+                          uint32_t n_consts, const uint32_t* base, uint64_t seed, uint32_t r,
+                          uint32_t lanes, uint32_t lane0, uint32_t n_lanes, uint32_t* out,
+                          uint32_t* moves) {
+    if (!leaves || !base || !out || (n_consts && !consts) || n_leaves == 0) return MG_E_ARG;
+    if (lanes < 1 || lanes > MG_REPAIR_MAX_LANES || r >= MG_REPAIR_MAX_ROUNDS) return MG_E_ARG;
+    if (lane0 > lanes || n_lanes > lanes - lane0) return MG_E_ARG;
+    for (uint32_t i = 0; i < n_leaves; ++i) {
+        if (leaves[i].width < 1 || leaves[i].width > MG_MAX_WIDTH) return MG_E_ARG;
+        if ((uint64_t)leaves[i].pool_off + leaves[i].pool_n > n_consts) return MG_E_ARG;
+        uint32_t v[8];
+        memcpy(v, base + (size_t)i * 8, 32);
+        mg_repair_mask(v, leaves[i].width);
+        if (memcmp(v, base + (size_t)i * 8, 32)) return MG_E_ARG;     // a base beyond its width
+    }
+    for (uint32_t a = 0; a < n_lanes; ++a) {
+        mg_repair_moves mv;
+        mg_repair_lane(base, leaves, consts, n_leaves, seed, r, lane0 + a, lanes, &mv);
+        for (uint32_t leaf = 0; leaf < n_leaves; ++leaf) {
+            uint32_t v[8];
+            mg_repair_leaf(base, mv, mv.n, leaf, v);
+            for (uint32_t k = 0; k < 8; ++k) out[((size_t)leaf * 8 + k) * n_lanes + a] = v[k];
+        }
+        if (moves) {
+            moves[4 * (size_t)a] = mv.n;
+            moves[4 * (size_t)a + 1] = mv.kind[0] | mv.kind[1] << 8;
+            moves[4 * (size_t)a + 2] = mv.leaf[0];
+            moves[4 * (size_t)a + 3] = mv.leaf[1];
+        }
     }
     return MG_OK;
 }

@@ -33,7 +33,7 @@ EXPORTS = ("mg_init", "mg_init_layout", "mg_layouts", "mg_free", "mg_last_error"
            "mg_search", "mg_batch_create", "mg_batch_free", "mg_batch_eval_gen", "mg_batch_search",
            "mg_batch_search_probes", "mg_keccak256", "mg_version", "mg_config", "mg_translate",
            "mg_asm_digest", "mg_asm_digest_layout", "mg_last_kernel_ms", "mg_jit_attach",
-           "mg_jit_detach", "mg_runtime_info", "mg_census")
+           "mg_jit_detach", "mg_runtime_info", "mg_census", "mg_repair", "mg_repair_mutate_host")
 
 
 def layouts() -> Dict[int, Tuple[int, int]]:
@@ -117,6 +117,9 @@ def load_library(path: str = _LIB_PATH, check_digest: bool = True):
         lib.mg_search.argtypes = [p, p, C.POINTER(Gen), u64, C.POINTER(i64), p]
         lib.mg_census.argtypes = [p, p, C.POINTER(Gen), u64, u32, u32, u64, p, p, p, p, p,
                                   C.POINTER(u32), C.POINTER(i64)]
+        lib.mg_repair.argtypes = [p, p, p, u32, u32, u64, u32, u32, u32, p, C.POINTER(u32),
+                                  C.POINTER(u32), p]
+        lib.mg_repair_mutate_host.argtypes = [p, u32, p, u32, p, u64, u32, u32, u32, u32, p, p]
         lib.mg_batch_create.argtypes = [p, C.POINTER(p), u32, C.POINTER(p)]
         lib.mg_batch_free.argtypes = [p]
         lib.mg_batch_free.restype = None
@@ -315,6 +318,31 @@ class Engine:
                       nfail_hist=u[3].astype(np.int64), best_nfail=int(best_nfail.value),
                       best_index=int(best_index.value), kernel_ms=self.last_kernel_ms())
 
+    def repair(self, lp: LoadedProgram, start_leaves: np.ndarray, n_roots: int, seed: int,
+               lanes: int = 4096, max_rounds: int = 64, sync_every: int = 8,
+               mask_probe0: int = 0):
+        """Greedy local search (mg_repair) from ``start_leaves``
+        ((n_leaves, 8) u32) on a program that carries its verdict mask as
+        probes ``mask_probe0``.. (load the ``census.census_view``): a
+        :class:`mythril_amd.repair.RepairResult` — the last base, its failing
+        constraints, the rounds run and each round's fewest failing
+        constraints."""
+        from .repair import RepairResult
+        n_leaves = len(lp.program.leaves)
+        start = np.ascontiguousarray(start_leaves, dtype=np.uint32)
+        if start.shape != (n_leaves, 8):
+            raise ValueError("start_leaves must be (n_leaves, 8)")
+        out = np.zeros((max(1, n_leaves), 8), dtype=np.uint32)
+        trace = np.zeros(max(1, min(int(max_rounds), 1 << 16)), dtype=np.uint32)
+        nfail, rounds = C.c_uint32(0), C.c_uint32(0)
+        rc = self.lib.mg_repair(self._ctx, lp.handle, _ptr(start) if n_leaves else _ptr(out),
+                                max(0, int(n_roots)), mask_probe0, seed & (2**64 - 1), lanes,
+                                max_rounds, sync_every, _ptr(out), C.byref(nfail),
+                                C.byref(rounds), _ptr(trace))
+        self._check(rc, "mg_repair")
+        return RepairResult(out[:n_leaves], int(nfail.value), int(rounds.value), trace,
+                            self.last_kernel_ms())
+
     def witness(self, lp: LoadedProgram, seed: int, index: int):
         """Leaves and probe values of candidate ``index`` (one lane): what a
         solve-mode program's model needs besides the generated leaves."""
@@ -454,6 +482,28 @@ def handler_variants(program: Program, lds_slots: Optional[int] = None):
             aop, var = c // (2 * asmgen.NVAR), (c // 2) % asmgen.NVAR
             out.add((asmgen.AOPS[aop], var))
     return out
+
+
+def repair_mutate_host(leafgen: Sequence[LeafGen], consts: np.ndarray, base: np.ndarray, seed: int,
+                       r: int, lanes: int, lane0: int = 0, n_lanes: Optional[int] = None):
+    """Host-only (no GPU): ``(neighbours (n_leaves, 8, n_lanes) u32, moves
+    (n_lanes, 4) u32)`` of lanes ``lane0``.. of round ``r`` from the library's
+    own move function (mg_repair_mutate_host; ``repair.mutate_ref`` is its
+    specification)."""
+    lib = load_library()
+    gens = list(leafgen)
+    garr = (LeafGen * max(1, len(gens)))(*gens)
+    consts = np.ascontiguousarray(consts, dtype=np.uint32).reshape(-1, 8)
+    base = np.ascontiguousarray(base, dtype=np.uint32)
+    n_lanes = lanes - lane0 if n_lanes is None else n_lanes
+    out = np.zeros((max(1, len(gens)), 8, max(1, n_lanes)), dtype=np.uint32)
+    moves = np.zeros((max(1, n_lanes), 4), dtype=np.uint32)
+    rc = lib.mg_repair_mutate_host(C.cast(garr, C.c_void_p), len(gens), _ptr(consts),
+                                   consts.shape[0], _ptr(base), seed & (2**64 - 1), r, lanes,
+                                   lane0, n_lanes, _ptr(out), _ptr(moves))
+    if rc != 0:
+        raise EngineError("mg_repair_mutate_host failed (%d)" % rc)
+    return out[:len(gens), :, :n_lanes], moves[:n_lanes]
 
 
 def unpack_bits(bits: np.ndarray, n: int) -> np.ndarray:

@@ -117,9 +117,16 @@ class SolverStatistics:
         self.ground_true = 0            # groups folded to true: answered without a launch
         self.ground_false = 0           # queries with a group folded to false: not searched
         self.refuted = 0                # queries refuted on the host (refute.py): not compiled
+        self.repair_attempts = 0        # missed groups handed to the local search (repair.py)
+        self.repair_hits = 0            # ... that it turned into a witness
         self.phase = {k: 0.0 for k in PHASES}
 
     def gpu_report(self) -> str:
+        return self._gpu_report() + (
+            "\nGPU repair: attempts: {} hits: {}".format(self.repair_attempts, self.repair_hits)
+            if self.repair_attempts or self.repair_hits else "")
+
+    def _gpu_report(self) -> str:
         return ("GPU pre-filter: queries: {} hits: {} fallbacks: {} unsupported: {} errors: {} "
                 "rejected by z3: {} memo misses: {} compile-gated: {} shape-skipped: {} "
                 "refuted: {}\n"
@@ -181,6 +188,9 @@ GPU_ENABLED = True
 # that shape is searched
 SHAPE_GATE = True
 REFUTE = True              # host refutation before compiling (refute.py)
+# opt-in (MYTHRIL_GPU_REPAIR=1): a group the search missed is handed to the
+# local search (repair.py) while search budget remains
+REPAIR = False
 SHAPE_MIN, SHAPE_FLOOR, SHAPE_PROBE = 4, 1.0 / 16, 8
 
 
@@ -191,8 +201,10 @@ def configure_from_env(env=None) -> None:
     ``MYTHRIL_GPU_CANDIDATES`` the candidates per query (a power of two),
     ``MYTHRIL_GPU_BUDGET_MS`` the share of a query's timeout the search may
     take, ``MYTHRIL_GPU_ADAPTIVE=0`` turns the per-shape gate off,
-    ``MYTHRIL_GPU_REFUTE=0`` the host refutation (refute.py)."""
-    global GPU_ENABLED, DEVICES, SEARCH_CANDIDATES, SEARCH_BUDGET_MS, SHAPE_GATE, REFUTE
+    ``MYTHRIL_GPU_REFUTE=0`` the host refutation (refute.py),
+    ``MYTHRIL_GPU_REPAIR=1`` turns the local search of missed groups on
+    (repair.py; off by default)."""
+    global GPU_ENABLED, DEVICES, SEARCH_CANDIDATES, SEARCH_BUDGET_MS, SHAPE_GATE, REFUTE, REPAIR
     import os
     env = os.environ if env is None else env
     GPU_ENABLED = env.get("MYTHRIL_GPU", "1").strip().lower() not in ("0", "off", "false", "no")
@@ -207,6 +219,7 @@ def configure_from_env(env=None) -> None:
     SHAPE_GATE = env.get("MYTHRIL_GPU_ADAPTIVE", "1").strip().lower() not in ("0", "off", "false",
                                                                              "no")
     REFUTE = env.get("MYTHRIL_GPU_REFUTE", "1").strip().lower() not in ("0", "off", "false", "no")
+    REPAIR = env.get("MYTHRIL_GPU_REPAIR", "0").strip().lower() in ("1", "on", "true", "yes")
 
 
 configure_from_env()
@@ -748,6 +761,7 @@ def gpu_search(nodes: Sequence[N.Node], budget_ms: float):
     no host round trip (mg_search / mg_batch_search).  The group-miss memo
     answers repeated (or extended) missed groups at once, and a query whose
     estimated compile time exceeds the budget is not searched."""
+    t_start = time.perf_counter()
     buckets, sizes = dependence_buckets_sized(nodes)
     keys = [_group_key(b) for b in buckets]
     if any(_known_miss(k, SEARCH_CANDIDATES) for k in keys):
@@ -794,6 +808,8 @@ def gpu_search(nodes: Sequence[N.Node], budget_ms: float):
             _count_kernel(eng)
             hits = [(h[0], _witness(eng, lp, h) if h[0] >= 0 else None)]
     stats.gpu_candidates += sum(n_cand if i < 0 else i + 1 for i, _ in hits)
+    if REPAIR and any(i < 0 for i, _ in hits):
+        hits = _repair_misses(buckets, hits, budget_ms, t_start)
     for k, (i, _) in zip(keys, hits):
         if i < 0:
             _note_miss(k, n_cand)
@@ -801,6 +817,29 @@ def gpu_search(nodes: Sequence[N.Node], budget_ms: float):
     if any(i < 0 for i, _ in hits):
         return None
     return _merge([a for _, a in hits]), progs
+
+
+def _repair_misses(buckets, hits, budget_ms: float, t_start: float):
+    """``hits`` with every missed group the local search repairs
+    (``repair.repair_group``, MYTHRIL_GPU_REPAIR=1) replaced by (0, its
+    assignment), as long as search budget remains; stops at the first group
+    it cannot repair (the query is a miss then).  The witness goes through
+    ``_accept`` like any other."""
+    from .repair import REPAIRED, repair_group
+    out = list(hits)
+    for k, (b, (i, _)) in enumerate(zip(buckets, hits)):
+        if i >= 0:
+            continue
+        if (time.perf_counter() - t_start) * 1e3 >= budget_ms:
+            break
+        stats.repair_attempts += 1
+        with _Phase("search"):
+            g = repair_group(b, device=(list(DEVICES) or [0])[0])
+        if g["status"] != REPAIRED:
+            break
+        stats.repair_hits += 1
+        out[k] = (0, g["assignment"])
+    return out
 
 
 # Set by install(): the reference's own Optimize wrapper
@@ -1131,6 +1170,16 @@ def explain_miss(constraints, **kw) -> dict:
     are those of the masked program, not of the program ``get_model`` runs."""
     from .census import explain
     return explain(_raw_nodes(constraints), **kw)
+
+
+def repair_miss(constraints, **kw) -> dict:
+    """Census, then local search from its best candidate, per independent
+    group of ``constraints`` (``mythril_amd/repair.py`` ``repair``; keywords
+    ``n_cand``, ``form``, ``lanes``, ``max_rounds``, ``device``): ``groups``
+    and, when every group was repaired, the joined ``model``.  Touches no
+    memo, gate or counter; the model is not verified by z3 here."""
+    from .repair import repair
+    return repair(_raw_nodes(constraints), **kw)
 
 
 def _patch_statistics(cls) -> None:

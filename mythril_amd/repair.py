@@ -1,0 +1,264 @@
+"""Greedy local search from a missed search's best candidate.
+
+The witness search draws every candidate afresh, so it never looks at a
+neighbour of a candidate that came close.  The census (``census.py``) names
+that candidate; this module walks from it: per round, ``lanes`` neighbours of
+the current base assignment — one or two leaves changed by a small move — are
+evaluated, and the neighbour with the fewest failing constraints becomes the
+next base if it fails strictly fewer than the base does.  The loop runs on
+the device (``mg_repair``, ``csrc/mg_repair.hip``); :func:`mutate_ref` is the
+specification of its move function (``csrc/mg_repair.h``) and
+:func:`repair_ref` of the loop, bit for bit.
+
+Soundness is the caller's as for any witness: :func:`repair_group` accepts an
+assignment only after one fresh evaluation of the full masked program shows
+the root and every mask bit set, and ``get_model`` still verifies it with z3.
+"""
+
+from __future__ import annotations
+
+from dataclasses import dataclass
+from typing import Callable, List, Optional, Sequence
+
+import numpy as np
+
+M64 = (1 << 64) - 1
+# the constants of csrc/mg_repair.h
+CR, CJ, CD = 0xD6E8FEB86659FD93, 0xA0761D6478BD642F, 0xE7037ED1A0B428DB
+GOLD, MIX = 0x9E3779B97F4A7C15, 0xBF58476D1CE4E5B9
+KINDS = 6
+FLIP, STEP, BYTE, LIMB, POOL, COPY = range(KINDS)
+MAX_LANES, MAX_ROUNDS = 1 << 20, 1 << 16
+
+
+def _hash(seed: int, r: int, j: np.ndarray, draw: int) -> np.ndarray:
+    """The generator's v9 mix of (seed, r, j, draw): u64 per lane."""
+    with np.errstate(over="ignore"):
+        s = (np.uint64(seed & M64) ^ np.uint64((r * CR) & M64) ^ (j.astype(np.uint64) * np.uint64(CJ))
+             ^ np.uint64(((draw + 1) * CD) & M64))
+        s = s + np.uint64(GOLD)
+        z = (s ^ (s >> np.uint64(32))) * np.uint64(MIX)
+        return z ^ (z >> np.uint64(32))
+
+
+def _mulhi(a: np.ndarray, n) -> np.ndarray:
+    return ((a.astype(np.uint64) * np.asarray(n, dtype=np.uint64)) >> np.uint64(32)).astype(np.int64)
+
+
+def _ints(rows: np.ndarray) -> List[int]:
+    b = np.ascontiguousarray(rows, dtype="<u4").tobytes()
+    return [int.from_bytes(b[32 * i:32 * i + 32], "little") for i in range(len(rows))]
+
+
+def _gen_fields(leafgen):
+    return (np.array([g.width for g in leafgen], dtype=np.int64),
+            np.array([g.pool_off for g in leafgen], dtype=np.int64),
+            np.array([g.pool_n for g in leafgen], dtype=np.int64))
+
+
+def moves_ref(leafgen, consts, base, seed: int, r: int, lanes: int):
+    """Per lane of round ``r``, its moves as a list of (leaf, kind, value):
+    leaf ``leaf`` takes ``value`` (a Python int, masked to the leaf's width),
+    in order; the second move of a lane sees the result of the first.  Lane
+    0 has none, lanes below ``lanes // 2`` one, the others two."""
+    width, pool_off, pool_n = _gen_fields(leafgen)
+    n_leaves = len(width)
+    if n_leaves == 0 or not 1 <= lanes <= MAX_LANES or not 0 <= r < MAX_ROUNDS:
+        raise ValueError("moves_ref: no leaves, lanes outside 1..2^20 or a round outside 0..2^16-1")
+    cvals = _ints(np.asarray(consts, dtype=np.uint32).reshape(-1, 8))
+    bvals = _ints(np.asarray(base, dtype=np.uint32).reshape(n_leaves, 8))
+    j = np.arange(lanes, dtype=np.int64)
+    n_moves = np.where(j == 0, 0, np.where(j < lanes // 2, 1, 2))
+    draws = []
+    for m in range(2):
+        h0, h1 = _hash(seed, r, j, 2 * m), _hash(seed, r, j, 2 * m + 1)
+        lo0, hi0 = h0 & np.uint64(0xFFFFFFFF), h0 >> np.uint64(32)
+        a, c = h1 & np.uint64(0xFFFFFFFF), h1 >> np.uint64(32)
+        leaf = _mulhi(lo0, n_leaves)
+        w = width[leaf]
+        draws.append((leaf.tolist(), _mulhi(hi0, KINDS).tolist(), a.tolist(), c.tolist(),
+                      _mulhi(a, w).tolist(), _mulhi(a, (w + 7) // 8).tolist(),
+                      _mulhi(a, (w + 31) // 32).tolist(), _mulhi(a, np.maximum(pool_n[leaf], 1)).tolist(),
+                      _mulhi(c, 3).tolist(), _mulhi(a, n_leaves).tolist()))
+    out = []
+    for lane in range(lanes):
+        cur = {}
+        row = []
+        for m in range(int(n_moves[lane])):
+            leaf, kind, a, c, b, byte, limb, e, delta, other = (d[lane] for d in draws[m])
+            w = int(width[leaf])
+            v = cur.get(leaf, bvals[leaf])
+            if kind == FLIP:
+                v ^= 1 << b
+            elif kind == STEP:
+                v = v - (1 << b) if c & 1 else v + (1 << b)
+            elif kind == BYTE:
+                v = (v & ~(0xFF << (8 * byte))) | ((c & 0xFF) << (8 * byte))
+            elif kind == LIMB:
+                v = (v & ~(0xFFFFFFFF << (32 * limb))) | (c << (32 * limb))
+            elif kind == POOL:
+                if pool_n[leaf] > 0:
+                    v = (cvals[int(pool_off[leaf]) + e] + delta - 1) % (1 << 256)
+                else:
+                    v = (0, 1, 1 << (w - 1), (1 << w) - 1)[c & 3]
+            else:
+                v = cur.get(other, bvals[other])
+            v &= (1 << w) - 1
+            cur[leaf] = v
+            row.append((leaf, kind, v))
+        out.append(row)
+    return out
+
+
+def mutate_ref(leafgen, consts, base, seed: int, r: int, lanes: int) -> np.ndarray:
+    """``[n_leaves][8][lanes]`` u32: the neighbours of ``base``
+    (``[n_leaves][8]`` u32) that round ``r`` evaluates — the specification of
+    ``csrc/mg_repair.h``.  ``leafgen``: the program's leaf table (width,
+    pool_off, pool_n), ``consts``: its constant table ``[n_consts][8]``."""
+    base = np.ascontiguousarray(base, dtype=np.uint32).reshape(-1, 8)
+    out = np.repeat(base[:, :, None], lanes, axis=2)
+    for lane, row in enumerate(moves_ref(leafgen, consts, base, seed, r, lanes)):
+        for leaf, _, v in row:
+            out[leaf, :, lane] = np.frombuffer(v.to_bytes(32, "little"), dtype="<u4")
+    return out
+
+
+@dataclass
+class RepairResult:
+    leaves: np.ndarray         # (n_leaves, 8) u32: the last base
+    nfail: int                 # its failing constraints (0: a model of the program)
+    rounds: int                # rounds run
+    trace: np.ndarray          # (max_rounds,) the fewest failing constraints of each round run
+    kernel_ms: float = 0.0     # device time of the rounds (not compared)
+
+
+def repair_ref(bits_fn: Callable[[np.ndarray], np.ndarray], leafgen, consts, start, seed: int,
+               lanes: int = 4096, max_rounds: int = 64, sync_every: int = 8) -> RepairResult:
+    """The whole loop as ``mg_repair`` runs it.  ``bits_fn`` maps an SoA leaf
+    array ``(n_leaves, 8, n)`` to ``(n, n_constraints)`` bool verdicts."""
+    base = np.ascontiguousarray(start, dtype=np.uint32).reshape(-1, 8).copy()
+    sync_every = sync_every or 8
+    trace = np.zeros(max_rounds, dtype=np.uint32)
+    base_nfail, r = None, 0
+    while r < max_rounds and base_nfail != 0:
+        stop = max_rounds if max_rounds - r < sync_every else r + sync_every
+        while r < stop:
+            nb = mutate_ref(leafgen, consts, base, seed, r, lanes)
+            nfail = (~np.asarray(bits_fn(nb), dtype=bool)).sum(axis=1)
+            lane = int(np.argmin(nfail))                  # the lowest lane of the minimum
+            if base_nfail is None or int(nfail[lane]) < base_nfail:
+                base, base_nfail = np.ascontiguousarray(nb[:, :, lane]), int(nfail[lane])
+            trace[r] = int(nfail[lane])
+            r += 1
+    return RepairResult(base, base_nfail, r, trace)
+
+
+# ---------------------------------------------------------------------------
+# repair a missed group
+# ---------------------------------------------------------------------------
+
+REPAIRED, STUCK = "repaired", "stuck"
+
+
+def repair_group(nodes: Sequence, n_cand: int = 1 << 16, form: str = "search", lanes: int = 4096,
+                 max_rounds: int = 64, device: int = 0, seed: Optional[int] = None,
+                 sync_every: int = 8) -> dict:
+    """Census, then local search, of ONE independent group (root k =
+    ``nodes[k]``): the statuses of ``census.explain_group`` for a group that
+    launches nothing, else ``repaired`` with ``assignment`` (a model of the
+    group) or ``stuck``; a launched group also reports ``census``, ``start``
+    (index and failing constraints of the census's best candidate) and
+    ``repair`` (the :class:`RepairResult`; None when the census itself found
+    a satisfying candidate).  The search runs on the census view from the
+    leaves of ``best_index``; the verdict is a fresh evaluation of the full
+    masked program on the returned leaves — root bit and every mask bit set
+    — not the loop's counter.  In solve form only the free leaves move: the
+    construction's definitions recompute the rest."""
+    from . import census as CS
+    from . import model as M
+    from .assign import unpack
+    from .engine import get_engine
+    from .ir import Unsupported
+    from .refute import refuted
+    if form not in ("search", "eval"):
+        raise ValueError("form must be 'search' or 'eval'")
+    nodes = list(nodes)
+    out: dict = {"n_roots": len(nodes), "status": STUCK}
+    if len(nodes) > 1 and refuted(nodes):
+        out["status"] = CS.REFUTED
+        return out
+    if len(nodes) > CS.MAX_ROOTS:
+        out.update(status=CS.UNSUPPORTED,
+                   why="%d constraints (at most %d)" % (len(nodes), CS.MAX_ROOTS))
+        return out
+    try:
+        ground = M._ground_value(CS._compile(nodes, (), form))
+        if ground is not None:
+            out["status"] = CS.GROUND_TRUE if ground else CS.GROUND_FALSE
+            return out
+        masked = CS._compile(nodes, CS.mask_probes(nodes), form)
+    except Unsupported as e:
+        out.update(status=CS.UNSUPPORTED, why=str(e))
+        return out
+    n_mask = CS.n_mask_probes(len(nodes))
+    if masked.n_user_probes != n_mask:
+        out["status"] = CS.DEAD if masked.n_user_probes == 0 else CS.UNSUPPORTED
+        out["why"] = "%d mask probes compiled to %d" % (n_mask, masked.n_user_probes)
+        return out
+    if not len(masked.leaves):
+        out.update(status=CS.UNSUPPORTED, why="no leaf to move")
+        return out
+    eng = get_engine(device, nreg=masked.nreg)
+    gens = CS._leafgen(masked, form)
+    view = eng.load(CS.census_view(masked, n_mask), gens, prog_seed=0)
+    full = eng.load(masked, gens, prog_seed=0)
+    c = eng.census(view, M.SEARCH_SEED, 0, n_cand, len(nodes), 0)
+    out["census"] = c
+    if not c.n_cand:
+        return out
+    leaves, _ = eng.witness(full, M.SEARCH_SEED, c.best_index)
+    out["start"] = {"index": c.best_index, "nfail": c.best_nfail}
+    out["repair"] = None
+    if c.best_nfail:
+        res = eng.repair(view, leaves, len(nodes), M.SEARCH_SEED if seed is None else seed, lanes,
+                         max_rounds, sync_every)
+        out["repair"] = res
+        if res.nfail:
+            return out
+        leaves = res.leaves
+    root, probes = eng.eval(full, np.ascontiguousarray(leaves[:, :, None]), want_probes=True)
+    holds = CS.mask_bits(probes[:n_mask], len(nodes))[0]
+    if not (bool(root[0]) and holds.all()):
+        out["why"] = "the fresh evaluation of the repaired leaves fails %d constraints" % (
+            int((~holds).sum()))
+        return out
+    out["status"] = REPAIRED
+    out["assignment"] = unpack(masked, leaves, probes[:, :, 0] if masked.solved else None)
+    return out
+
+
+def repair(constraints: Sequence, **kw) -> dict:
+    """:func:`repair_group` per independent group
+    (``model.dependence_buckets``), each entry with the positions of its
+    constraints in the caller's list (``constraints``); ``model`` is the
+    joined assignment when every group is ground-true or repaired, else None.
+    Touches no memo, gate or statistic of the model module."""
+    from . import census as CS
+    from .assign import Assignment
+    from .model import _merge, dependence_buckets
+    nodes = list(constraints)
+    where = {}
+    for i, c in enumerate(nodes):
+        where.setdefault(c.id, []).append(i)
+    groups, parts, whole = [], [], True
+    for b in dependence_buckets(nodes):
+        g = repair_group(b, **kw)
+        g["constraints"] = [where[c.id].pop(0) for c in b]
+        groups.append(g)
+        if g["status"] == REPAIRED:
+            parts.append(g["assignment"])
+        elif g["status"] == CS.GROUND_TRUE:
+            parts.append(Assignment())
+        else:
+            whole = False
+    return {"groups": groups, "model": _merge(parts) if whole else None}

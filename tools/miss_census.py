@@ -14,6 +14,11 @@ usage: tools/miss_census.py --workload {c1,c3,c3o,c4,c5} --query N
                             [--candidates K] [--json] [--split-and]
        tools/miss_census.py --known-misses [--candidates K] [--json] [--split-and]
            every entry of tests/golden/recall_known_miss.json and c3o query 50
+       ... --repair [--lanes L] [--rounds R]
+           after the census, the local search (mythril_amd/repair.py, DESIGN.md
+           §3.9) from each launched group's best candidate: the trace, the
+           outcome, and the device time per round next to the census's time
+           for as many candidates in chunks of L
        tools/miss_census.py [workload] [n]
            the older census: which of a stream's first n queries the batched
            search misses, grouped by the shape of their newest constraint
@@ -133,6 +138,58 @@ def report(wl, qi, n_cand, split_and=False):
     return out
 
 
+def repair_rows(wl, qi, n_cand, lanes, rounds):
+    """Per independent group of the query: what ``repair.repair_group`` did
+    (status, start, trace, rounds) and, for a group whose search ran, the
+    device time per round beside ``Engine.census`` over rounds x lanes
+    candidates of the same view in chunks of ``lanes``."""
+    import mythril_amd.model as M
+    from mythril_amd import census as CS
+    from mythril_amd import repair as RP
+    from mythril_amd.engine import get_engine
+    rows = []
+    for group in M.dependence_buckets(stream_query(wl, qi)):
+        g = RP.repair_group(group, n_cand=n_cand, form="search", lanes=lanes, max_rounds=rounds)
+        row = {"constraints": len(group), "status": g["status"]}
+        if "why" in g:
+            row["why"] = g["why"]
+        if "start" in g:
+            row["start"] = g["start"]
+        res = g.get("repair")
+        if res is not None:
+            row.update(nfail=res.nfail, rounds=res.rounds,
+                       trace=[int(v) for v in res.trace[:res.rounds]],
+                       repair_kernel_ms=round(res.kernel_ms, 3),
+                       ms_per_round=round(res.kernel_ms / max(1, res.rounds), 4))
+            masked = CS._compile(group, CS.mask_probes(group), "search")
+            eng = get_engine(0, nreg=masked.nreg)
+            n_mask = CS.n_mask_probes(len(group))
+            lp = eng.load(CS.census_view(masked, n_mask), CS._leafgen(masked, "search"), prog_seed=0)
+            chunk = (lanes + 255) // 256 * 256
+            c = eng.census(lp, M.SEARCH_SEED, 0, res.rounds * chunk, len(group), 0, chunk)
+            row["census_same_candidates_ms"] = round(c.kernel_ms, 3)
+            row["census_ms_per_chunk"] = round(c.kernel_ms / max(1, res.rounds), 4)
+            row["records"] = masked.n_ins
+        rows.append(row)
+    return rows
+
+
+def show_repair(rows, lanes):
+    for gi, g in enumerate(rows):
+        print(" repair group %d: %d constraints -> %s%s" % (
+            gi, g["constraints"], g["status"], (" (%s)" % g["why"]) if "why" in g else ""))
+        if "start" in g:
+            print("  start: candidate %d, %d failing" % (g["start"]["index"], g["start"]["nfail"]))
+        if "trace" in g:
+            print("  %d rounds of %d lanes, %d failing at the end; trace: %s" % (
+                g["rounds"], lanes, g["nfail"], " ".join(str(v) for v in g["trace"])))
+            print("  device: %.3f ms, %.4f ms per round (%d records); census of the same %d "
+                  "candidates in chunks of %d: %.3f ms, %.4f ms per chunk" % (
+                      g["repair_kernel_ms"], g["ms_per_round"], g["records"],
+                      g["rounds"] * lanes, lanes, g["census_same_candidates_ms"],
+                      g["census_ms_per_chunk"]))
+
+
 def show(r):
     print("== %s query %d%s: %d constraints, %d candidates per group (%.0f ms in all)" % (
         r["workload"], r["query"], " (top-level ands split, i.j = conjunct j of constraint i)"
@@ -175,6 +232,10 @@ def main():
     ap.add_argument("--json", action="store_true")
     ap.add_argument("--split-and", action="store_true",
                     help="census the query with every top-level `and` split into its conjuncts")
+    ap.add_argument("--repair", action="store_true",
+                    help="then run the local search from each group's best candidate")
+    ap.add_argument("--lanes", type=int, default=4096)
+    ap.add_argument("--rounds", type=int, default=64)
     a = ap.parse_args()
     if a.known_misses:
         known = json.load(open(os.path.join(GOLDEN, "recall_known_miss.json")))
@@ -186,11 +247,16 @@ def main():
     else:
         ap.error("give --workload and --query, or --known-misses")
     reports = [report(wl, qi, a.candidates, a.split_and) for wl, qi in jobs]
+    if a.repair:
+        for r in reports:
+            r["repair"] = repair_rows(r["workload"], r["query"], a.candidates, a.lanes, a.rounds)
     if a.json:
         print(json.dumps(reports, indent=1))
     else:
         for r in reports:
             show(r)
+            if a.repair:
+                show_repair(r["repair"], a.lanes)
 
 
 if __name__ == "__main__":
