@@ -223,6 +223,57 @@ int mg_repair_mutate_host(const mg_leafgen* leaves, uint32_t n_leaves, const uin
                           uint64_t seed, uint32_t r, uint32_t lanes, uint32_t lane0,
                           uint32_t n_lanes, uint32_t* out, uint32_t* moves);
 
+/* Scored walk: `walkers` local searches in one launch
+ * sequence, neighbours ranked by (failing roots, cost) instead of the failing
+ * count alone.  Like mg_repair it has no reference counterpart and serves the
+ * misses of Constraints.is_possible (reference
+ * laser/ethereum/state/constraints.py:26-45).
+ * The program carries its verdict mask as probes mask_probe0 .. (as for
+ * mg_census) and, right after the mask, n_resid residual probes
+ * (mythril_amd/repair.py residuals).  table[k] = kind << 16 | index of root
+ * k's residual among them; a failing root costs its distance: kind 0 (flat)
+ * 1, kind 1 (Hamming, residual a xor b of a root a = b) max(1, popcount),
+ * kind 2 (magnitude, residual a - b of an order root) 1 + bit length.  cost =
+ * the sum over the failing roots (csrc/mg_walk.h; repair.py score_ref is its
+ * specification).  Whether a root holds is read from the mask alone.
+ * Walker w starts at starts[w] and draws the moves of mg_repair under the
+ * seed seed ^ w * MG_WALK_CW.  Per round, on the context stream and with no
+ * host round trip, every walker's `lanes` neighbours are written, evaluated
+ * in ONE eval-mode launch over walkers * lanes lanes and scored; a walker
+ * adopts its best neighbour (ties: the lowest lane) on a strict improvement
+ * of (failing roots, cost).  After every sync_every rounds (0: 8) the host
+ * reads the walkers' states and stops once any walker has no failing root, or
+ * after max_rounds.  Outputs:
+ *   out_leaves [walkers][n_leaves][8]  each walker's last base
+ *   out_nfail, out_cost [walkers]      its failing roots and cost
+ *   out_rounds                         rounds run (the same for every walker)
+ *   trace [walkers][max_rounds][2] or NULL: (failing roots, cost) of each
+ *                                      walker's best neighbour per round run
+ *                                      (0 beyond out_rounds)
+ *   out_winner                         the walker of minimum (nfail, cost, w)
+ * A function of the arguments alone: identical across runs.  MG_E_ARG without
+ * a launch for: a null pointer other than trace, a program with no leaves,
+ * walkers outside 1..64, n_roots outside 1..1024, mask or residual probes
+ * outside the program's probes, lanes outside 1..2^20, max_rounds outside
+ * 1..2^16, a table entry with an unknown kind or a residual index at or
+ * above n_resid, and walkers * lanes * probes * 32 B above 256 MiB (load the
+ * census view).  mg_last_kernel_ms covers the rounds. */
+int mg_walk(mg_ctx* ctx, const mg_prog* prog, const uint32_t* starts /*[walkers][n_leaves][8]*/,
+            uint32_t walkers, uint32_t n_roots, uint32_t mask_probe0,
+            const uint32_t* table /*[n_roots]*/, uint32_t n_resid, uint64_t seed, uint32_t lanes,
+            uint32_t max_rounds, uint32_t sync_every,
+            uint32_t* out_leaves /*[walkers][n_leaves][8]*/, uint32_t* out_nfail /*[walkers]*/,
+            uint32_t* out_cost /*[walkers]*/, uint32_t* out_rounds,
+            uint32_t* trace /*[walkers][max_rounds][2] or NULL*/, uint32_t* out_winner);
+/* Host-only (no GPU): mg_walk's scoring function on n lanes.  masks:
+ * [ceil(n_roots / 256) * 8][n] u32, the rows of the verdict mask; resid:
+ * [n_resid * 8][n] u32 (may be NULL when n_resid = 0); nfail, cost: [n].
+ * MG_E_ARG for a null pointer, n_roots outside 1..1024 and a table entry
+ * mg_walk refuses. */
+int mg_walk_score_host(const uint32_t* masks, const uint32_t* resid, const uint32_t* table,
+                       uint32_t n_roots, uint32_t n_resid, uint64_t n, uint32_t* nfail,
+                       uint32_t* cost);
+
 /* Corpus batches: many programs, one launch.  Device-pointer API for
  * resident benchmarking; stream is a hipStream_t (NULL = the context's own
  * stream, which the synchronous calls also use).

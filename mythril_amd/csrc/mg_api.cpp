@@ -25,6 +25,7 @@
 #include "mg_host.h"
 #include "mg_census.h"
 #include "mg_repair.h"
+#include "mg_walk.h"
 
 // the interpreter of each register layout (mg_interp_asm.hip, one
 // translation unit per layout; mg_find_layout lists them)
@@ -64,6 +65,20 @@ hipError_t mg_launch_repair_pick(const uint32_t* d_rows, uint32_t lanes, uint32_
                                  const uint32_t* d_consts, uint32_t n_leaves, uint64_t seed,
                                  uint32_t r, mg_repair_state* d_state, uint32_t* d_trace,
                                  hipStream_t stream);
+// one round of the scored walk (mg_walk.hip), all walkers per launch: the
+// neighbours of every base into the eval-mode input ([..][walkers * lanes]);
+// then, after the interpreter wrote their masks and residual probes, each
+// walker's best neighbour into its base and its key into trace[w][r]
+hipError_t mg_launch_walk_round(const uint32_t* d_bases, const mg_leafgen* d_gen,
+                                const uint32_t* d_consts, uint32_t n_leaves, uint64_t seed,
+                                uint32_t r, uint32_t lanes, uint32_t walkers, uint32_t* d_leaves,
+                                hipStream_t stream);
+hipError_t mg_launch_walk_pick(const uint32_t* d_masks, const uint32_t* d_resid,
+                               const uint32_t* d_table, uint32_t lanes, uint32_t walkers,
+                               uint32_t n_roots, uint32_t* d_bases, const mg_leafgen* d_gen,
+                               const uint32_t* d_consts, uint32_t n_leaves, uint64_t seed,
+                               uint32_t r, uint32_t max_rounds, mg_walk_state* d_state,
+                               uint32_t* d_trace, hipStream_t stream);
 
 
 struct mg_ctx {
@@ -959,6 +974,144 @@ int mg_repair_mutate_host(const mg_leafgen* leaves, uint32_t n_leaves, const uin
             moves[4 * (size_t)a + 3] = mv.leaf[1];
         }
     }
+    return MG_OK;
+}
+
+// a residual table entry names a known kind and, unless flat, a probe it has
+static bool walk_table_ok(const uint32_t* table, uint32_t n_roots, uint32_t n_resid) {
+    for (uint32_t k = 0; k < n_roots; ++k) {
+        const uint32_t kind = table[k] >> 16, p = table[k] & 0xFFFFu;
+        if (kind >= MG_WALK_KINDS || (kind != MG_WALK_FLAT && p >= n_resid)) return false;
+    }
+    return true;
+}
+
+// The scored walk.  Rounds are queued back to back; after
+// every sync_every rounds the host reads the walkers' states (16 bytes each)
+// and stops once one of them has no failing root.
+int mg_walk(mg_ctx* ctx, const mg_prog* prog, const uint32_t* starts, uint32_t walkers,
+            uint32_t n_roots, uint32_t mask_probe0, const uint32_t* table, uint32_t n_resid,
+            uint64_t seed, uint32_t lanes, uint32_t max_rounds, uint32_t sync_every,
+            uint32_t* out_leaves, uint32_t* out_nfail, uint32_t* out_cost, uint32_t* out_rounds,
+            uint32_t* trace, uint32_t* out_winner) {
+    if (!ctx || !prog || !starts || !table || !out_leaves || !out_nfail || !out_cost ||
+        !out_rounds || !out_winner)
+        return fail(ctx, MG_E_ARG, "null argument");
+    if (prog->n_leaves == 0) return fail(ctx, MG_E_ARG, "walk: the program has no leaves");
+    if (walkers < 1 || walkers > MG_WALK_MAX_WALKERS)
+        return fail(ctx, MG_E_ARG, "walk: %u walkers outside 1..%u", walkers, MG_WALK_MAX_WALKERS);
+    if (n_roots < 1 || n_roots > MG_CENSUS_MAX_ROOTS)
+        return fail(ctx, MG_E_ARG, "walk: n_roots %u outside 1..%u", n_roots, MG_CENSUS_MAX_ROOTS);
+    const uint32_t n_mask = (n_roots + 255) / 256;
+    if (mask_probe0 >= prog->n_probes || n_mask > prog->n_probes - mask_probe0 ||
+        n_resid > prog->n_probes - mask_probe0 - n_mask)
+        return fail(ctx, MG_E_ARG, "walk: mask probes %u..%u and %u residual probes outside the "
+                    "program's %u probes", mask_probe0, mask_probe0 + n_mask - 1, n_resid,
+                    prog->n_probes);
+    if (lanes < 1 || lanes > MG_REPAIR_MAX_LANES)
+        return fail(ctx, MG_E_ARG, "walk: %u lanes outside 1..%u", lanes, MG_REPAIR_MAX_LANES);
+    if (max_rounds < 1 || max_rounds > MG_REPAIR_MAX_ROUNDS)
+        return fail(ctx, MG_E_ARG, "walk: %u rounds outside 1..%u", max_rounds,
+                    MG_REPAIR_MAX_ROUNDS);
+    if (!walk_table_ok(table, n_roots, n_resid))
+        return fail(ctx, MG_E_ARG, "walk: a table entry names an unknown kind or a residual "
+                    "probe at or above %u", n_resid);
+    const uint64_t total = (uint64_t)walkers * lanes;
+    if (total > MG_CENSUS_MAX_PROBE_BYTES / 32 / prog->n_probes)
+        return fail(ctx, MG_E_ARG, "walk: %u probes x %u walkers x %u lanes exceed a %zu MiB "
+                    "probe buffer; load the census view of the program (census.census_view: "
+                    "only the mask and residual probes are written) or pass fewer lanes",
+                    prog->n_probes, walkers, lanes, MG_CENSUS_MAX_PROBE_BYTES >> 20);
+    if (sync_every == 0) sync_every = 8;
+    HIPCHECK(ctx, hipSetDevice(ctx->device));
+    auto align = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const uint32_t n_leaves = prog->n_leaves;
+    const uint64_t words = (total + 63) / 64;
+    const size_t state_b = (size_t)walkers * sizeof(mg_walk_state),
+                 base_b = (size_t)walkers * n_leaves * 32,
+                 gen_b = (size_t)n_leaves * sizeof(mg_leafgen), table_b = (size_t)n_roots * 4,
+                 trace_b = (size_t)walkers * max_rounds * 8, root_b = words * 8,
+                 leaf_b = (size_t)n_leaves * 8 * total * 4,
+                 probe_b = (size_t)prog->n_probes * 8 * total * 4;
+    const size_t off_base = align(state_b), off_gen = off_base + align(base_b),
+                 off_table = off_gen + align(gen_b), off_trace = off_table + align(table_b),
+                 off_root = off_trace + align(trace_b), off_leaf = off_root + align(root_b),
+                 off_probe = off_leaf + align(leaf_b), bytes = off_probe + align(probe_b);
+    void* ws;
+    int rc = workspace(ctx, bytes + 256, &ws);
+    if (rc) return rc;
+    uint8_t* w = (uint8_t*)ws;
+    mg_walk_state* d_state = (mg_walk_state*)w;
+    uint32_t* d_bases = (uint32_t*)(w + off_base);
+    mg_leafgen* d_gen = (mg_leafgen*)(w + off_gen);
+    uint32_t* d_table = (uint32_t*)(w + off_table);
+    uint32_t* d_trace = (uint32_t*)(w + off_trace);
+    uint32_t* d_leaves = (uint32_t*)(w + off_leaf);
+    uint32_t* d_probes = (uint32_t*)(w + off_probe);
+    HIPCHECK(ctx, hipMemsetAsync(d_state, 0xFF, state_b, ctx->stream));
+    HIPCHECK(ctx, hipMemsetAsync(d_trace, 0, trace_b, ctx->stream));
+    HIPCHECK(ctx, hipMemcpyAsync(d_bases, starts, base_b, hipMemcpyHostToDevice, ctx->stream));
+    HIPCHECK(ctx, hipMemcpyAsync(d_gen, prog->leafgen.data(), gen_b, hipMemcpyHostToDevice,
+                                 ctx->stream));
+    HIPCHECK(ctx, hipMemcpyAsync(d_table, table, table_b, hipMemcpyHostToDevice, ctx->stream));
+    mg_run run = empty_run();
+    run.leaves = d_leaves;
+    run.root_bits = (uint64_t*)(w + off_root);
+    run.probes = d_probes;
+    run.stride = total;
+    run.n_assign = total;
+    run.words_per_prog = words;
+    const uint32_t* d_masks = d_probes + (size_t)mask_probe0 * 8 * total;
+    const uint32_t* d_resid = d_masks + (size_t)n_mask * 8 * total;
+    const uint32_t* d_consts = prog->h_desc.consts;       // the first n_consts entries: as loaded
+    std::vector<mg_walk_state> h_state(walkers);
+    bool done = false;
+    timing_begin(ctx);
+    uint32_t r = 0;
+    while (r < max_rounds && !done) {
+        const uint32_t stop = max_rounds - r < sync_every ? max_rounds : r + sync_every;
+        for (; r < stop; ++r) {
+            HIPCHECK(ctx, mg_launch_walk_round(d_bases, d_gen, d_consts, n_leaves, seed, r, lanes,
+                                               walkers, d_leaves, ctx->stream));
+            HIPCHECK(ctx, launch(ctx, 0, prog->d_desc, 1, run, prog->n_lds, ctx->stream));
+            HIPCHECK(ctx, mg_launch_walk_pick(d_masks, d_resid, d_table, lanes, walkers, n_roots,
+                                              d_bases, d_gen, d_consts, n_leaves, seed, r,
+                                              max_rounds, d_state, d_trace, ctx->stream));
+        }
+        timing_end(ctx);
+        HIPCHECK(ctx, hipMemcpyAsync(h_state.data(), d_state, state_b, hipMemcpyDeviceToHost,
+                                     ctx->stream));
+        HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
+        for (uint32_t k = 0; k < walkers; ++k) done = done || h_state[k].nfail == 0;
+    }
+    timing_read(ctx);
+    HIPCHECK(ctx, hipMemcpyAsync(out_leaves, d_bases, base_b, hipMemcpyDeviceToHost, ctx->stream));
+    if (trace)
+        HIPCHECK(ctx, hipMemcpyAsync(trace, d_trace, trace_b, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
+    uint32_t win = 0;
+    for (uint32_t k = 0; k < walkers; ++k) {
+        out_nfail[k] = h_state[k].nfail;
+        out_cost[k] = h_state[k].cost;
+        if (h_state[k].nfail < h_state[win].nfail ||
+            (h_state[k].nfail == h_state[win].nfail && h_state[k].cost < h_state[win].cost))
+            win = k;
+    }
+    *out_rounds = r;
+    *out_winner = win;
+    return MG_OK;
+}
+
+// Host only: the scoring function (mg_walk.h) on n lanes of host rows, as
+// the score kernel runs it.
+int mg_walk_score_host(const uint32_t* masks, const uint32_t* resid, const uint32_t* table,
+                       uint32_t n_roots, uint32_t n_resid, uint64_t n, uint32_t* nfail,
+                       uint32_t* cost) {
+    if (!masks || !table || !nfail || !cost || (n_resid && !resid)) return MG_E_ARG;
+    if (n_roots < 1 || n_roots > MG_CENSUS_MAX_ROOTS || n_resid > 0xFFFFu) return MG_E_ARG;
+    if (!walk_table_ok(table, n_roots, n_resid)) return MG_E_ARG;
+    for (uint64_t a = 0; a < n; ++a)
+        mg_walk_score_lane(masks, resid, n, a, table, n_roots, true, nfail + a, cost + a);
     return MG_OK;
 }
 

@@ -33,7 +33,8 @@ EXPORTS = ("mg_init", "mg_init_layout", "mg_layouts", "mg_free", "mg_last_error"
            "mg_search", "mg_batch_create", "mg_batch_free", "mg_batch_eval_gen", "mg_batch_search",
            "mg_batch_search_probes", "mg_keccak256", "mg_version", "mg_config", "mg_translate",
            "mg_asm_digest", "mg_asm_digest_layout", "mg_last_kernel_ms", "mg_jit_attach",
-           "mg_jit_detach", "mg_runtime_info", "mg_census", "mg_repair", "mg_repair_mutate_host")
+           "mg_jit_detach", "mg_runtime_info", "mg_census", "mg_repair", "mg_repair_mutate_host",
+           "mg_walk", "mg_walk_score_host")
 
 
 def layouts() -> Dict[int, Tuple[int, int]]:
@@ -120,6 +121,9 @@ def load_library(path: str = _LIB_PATH, check_digest: bool = True):
         lib.mg_repair.argtypes = [p, p, p, u32, u32, u64, u32, u32, u32, p, C.POINTER(u32),
                                   C.POINTER(u32), p]
         lib.mg_repair_mutate_host.argtypes = [p, u32, p, u32, p, u64, u32, u32, u32, u32, p, p]
+        lib.mg_walk.argtypes = [p, p, p, u32, u32, u32, p, u32, u64, u32, u32, u32, p, p, p,
+                                C.POINTER(u32), p, C.POINTER(u32)]
+        lib.mg_walk_score_host.argtypes = [p, p, p, u32, u32, u64, p, p]
         lib.mg_batch_create.argtypes = [p, C.POINTER(p), u32, C.POINTER(p)]
         lib.mg_batch_free.argtypes = [p]
         lib.mg_batch_free.restype = None
@@ -343,6 +347,38 @@ class Engine:
         return RepairResult(out[:n_leaves], int(nfail.value), int(rounds.value), trace,
                             self.last_kernel_ms())
 
+    def walk(self, lp: LoadedProgram, starts: np.ndarray, n_roots: int, table: np.ndarray,
+             n_resid: int, seed: int, lanes: int = 4096, max_rounds: int = 64,
+             sync_every: int = 8, mask_probe0: int = 0):
+        """Scored walk (mg_walk) of ``len(starts)`` walkers
+        from ``starts`` ((walkers, n_leaves, 8) u32) on a program that carries
+        its verdict mask as probes ``mask_probe0``.. and ``n_resid`` residual
+        probes right after it (``repair.residuals``, whose ``table`` says
+        which root reads which): a :class:`mythril_amd.repair.WalkResult`."""
+        from .repair import WalkResult
+        n_leaves = len(lp.program.leaves)
+        starts = np.ascontiguousarray(starts, dtype=np.uint32)
+        if starts.ndim != 3 or starts.shape[1:] != (n_leaves, 8):
+            raise ValueError("starts must be (walkers, n_leaves, 8)")
+        walkers = starts.shape[0]
+        table = np.ascontiguousarray(table, dtype=np.uint32)
+        if table.shape != (max(0, int(n_roots)),) and 1 <= int(n_roots) <= 1024:
+            raise ValueError("table must have n_roots entries")
+        w1, r1 = max(1, min(walkers, 64)), max(1, min(int(max_rounds), 1 << 16))
+        out = np.zeros((w1, max(1, n_leaves), 8), dtype=np.uint32)
+        nfail, cost = np.zeros(w1, dtype=np.uint32), np.zeros(w1, dtype=np.uint32)
+        trace = np.zeros((w1, r1, 2), dtype=np.uint32)
+        rounds, winner = C.c_uint32(0), C.c_uint32(0)
+        rc = self.lib.mg_walk(self._ctx, lp.handle, _ptr(starts) if starts.size else _ptr(out),
+                              walkers, max(0, int(n_roots)), mask_probe0,
+                              _ptr(table) if table.size else _ptr(nfail), max(0, int(n_resid)),
+                              seed & (2**64 - 1), lanes, max_rounds, sync_every, _ptr(out),
+                              _ptr(nfail), _ptr(cost), C.byref(rounds), _ptr(trace),
+                              C.byref(winner))
+        self._check(rc, "mg_walk")
+        return WalkResult(out[:, :n_leaves], nfail.astype(np.int64), cost.astype(np.int64),
+                          int(rounds.value), trace, int(winner.value), self.last_kernel_ms())
+
     def witness(self, lp: LoadedProgram, seed: int, index: int):
         """Leaves and probe values of candidate ``index`` (one lane): what a
         solve-mode program's model needs besides the generated leaves."""
@@ -504,6 +540,26 @@ def repair_mutate_host(leafgen: Sequence[LeafGen], consts: np.ndarray, base: np.
     if rc != 0:
         raise EngineError("mg_repair_mutate_host failed (%d)" % rc)
     return out[:len(gens), :, :n_lanes], moves[:n_lanes]
+
+
+def walk_score_host(masks: np.ndarray, resid: Optional[np.ndarray], table: np.ndarray,
+                    n_roots: int):
+    """Host-only (no GPU): ``(nfail, cost)`` (n,) u32 of the lanes of mask
+    probes ``masks`` (n_mask, 8, n) u32 and residual probes ``resid``
+    (n_resid, 8, n) u32 from the library's own scoring function
+    (mg_walk_score_host; ``repair.score_ref`` is its specification)."""
+    lib = load_library()
+    masks = np.ascontiguousarray(masks, dtype=np.uint32)
+    n = masks.shape[2]
+    n_resid = 0 if resid is None else resid.shape[0]
+    resid = None if not n_resid else np.ascontiguousarray(resid, dtype=np.uint32)
+    table = np.ascontiguousarray(table, dtype=np.uint32)
+    nfail, cost = np.zeros(max(1, n), dtype=np.uint32), np.zeros(max(1, n), dtype=np.uint32)
+    rc = lib.mg_walk_score_host(_ptr(masks), _ptr(resid), _ptr(table), n_roots, n_resid, n,
+                                _ptr(nfail), _ptr(cost))
+    if rc != 0:
+        raise EngineError("mg_walk_score_host failed (%d)" % rc)
+    return nfail[:n], cost[:n]
 
 
 def unpack_bits(bits: np.ndarray, n: int) -> np.ndarray:

@@ -189,8 +189,11 @@ GPU_ENABLED = True
 SHAPE_GATE = True
 REFUTE = True              # host refutation before compiling (refute.py)
 # opt-in (MYTHRIL_GPU_REPAIR=1): a group the search missed is handed to the
-# local search (repair.py) while search budget remains
+# local search (repair.py) while search budget remains;
+# MYTHRIL_GPU_REPAIR=2: to the scored walk of REPAIR_WALKERS walkers (§3.10)
 REPAIR = False
+REPAIR_SCORED = False
+REPAIR_WALKERS = 16
 SHAPE_MIN, SHAPE_FLOOR, SHAPE_PROBE = 4, 1.0 / 16, 8
 
 
@@ -203,8 +206,10 @@ def configure_from_env(env=None) -> None:
     take, ``MYTHRIL_GPU_ADAPTIVE=0`` turns the per-shape gate off,
     ``MYTHRIL_GPU_REFUTE=0`` the host refutation (refute.py),
     ``MYTHRIL_GPU_REPAIR=1`` turns the local search of missed groups on
-    (repair.py; off by default)."""
+    (repair.py; off by default), ``MYTHRIL_GPU_REPAIR=2`` its scored walk of
+    several walkers instead."""
     global GPU_ENABLED, DEVICES, SEARCH_CANDIDATES, SEARCH_BUDGET_MS, SHAPE_GATE, REFUTE, REPAIR
+    global REPAIR_SCORED
     import os
     env = os.environ if env is None else env
     GPU_ENABLED = env.get("MYTHRIL_GPU", "1").strip().lower() not in ("0", "off", "false", "no")
@@ -219,7 +224,9 @@ def configure_from_env(env=None) -> None:
     SHAPE_GATE = env.get("MYTHRIL_GPU_ADAPTIVE", "1").strip().lower() not in ("0", "off", "false",
                                                                              "no")
     REFUTE = env.get("MYTHRIL_GPU_REFUTE", "1").strip().lower() not in ("0", "off", "false", "no")
-    REPAIR = env.get("MYTHRIL_GPU_REPAIR", "0").strip().lower() in ("1", "on", "true", "yes")
+    REPAIR_SCORED = env.get("MYTHRIL_GPU_REPAIR", "0").strip() == "2"
+    REPAIR = REPAIR_SCORED or env.get("MYTHRIL_GPU_REPAIR", "0").strip().lower() in (
+        "1", "on", "true", "yes")
 
 
 configure_from_env()
@@ -821,7 +828,7 @@ def gpu_search(nodes: Sequence[N.Node], budget_ms: float):
 
 def _repair_misses(buckets, hits, budget_ms: float, t_start: float):
     """``hits`` with every missed group the local search repairs
-    (``repair.repair_group``, MYTHRIL_GPU_REPAIR=1) replaced by (0, its
+    (``repair.repair_group``, MYTHRIL_GPU_REPAIR=1, or 2: scored) replaced by (0, its
     assignment), as long as search budget remains; stops at the first group
     it cannot repair (the query is a miss then).  The witness goes through
     ``_accept`` like any other."""
@@ -834,7 +841,8 @@ def _repair_misses(buckets, hits, budget_ms: float, t_start: float):
             break
         stats.repair_attempts += 1
         with _Phase("search"):
-            g = repair_group(b, device=(list(DEVICES) or [0])[0])
+            g = repair_group(b, device=(list(DEVICES) or [0])[0], scored=REPAIR_SCORED,
+                             walkers=REPAIR_WALKERS if REPAIR_SCORED else 1)
         if g["status"] != REPAIRED:
             break
         stats.repair_hits += 1
@@ -1175,7 +1183,8 @@ def explain_miss(constraints, **kw) -> dict:
 def repair_miss(constraints, **kw) -> dict:
     """Census, then local search from its best candidate, per independent
     group of ``constraints`` (``mythril_amd/repair.py`` ``repair``; keywords
-    ``n_cand``, ``form``, ``lanes``, ``max_rounds``, ``device``): ``groups``
+    ``n_cand``, ``form``, ``lanes``, ``max_rounds``, ``device``, and
+    ``scored``, ``walkers`` for the scored walk of DESIGN.md §3.10): ``groups``
     and, when every group was repaired, the joined ``model``.  Touches no
     memo, gate or counter; the model is not verified by z3 here."""
     from .repair import repair

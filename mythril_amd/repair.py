@@ -154,6 +154,173 @@ def repair_ref(bits_fn: Callable[[np.ndarray], np.ndarray], leafgen, consts, sta
 
 
 # ---------------------------------------------------------------------------
+# the scored walk: residual probes, the key, several walkers
+# ---------------------------------------------------------------------------
+
+# the constants of csrc/mg_walk.h
+CW = 0x8CB92BA72F3D8DD7
+FLAT, HAMMING, MAGNITUDE = range(3)
+MAX_WALKERS = 64
+RESIDUAL_BITS = 256
+
+_LESS = ("bvult", "bvule", "bvslt", "bvsle")
+_GREATER = ("bvugt", "bvuge", "bvsgt", "bvsge")
+
+
+def _ite10(n) -> bool:
+    return (n.op == "ite" and n.is_bv() and n.args[1].op == "bvnum" and n.args[2].op == "bvnum"
+            and n.args[1].params[0] == 1 and n.args[2].params[0] == 0)
+
+
+def peel(c):
+    """``(d, negated)``: ``c`` is ``d`` or ``not d`` after dropping every
+    ``not`` and LASER's Bool-as-word wrappers ``ite(d, 1, 0) = 0`` (``not
+    d``) and ``ite(d, 1, 0) = 1`` (``d``)."""
+    neg = False
+    while True:
+        if c.op == "not":
+            c, neg = c.args[0], not neg
+            continue
+        if c.op == "=":
+            a, b = c.args
+            if _ite10(b):
+                a, b = b, a
+            if _ite10(a) and b.op == "bvnum" and b.params[0] in (0, 1):
+                c, neg = a.args[0], neg != (b.params[0] == 0)
+                continue
+        return c, neg
+
+
+def _difference(c):
+    """``a - b`` of an order atom ``a < b`` / ``a <= b`` (``b - a`` of the
+    ``>`` forms) over at most 256 bits, else None."""
+    from .smt import node as N
+    if c.op not in _LESS + _GREATER or c.args[0].width > RESIDUAL_BITS:
+        return None
+    a, b = c.args if c.op in _LESS else c.args[::-1]
+    return N.bv_op("bvsub", a, b)
+
+
+def classify(c):
+    """``(kind, residual node or None)`` of one constraint."""
+    from .smt import node as N
+    c, neg = peel(c)
+    if neg:
+        return FLAT, None
+    # (a one-bit equality's distance is identically 1: FLAT, and no probe)
+    if c.op == "=" and c.args[0].is_bv() and 2 <= c.args[0].width <= RESIDUAL_BITS:
+        return HAMMING, N.bv_op("bvxor", *c.args)
+    atoms = [c] if c.op != "or" else [d for d, negated in map(peel, c.args) if not negated]
+    for d in atoms:
+        r = _difference(d)
+        if r is not None:
+            return MAGNITUDE, r
+    return FLAT, None
+
+
+def residuals(constraints: Sequence):
+    """``(probes, table)``: the residual probe nodes of ``constraints`` (one
+    per distinct term, to compile right after the mask probes) and ``table``
+    (n_roots,) u32, ``kind << 16 | probe index``: what a failing root costs
+    (``score_ref``).  The distance is a heuristic; whether a root holds is
+    always read from its mask bit."""
+    probes, index, table = [], {}, []
+    for c in constraints:
+        kind, r = classify(c)
+        if r is None:
+            table.append(FLAT << 16)
+            continue
+        if r.id not in index:
+            index[r.id] = len(probes)
+            probes.append(r)
+        table.append(kind << 16 | index[r.id])
+    return probes, np.array(table, dtype=np.uint32)
+
+
+def flat_table(n_roots: int) -> np.ndarray:
+    return np.zeros(n_roots, dtype=np.uint32)
+
+
+def _score_bits(bits: np.ndarray, resid, table) -> tuple:
+    """(nfail, cost) int64 (n,) of verdicts ``bits`` (n, n_roots) bool and
+    residual values ``resid`` (n_resid, 8, n) u32."""
+    fail = ~np.asarray(bits, dtype=bool)
+    n, n_roots = fail.shape
+    table = np.asarray(table, dtype=np.int64)
+    kind, probe = table >> 16, table & 0xFFFF
+    dist = np.ones((n, n_roots), dtype=np.int64)
+    if (kind != FLAT).any():
+        resid = np.ascontiguousarray(resid, dtype="<u4")
+        pop = np.unpackbits(resid.view(np.uint8).reshape(resid.shape[0], 8, n, 4),
+                            axis=3).sum(axis=(1, 3)).astype(np.int64)          # (n_resid, n)
+        length = np.zeros(pop.shape, dtype=np.int64)
+        for i in range(8):                               # the highest non-zero limb wins
+            limb = resid[:, i, :]
+            length = np.where(limb != 0, 32 * i + np.frexp(limb.astype(np.float64))[1], length)
+        for k in np.flatnonzero(kind != FLAT):
+            dist[:, k] = (np.maximum(1, pop[probe[k]]) if kind[k] == HAMMING
+                          else 1 + length[probe[k]])
+    return fail.sum(axis=1).astype(np.int64), (fail * dist).sum(axis=1).astype(np.int64)
+
+
+def score_ref(masks: np.ndarray, resid, table, n_roots: int) -> tuple:
+    """The key ``(nfail, cost)`` of every lane, from host mask probes
+    ``masks`` (n_mask, 8, n) u32 and residual probes ``resid`` (n_resid, 8,
+    n) u32 — the specification of ``csrc/mg_walk.h``.  A failing root k costs
+    1 (FLAT), max(1, popcount(R_k)) (HAMMING) or 1 + bitlen(R_k)
+    (MAGNITUDE); cost is the sum over the failing roots."""
+    from .census import mask_bits
+    return _score_bits(mask_bits(masks, n_roots), resid, table)
+
+
+@dataclass
+class WalkResult:
+    leaves: np.ndarray         # (walkers, n_leaves, 8) u32: each walker's last base
+    nfail: np.ndarray          # (walkers,) its failing constraints
+    cost: np.ndarray           # (walkers,) and their summed distance
+    rounds: int                # rounds run (every walker runs them all)
+    trace: np.ndarray          # (walkers, max_rounds, 2) (nfail, cost) of each round's best
+    winner: int                # the walker of minimum (nfail, cost, w)
+    kernel_ms: float = 0.0     # device time of the rounds (not compared)
+
+
+def walk_ref(values_fn: Callable, leafgen, consts, starts, table, seed: int, lanes: int = 4096,
+             max_rounds: int = 64, sync_every: int = 8) -> WalkResult:
+    """The whole loop as ``mg_walk`` runs it.  ``values_fn`` maps an SoA leaf
+    array ``(n_leaves, 8, n)`` to ``(bits (n, n_roots) bool, resid (n_resid,
+    8, n) u32)``: the verdicts and the residual values.  Walker w moves under
+    the seed ``seed ^ w * CW``; all walkers stop at the first sync after one
+    of them has no failing root."""
+    bases = np.ascontiguousarray(starts, dtype=np.uint32).copy()
+    walkers = bases.shape[0]
+    if not 1 <= walkers <= MAX_WALKERS or bases.shape[2:] != (8,):
+        raise ValueError("starts must be (1..64 walkers, n_leaves, 8)")
+    sync_every = sync_every or 8
+    trace = np.zeros((walkers, max_rounds, 2), dtype=np.uint32)
+    keys: List[Optional[tuple]] = [None] * walkers
+    r = 0
+    while r < max_rounds and not any(k is not None and k[0] == 0 for k in keys):
+        stop = max_rounds if max_rounds - r < sync_every else r + sync_every
+        while r < stop:
+            nb = np.concatenate([mutate_ref(leafgen, consts, bases[w], seed ^ (w * CW & M64), r,
+                                            lanes) for w in range(walkers)], axis=2)
+            bits, resid = values_fn(nb)
+            nfail, cost = _score_bits(bits, resid, table)
+            for w in range(walkers):
+                nf, co = nfail[w * lanes:(w + 1) * lanes], cost[w * lanes:(w + 1) * lanes]
+                lane = int(np.lexsort((co, nf))[0])       # stable: the lowest lane of the minimum
+                key = (int(nf[lane]), int(co[lane]))
+                if keys[w] is None or key < keys[w]:
+                    bases[w], keys[w] = nb[:, :, w * lanes + lane], key
+                trace[w, r] = key
+            r += 1
+    nfail = np.array([k[0] for k in keys], dtype=np.int64)
+    cost = np.array([k[1] for k in keys], dtype=np.int64)
+    winner = min(range(walkers), key=lambda w: (keys[w], w))
+    return WalkResult(bases, nfail, cost, r, trace, winner)
+
+
+# ---------------------------------------------------------------------------
 # repair a missed group
 # ---------------------------------------------------------------------------
 
@@ -162,7 +329,7 @@ REPAIRED, STUCK = "repaired", "stuck"
 
 def repair_group(nodes: Sequence, n_cand: int = 1 << 16, form: str = "search", lanes: int = 4096,
                  max_rounds: int = 64, device: int = 0, seed: Optional[int] = None,
-                 sync_every: int = 8) -> dict:
+                 sync_every: int = 8, scored: bool = False, walkers: int = 1) -> dict:
     """Census, then local search, of ONE independent group (root k =
     ``nodes[k]``): the statuses of ``census.explain_group`` for a group that
     launches nothing, else ``repaired`` with ``assignment`` (a model of the
@@ -173,7 +340,17 @@ def repair_group(nodes: Sequence, n_cand: int = 1 << 16, form: str = "search", l
     leaves of ``best_index``; the verdict is a fresh evaluation of the full
     masked program on the returned leaves — root bit and every mask bit set
     — not the loop's counter.  In solve form only the free leaves move: the
-    construction's definitions recompute the rest."""
+    construction's definitions recompute the rest.
+
+    ``scored``: the scored walk (``mg_walk``) of ``walkers``
+    walkers instead: the program also carries the residual probes of
+    :func:`residuals`, ``repair`` is a :class:`WalkResult` and ``starts`` the
+    candidate indices the walkers left from — the census's ``best_index``,
+    then ``sole_index`` of its ``blockers()`` in rank order without
+    duplicates, then ``best_index`` again; ``table`` is the residual table
+    and, when the walk is stuck, ``failing`` the roots its winner still
+    fails.  The verdict is the same fresh evaluation, of the winner's
+    leaves."""
     from . import census as CS
     from . import model as M
     from .assign import unpack
@@ -191,17 +368,32 @@ def repair_group(nodes: Sequence, n_cand: int = 1 << 16, form: str = "search", l
         out.update(status=CS.UNSUPPORTED,
                    why="%d constraints (at most %d)" % (len(nodes), CS.MAX_ROOTS))
         return out
+    # (built before the mask: a program's schedule follows the node ids, and a
+    # wide mask leaves the compiler's spill budget little room)
+    resid, table = residuals(nodes) if scored else ([], flat_table(len(nodes)))
     try:
         ground = M._ground_value(CS._compile(nodes, (), form))
         if ground is not None:
             out["status"] = CS.GROUND_TRUE if ground else CS.GROUND_FALSE
             return out
         masked = CS._compile(nodes, CS.mask_probes(nodes), form)
+        if resid:
+            # residuals the compiler folds or cannot place: the walkers rank by
+            # the count alone
+            try:
+                with_resid = CS._compile(nodes, CS.mask_probes(nodes) + resid, form)
+            except Unsupported:
+                with_resid = None
+            if with_resid is not None and \
+                    with_resid.n_user_probes == masked.n_user_probes + len(resid):
+                masked = with_resid
+            else:
+                resid, table = [], flat_table(len(nodes))
     except Unsupported as e:
         out.update(status=CS.UNSUPPORTED, why=str(e))
         return out
     n_mask = CS.n_mask_probes(len(nodes))
-    if masked.n_user_probes != n_mask:
+    if masked.n_user_probes != n_mask + len(resid):
         out["status"] = CS.DEAD if masked.n_user_probes == 0 else CS.UNSUPPORTED
         out["why"] = "%d mask probes compiled to %d" % (n_mask, masked.n_user_probes)
         return out
@@ -219,9 +411,29 @@ def repair_group(nodes: Sequence, n_cand: int = 1 << 16, form: str = "search", l
     leaves, _ = eng.witness(full, M.SEARCH_SEED, c.best_index)
     out["start"] = {"index": c.best_index, "nfail": c.best_nfail}
     out["repair"] = None
-    if c.best_nfail:
-        res = eng.repair(view, leaves, len(nodes), M.SEARCH_SEED if seed is None else seed, lanes,
-                         max_rounds, sync_every)
+    seed = M.SEARCH_SEED if seed is None else seed
+    if c.best_nfail and scored:
+        picks = [c.best_index]
+        for k in c.blockers():
+            if c.sole_index[k] >= 0 and int(c.sole_index[k]) not in picks:
+                picks.append(int(c.sole_index[k]))
+        picks = (picks + [c.best_index] * walkers)[:walkers]
+        starts = np.stack([leaves if i == c.best_index else eng.witness(full, M.SEARCH_SEED, i)[0]
+                           for i in picks])
+        wide = eng.load(CS.census_view(masked, n_mask + len(resid)), gens, prog_seed=0)
+        res = eng.walk(wide, starts, len(nodes), table, len(resid), seed, lanes, max_rounds,
+                       sync_every)
+        out.update(starts=picks, repair=res, table=table)
+        if res.nfail[res.winner]:
+            # which roots the winner still fails (one lane of the full program)
+            _, probes = eng.eval(full, np.ascontiguousarray(res.leaves[res.winner][:, :, None]),
+                                 want_probes=True)
+            holds = CS.mask_bits(probes[:n_mask], len(nodes))[0]
+            out["failing"] = [int(k) for k in np.flatnonzero(~holds)]
+            return out
+        leaves = res.leaves[res.winner]
+    elif c.best_nfail:
+        res = eng.repair(view, leaves, len(nodes), seed, lanes, max_rounds, sync_every)
         out["repair"] = res
         if res.nfail:
             return out

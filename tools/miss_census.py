@@ -19,6 +19,12 @@ usage: tools/miss_census.py --workload {c1,c3,c3o,c4,c5} --query N
            §3.9) from each launched group's best candidate: the trace, the
            outcome, and the device time per round next to the census's time
            for as many candidates in chunks of L
+       ... --walk [--walkers N] [--lanes L] [--rounds R]
+           after the census, the scored walk of N walkers
+           (16) from each launched group's census starts: every walker's
+           trace of (failing constraints, cost), the outcome, what the winner
+           still fails, and the device time per round of one walker and of N
+           beside mg_repair's on the same group
        tools/miss_census.py [workload] [n]
            the older census: which of a stream's first n queries the batched
            search misses, grouped by the shape of their newest constraint
@@ -190,6 +196,84 @@ def show_repair(rows, lanes):
                       g["census_ms_per_chunk"]))
 
 
+def _runs(trace):
+    """A walker's trace [(nfail, cost), ...] as 'nfail/cost x rounds' runs."""
+    out, prev, n = [], None, 0
+    for key in [tuple(int(v) for v in t) for t in trace] + [None]:
+        if key != prev and prev is not None:
+            out.append("%d/%d" % prev + (" x%d" % n if n > 1 else ""))
+            n = 0
+        prev, n = key, n + 1
+    return ", ".join(out)
+
+
+def walk_rows(wl, qi, n_cand, lanes, rounds, walkers):
+    """Per independent group of the query: what ``repair.repair_group(scored=
+    True)`` did with ``walkers`` walkers (status, starts, every walker's
+    trace, the roots the winner still fails with their kinds), and the device
+    time per round of mg_walk with one walker and with ``walkers``, beside
+    mg_repair's from the same start."""
+    import mythril_amd.model as M
+    from mythril_amd import repair as RP
+    from mythril_amd.smt import node as N
+    kinds = ("flat", "hamming", "magnitude")
+    rows = []
+    q = stream_query(wl, qi)
+    where = {}
+    for i, c in enumerate(q):
+        where.setdefault(c.id, []).append(i)
+    for group in M.dependence_buckets(q):
+        pos = [where[c.id].pop(0) for c in group]        # root k = constraint pos[k]
+        kw = dict(n_cand=n_cand, form="search", lanes=lanes, max_rounds=rounds)
+        g = RP.repair_group(group, scored=True, walkers=walkers, **kw)
+        row = {"constraints": len(group), "status": g["status"]}
+        if "why" in g:
+            row["why"] = g["why"]
+        res = g.get("repair")
+        if res is not None:
+            t = g["table"]
+            row.update(starts=g["starts"], winner=res.winner, rounds=res.rounds, walkers=walkers,
+                       kinds={k: int((t >> 16 == i).sum()) for i, k in enumerate(kinds)},
+                       residual_probes=len({int(v) & 0xFFFF for v in t if int(v) >> 16}),
+                       nfail=[int(v) for v in res.nfail], cost=[int(v) for v in res.cost],
+                       traces=[_runs(res.trace[w, :res.rounds]) for w in range(walkers)],
+                       walk_kernel_ms=round(res.kernel_ms, 3),
+                       walk_ms_per_round=round(res.kernel_ms / max(1, res.rounds), 4))
+            row["failing"] = [{"root": k, "constraint": pos[k], "kind": kinds[int(t[k]) >> 16],
+                               "sexpr": N.to_sexpr(group[k], 3)} for k in g.get("failing", [])]
+            one = RP.repair_group(group, scored=True, walkers=1, **kw).get("repair")
+            flat = RP.repair_group(group, **kw).get("repair")
+            if one is not None:
+                row["walk1_ms_per_round"] = round(one.kernel_ms / max(1, one.rounds), 4)
+                row["walk1_rounds"] = one.rounds
+            if flat is not None:
+                row["repair_ms_per_round"] = round(flat.kernel_ms / max(1, flat.rounds), 4)
+                row["repair_rounds"] = flat.rounds
+        rows.append(row)
+    return rows
+
+
+def show_walk(rows, lanes):
+    for gi, g in enumerate(rows):
+        print(" walk group %d: %d constraints -> %s%s" % (
+            gi, g["constraints"], g["status"], (" (%s)" % g["why"]) if "why" in g else ""))
+        if "traces" not in g:
+            continue
+        print("  roots by kind: %s; %d residual probes" % (
+            " ".join("%s %d" % kv for kv in g["kinds"].items()), g["residual_probes"]))
+        print("  %d walkers, %d rounds of %d lanes each; winner: walker %d" % (
+            g["walkers"], g["rounds"], lanes, g["winner"]))
+        for w, tr in enumerate(g["traces"]):
+            print("   walker %2d from candidate %d: ends %d/%d; nfail/cost per round: %s" % (
+                w, g["starts"][w], g["nfail"][w], g["cost"][w], tr))
+        for f in g["failing"]:
+            print("  the winner still fails constraint #%d (root %d, %s): %s" % (
+                f["constraint"], f["root"], f["kind"], f["sexpr"]))
+        print("  device time per round: mg_walk x%d %.4f ms; mg_walk x1 %s ms; mg_repair %s ms" % (
+            g["walkers"], g["walk_ms_per_round"], g.get("walk1_ms_per_round"),
+            g.get("repair_ms_per_round")))
+
+
 def show(r):
     print("== %s query %d%s: %d constraints, %d candidates per group (%.0f ms in all)" % (
         r["workload"], r["query"], " (top-level ands split, i.j = conjunct j of constraint i)"
@@ -234,6 +318,9 @@ def main():
                     help="census the query with every top-level `and` split into its conjuncts")
     ap.add_argument("--repair", action="store_true",
                     help="then run the local search from each group's best candidate")
+    ap.add_argument("--walk", action="store_true",
+                    help="then run the scored walk from each group's census starts")
+    ap.add_argument("--walkers", type=int, default=16)
     ap.add_argument("--lanes", type=int, default=4096)
     ap.add_argument("--rounds", type=int, default=64)
     a = ap.parse_args()
@@ -250,6 +337,10 @@ def main():
     if a.repair:
         for r in reports:
             r["repair"] = repair_rows(r["workload"], r["query"], a.candidates, a.lanes, a.rounds)
+    if a.walk:
+        for r in reports:
+            r["walk"] = walk_rows(r["workload"], r["query"], a.candidates, a.lanes, a.rounds,
+                                  a.walkers)
     if a.json:
         print(json.dumps(reports, indent=1))
     else:
@@ -257,6 +348,8 @@ def main():
             show(r)
             if a.repair:
                 show_repair(r["repair"], a.lanes)
+            if a.walk:
+                show_walk(r["walk"], a.lanes)
 
 
 if __name__ == "__main__":
