@@ -274,6 +274,42 @@ int mg_walk_score_host(const uint32_t* masks, const uint32_t* resid, const uint3
                        uint32_t n_roots, uint32_t n_resid, uint64_t n, uint32_t* nfail,
                        uint32_t* cost);
 
+/* Scored walk with tree distances: mg_walk, but a failing
+ * root may cost the branch distance of a small postfix program over atoms
+ * (and = sum, or = minimum), so a root made of equalities and orders under
+ * and / or / ite / store chains has a gradient.  The program carries, from
+ * probe mask_probe0 on: the root mask (ceil(n_roots / 256) probes), the atom
+ * mask (ceil(n_atoms / 256) probes, bit i: atom i holds), then n_resid
+ * residual probes.  roots[k] is a table entry of mg_walk or 1 << 31 | offset
+ * of the root's program in code; atoms[i] = kind << 16 | residual probe;
+ * code: words op << 16 | argument (csrc/mg_walk_tree.h fixes the encoding and
+ * the limits; mythril_amd/repair.py distance_trees builds the tables,
+ * tree_score_ref is the specification).  Moves, rounds, walkers, outputs and
+ * workspace are those of mg_walk.  Refused without a launch: what mg_walk
+ * refuses, n_atoms above 1024, atom-mask or residual probes outside the
+ * program's probes, and tables mg_walk_tree_ok refuses (unknown kind or
+ * opcode, atom or residual index out of range, offset outside code, a stack
+ * that underflows or is deeper than 8, a program that does not end with one
+ * value, more than 32 atoms or 64 words per root). */
+int mg_walk_tree(mg_ctx* ctx, const mg_prog* prog,
+                 const uint32_t* starts /*[walkers][n_leaves][8]*/, uint32_t walkers,
+                 uint32_t n_roots, uint32_t mask_probe0, const uint32_t* roots /*[n_roots]*/,
+                 uint32_t n_atoms, const uint32_t* atoms /*[n_atoms] or NULL*/,
+                 const uint32_t* code /*[n_code] or NULL*/, uint32_t n_code, uint32_t n_resid,
+                 uint64_t seed, uint32_t lanes, uint32_t max_rounds, uint32_t sync_every,
+                 uint32_t* out_leaves /*[walkers][n_leaves][8]*/,
+                 uint32_t* out_nfail /*[walkers]*/, uint32_t* out_cost /*[walkers]*/,
+                 uint32_t* out_rounds, uint32_t* trace /*[walkers][max_rounds][2] or NULL*/,
+                 uint32_t* out_winner);
+/* Host-only (no GPU): mg_walk_tree's scoring function on n lanes.  masks,
+ * amasks: the rows of the root mask and of the atom mask ([.. * 8][n] u32;
+ * amasks may be NULL when n_atoms = 0), resid as for mg_walk_score_host.
+ * MG_E_ARG for a null pointer and for tables mg_walk_tree refuses. */
+int mg_walk_tree_score_host(const uint32_t* masks, const uint32_t* amasks, const uint32_t* resid,
+                            const uint32_t* roots, uint32_t n_roots, const uint32_t* atoms,
+                            uint32_t n_atoms, const uint32_t* code, uint32_t n_code,
+                            uint32_t n_resid, uint64_t n, uint32_t* nfail, uint32_t* cost);
+
 /* Corpus batches: many programs, one launch.  Device-pointer API for
  * resident benchmarking; stream is a hipStream_t (NULL = the context's own
  * stream, which the synchronous calls also use).

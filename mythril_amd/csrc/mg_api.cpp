@@ -26,6 +26,7 @@
 #include "mg_census.h"
 #include "mg_repair.h"
 #include "mg_walk.h"
+#include "mg_walk_tree.h"
 
 // the interpreter of each register layout (mg_interp_asm.hip, one
 // translation unit per layout; mg_find_layout lists them)
@@ -79,6 +80,16 @@ hipError_t mg_launch_walk_pick(const uint32_t* d_masks, const uint32_t* d_resid,
                                const uint32_t* d_consts, uint32_t n_leaves, uint64_t seed,
                                uint32_t r, uint32_t max_rounds, mg_walk_state* d_state,
                                uint32_t* d_trace, hipStream_t stream);
+// the same round with the tree scoring (mg_walk_tree.hip): the score kernel of
+// DESIGN.md §3.11, then the adopt step of mg_walk.hip
+hipError_t mg_launch_walk_tree_pick(const uint32_t* d_masks, const uint32_t* d_amasks,
+                                    const uint32_t* d_resid, const uint32_t* d_roots,
+                                    const uint32_t* d_atoms, const uint32_t* d_code,
+                                    uint32_t lanes, uint32_t walkers, uint32_t n_roots,
+                                    uint32_t* d_bases, const mg_leafgen* d_gen,
+                                    const uint32_t* d_consts, uint32_t n_leaves, uint64_t seed,
+                                    uint32_t r, uint32_t max_rounds, mg_walk_state* d_state,
+                                    uint32_t* d_trace, hipStream_t stream);
 
 
 struct mg_ctx {
@@ -986,36 +997,59 @@ static bool walk_table_ok(const uint32_t* table, uint32_t n_roots, uint32_t n_re
     return true;
 }
 
-// The scored walk.  Rounds are queued back to back; after
-// every sync_every rounds the host reads the walkers' states (16 bytes each)
-// and stops once one of them has no failing root.
-int mg_walk(mg_ctx* ctx, const mg_prog* prog, const uint32_t* starts, uint32_t walkers,
-            uint32_t n_roots, uint32_t mask_probe0, const uint32_t* table, uint32_t n_resid,
-            uint64_t seed, uint32_t lanes, uint32_t max_rounds, uint32_t sync_every,
-            uint32_t* out_leaves, uint32_t* out_nfail, uint32_t* out_cost, uint32_t* out_rounds,
-            uint32_t* trace, uint32_t* out_winner) {
+// what scores a walk's neighbours: the residual table of mg_walk (no atoms, no
+// code) or the tree tables of mg_walk_tree (table: its root entries)
+struct walk_scoring {
+    const uint32_t* table;
+    const uint32_t* atoms;
+    uint32_t n_atoms;
+    const uint32_t* code;
+    uint32_t n_code;
+    bool tree;
+};
+
+// The scored walk.  Rounds are queued back to back;
+// after every sync_every rounds the host reads the walkers' states (16 bytes
+// each) and stops once one of them has no failing root.
+static int walk_run(mg_ctx* ctx, const mg_prog* prog, const uint32_t* starts, uint32_t walkers,
+                    uint32_t n_roots, uint32_t mask_probe0, const walk_scoring& sc,
+                    uint32_t n_resid, uint64_t seed, uint32_t lanes, uint32_t max_rounds,
+                    uint32_t sync_every, uint32_t* out_leaves, uint32_t* out_nfail,
+                    uint32_t* out_cost, uint32_t* out_rounds, uint32_t* trace,
+                    uint32_t* out_winner) {
+    const uint32_t* table = sc.table;
     if (!ctx || !prog || !starts || !table || !out_leaves || !out_nfail || !out_cost ||
-        !out_rounds || !out_winner)
+        !out_rounds || !out_winner || (sc.n_atoms && !sc.atoms) || (sc.n_code && !sc.code))
         return fail(ctx, MG_E_ARG, "null argument");
     if (prog->n_leaves == 0) return fail(ctx, MG_E_ARG, "walk: the program has no leaves");
     if (walkers < 1 || walkers > MG_WALK_MAX_WALKERS)
         return fail(ctx, MG_E_ARG, "walk: %u walkers outside 1..%u", walkers, MG_WALK_MAX_WALKERS);
     if (n_roots < 1 || n_roots > MG_CENSUS_MAX_ROOTS)
         return fail(ctx, MG_E_ARG, "walk: n_roots %u outside 1..%u", n_roots, MG_CENSUS_MAX_ROOTS);
-    const uint32_t n_mask = (n_roots + 255) / 256;
+    if (sc.n_atoms > MG_WT_MAX_ATOMS)
+        return fail(ctx, MG_E_ARG, "walk_tree: %u atoms (at most %u)", sc.n_atoms,
+                    MG_WT_MAX_ATOMS);
+    // the root mask, then the atom mask (tree scoring), then the residuals
+    const uint32_t n_mask = (n_roots + 255) / 256, n_amask = (sc.n_atoms + 255) / 256;
     if (mask_probe0 >= prog->n_probes || n_mask > prog->n_probes - mask_probe0 ||
-        n_resid > prog->n_probes - mask_probe0 - n_mask)
+        n_amask > prog->n_probes - mask_probe0 - n_mask ||
+        n_resid > prog->n_probes - mask_probe0 - n_mask - n_amask)
         return fail(ctx, MG_E_ARG, "walk: mask probes %u..%u and %u residual probes outside the "
-                    "program's %u probes", mask_probe0, mask_probe0 + n_mask - 1, n_resid,
-                    prog->n_probes);
+                    "program's %u probes", mask_probe0, mask_probe0 + n_mask + n_amask - 1,
+                    n_resid, prog->n_probes);
     if (lanes < 1 || lanes > MG_REPAIR_MAX_LANES)
         return fail(ctx, MG_E_ARG, "walk: %u lanes outside 1..%u", lanes, MG_REPAIR_MAX_LANES);
     if (max_rounds < 1 || max_rounds > MG_REPAIR_MAX_ROUNDS)
         return fail(ctx, MG_E_ARG, "walk: %u rounds outside 1..%u", max_rounds,
                     MG_REPAIR_MAX_ROUNDS);
-    if (!walk_table_ok(table, n_roots, n_resid))
+    if (sc.tree) {
+        if (!mg_walk_tree_ok(table, n_roots, sc.atoms, sc.n_atoms, sc.code, sc.n_code, n_resid))
+            return fail(ctx, MG_E_ARG, "walk_tree: malformed tables (mg_walk_tree_ok: kinds, "
+                        "atom and residual indices, offsets, stack depth, limits per root)");
+    } else if (!walk_table_ok(table, n_roots, n_resid)) {
         return fail(ctx, MG_E_ARG, "walk: a table entry names an unknown kind or a residual "
                     "probe at or above %u", n_resid);
+    }
     const uint64_t total = (uint64_t)walkers * lanes;
     if (total > MG_CENSUS_MAX_PROBE_BYTES / 32 / prog->n_probes)
         return fail(ctx, MG_E_ARG, "walk: %u probes x %u walkers x %u lanes exceed a %zu MiB "
@@ -1032,11 +1066,13 @@ int mg_walk(mg_ctx* ctx, const mg_prog* prog, const uint32_t* starts, uint32_t w
                  gen_b = (size_t)n_leaves * sizeof(mg_leafgen), table_b = (size_t)n_roots * 4,
                  trace_b = (size_t)walkers * max_rounds * 8, root_b = words * 8,
                  leaf_b = (size_t)n_leaves * 8 * total * 4,
-                 probe_b = (size_t)prog->n_probes * 8 * total * 4;
+                 probe_b = (size_t)prog->n_probes * 8 * total * 4,
+                 atom_b = (size_t)sc.n_atoms * 4, code_b = (size_t)sc.n_code * 4;
     const size_t off_base = align(state_b), off_gen = off_base + align(base_b),
                  off_table = off_gen + align(gen_b), off_trace = off_table + align(table_b),
                  off_root = off_trace + align(trace_b), off_leaf = off_root + align(root_b),
-                 off_probe = off_leaf + align(leaf_b), bytes = off_probe + align(probe_b);
+                 off_probe = off_leaf + align(leaf_b), off_atom = off_probe + align(probe_b),
+                 off_code = off_atom + align(atom_b), bytes = off_code + align(code_b);
     void* ws;
     int rc = workspace(ctx, bytes + 256, &ws);
     if (rc) return rc;
@@ -1048,12 +1084,20 @@ int mg_walk(mg_ctx* ctx, const mg_prog* prog, const uint32_t* starts, uint32_t w
     uint32_t* d_trace = (uint32_t*)(w + off_trace);
     uint32_t* d_leaves = (uint32_t*)(w + off_leaf);
     uint32_t* d_probes = (uint32_t*)(w + off_probe);
+    uint32_t* d_atoms = (uint32_t*)(w + off_atom);
+    uint32_t* d_code = (uint32_t*)(w + off_code);
     HIPCHECK(ctx, hipMemsetAsync(d_state, 0xFF, state_b, ctx->stream));
     HIPCHECK(ctx, hipMemsetAsync(d_trace, 0, trace_b, ctx->stream));
     HIPCHECK(ctx, hipMemcpyAsync(d_bases, starts, base_b, hipMemcpyHostToDevice, ctx->stream));
     HIPCHECK(ctx, hipMemcpyAsync(d_gen, prog->leafgen.data(), gen_b, hipMemcpyHostToDevice,
                                  ctx->stream));
     HIPCHECK(ctx, hipMemcpyAsync(d_table, table, table_b, hipMemcpyHostToDevice, ctx->stream));
+    if (atom_b)
+        HIPCHECK(ctx, hipMemcpyAsync(d_atoms, sc.atoms, atom_b, hipMemcpyHostToDevice,
+                                     ctx->stream));
+    if (code_b)
+        HIPCHECK(ctx, hipMemcpyAsync(d_code, sc.code, code_b, hipMemcpyHostToDevice,
+                                     ctx->stream));
     mg_run run = empty_run();
     run.leaves = d_leaves;
     run.root_bits = (uint64_t*)(w + off_root);
@@ -1062,7 +1106,8 @@ int mg_walk(mg_ctx* ctx, const mg_prog* prog, const uint32_t* starts, uint32_t w
     run.n_assign = total;
     run.words_per_prog = words;
     const uint32_t* d_masks = d_probes + (size_t)mask_probe0 * 8 * total;
-    const uint32_t* d_resid = d_masks + (size_t)n_mask * 8 * total;
+    const uint32_t* d_amasks = d_masks + (size_t)n_mask * 8 * total;
+    const uint32_t* d_resid = d_amasks + (size_t)n_amask * 8 * total;
     const uint32_t* d_consts = prog->h_desc.consts;       // the first n_consts entries: as loaded
     std::vector<mg_walk_state> h_state(walkers);
     bool done = false;
@@ -1074,9 +1119,17 @@ int mg_walk(mg_ctx* ctx, const mg_prog* prog, const uint32_t* starts, uint32_t w
             HIPCHECK(ctx, mg_launch_walk_round(d_bases, d_gen, d_consts, n_leaves, seed, r, lanes,
                                                walkers, d_leaves, ctx->stream));
             HIPCHECK(ctx, launch(ctx, 0, prog->d_desc, 1, run, prog->n_lds, ctx->stream));
-            HIPCHECK(ctx, mg_launch_walk_pick(d_masks, d_resid, d_table, lanes, walkers, n_roots,
-                                              d_bases, d_gen, d_consts, n_leaves, seed, r,
-                                              max_rounds, d_state, d_trace, ctx->stream));
+            if (sc.tree)
+                HIPCHECK(ctx, mg_launch_walk_tree_pick(d_masks, d_amasks, d_resid, d_table,
+                                                       d_atoms, d_code, lanes, walkers, n_roots,
+                                                       d_bases, d_gen, d_consts, n_leaves, seed,
+                                                       r, max_rounds, d_state, d_trace,
+                                                       ctx->stream));
+            else
+                HIPCHECK(ctx, mg_launch_walk_pick(d_masks, d_resid, d_table, lanes, walkers,
+                                                  n_roots, d_bases, d_gen, d_consts, n_leaves,
+                                                  seed, r, max_rounds, d_state, d_trace,
+                                                  ctx->stream));
         }
         timing_end(ctx);
         HIPCHECK(ctx, hipMemcpyAsync(h_state.data(), d_state, state_b, hipMemcpyDeviceToHost,
@@ -1099,6 +1152,47 @@ int mg_walk(mg_ctx* ctx, const mg_prog* prog, const uint32_t* starts, uint32_t w
     }
     *out_rounds = r;
     *out_winner = win;
+    return MG_OK;
+}
+
+int mg_walk(mg_ctx* ctx, const mg_prog* prog, const uint32_t* starts, uint32_t walkers,
+            uint32_t n_roots, uint32_t mask_probe0, const uint32_t* table, uint32_t n_resid,
+            uint64_t seed, uint32_t lanes, uint32_t max_rounds, uint32_t sync_every,
+            uint32_t* out_leaves, uint32_t* out_nfail, uint32_t* out_cost, uint32_t* out_rounds,
+            uint32_t* trace, uint32_t* out_winner) {
+    const walk_scoring sc = {table, nullptr, 0, nullptr, 0, false};
+    return walk_run(ctx, prog, starts, walkers, n_roots, mask_probe0, sc, n_resid, seed, lanes,
+                    max_rounds, sync_every, out_leaves, out_nfail, out_cost, out_rounds, trace,
+                    out_winner);
+}
+
+// The scored walk with tree distances: mg_walk with the
+// tables of mg_walk_tree.h in place of the residual table.
+int mg_walk_tree(mg_ctx* ctx, const mg_prog* prog, const uint32_t* starts, uint32_t walkers,
+                 uint32_t n_roots, uint32_t mask_probe0, const uint32_t* roots, uint32_t n_atoms,
+                 const uint32_t* atoms, const uint32_t* code, uint32_t n_code, uint32_t n_resid,
+                 uint64_t seed, uint32_t lanes, uint32_t max_rounds, uint32_t sync_every,
+                 uint32_t* out_leaves, uint32_t* out_nfail, uint32_t* out_cost,
+                 uint32_t* out_rounds, uint32_t* trace, uint32_t* out_winner) {
+    const walk_scoring sc = {roots, atoms, n_atoms, code, n_code, true};
+    return walk_run(ctx, prog, starts, walkers, n_roots, mask_probe0, sc, n_resid, seed, lanes,
+                    max_rounds, sync_every, out_leaves, out_nfail, out_cost, out_rounds, trace,
+                    out_winner);
+}
+
+// Host only: the tree scoring (mg_walk_tree.h) on n lanes of host rows, as
+// the score kernel runs it.  amasks may be null when there are no atoms.
+int mg_walk_tree_score_host(const uint32_t* masks, const uint32_t* amasks, const uint32_t* resid,
+                            const uint32_t* roots, uint32_t n_roots, const uint32_t* atoms,
+                            uint32_t n_atoms, const uint32_t* code, uint32_t n_code,
+                            uint32_t n_resid, uint64_t n, uint32_t* nfail, uint32_t* cost) {
+    if (!masks || !roots || !nfail || !cost || (n_resid && !resid) || (n_atoms && !amasks))
+        return MG_E_ARG;
+    if (!mg_walk_tree_ok(roots, n_roots, atoms, n_atoms, code, n_code, n_resid)) return MG_E_ARG;
+    uint32_t stack[MG_WT_STACK];
+    for (uint64_t a = 0; a < n; ++a)
+        mg_walk_tree_score_lane(masks, amasks, resid, n, a, roots, atoms, code, n_roots, true,
+                                stack, 1, nfail + a, cost + a);
     return MG_OK;
 }
 

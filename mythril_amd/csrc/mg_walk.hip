@@ -151,3 +151,17 @@ hipError_t mg_launch_walk_pick(const uint32_t* d_masks, const uint32_t* d_resid,
                        d_trace);
     return hipGetLastError();
 }
+
+// the adopt step alone, for a round that scores with another kernel
+// (mg_walk_tree.hip)
+hipError_t mg_launch_walk_adopt(uint32_t* d_bases, const mg_leafgen* d_gen,
+                                const uint32_t* d_consts, uint32_t n_leaves, uint64_t seed,
+                                uint32_t r, uint32_t lanes, uint32_t walkers, uint32_t max_rounds,
+                                mg_walk_state* d_state, uint32_t* d_trace, hipStream_t stream) {
+    if (!walk_shape_ok(walkers, lanes, n_leaves, r) || r >= max_rounds)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(mg_walk_adopt, dim3((walkers + 63) / 64), dim3(64), 0, stream, d_bases,
+                       d_gen, d_consts, n_leaves, seed, r, lanes, walkers, max_rounds, d_state,
+                       d_trace);
+    return hipGetLastError();
+}

@@ -34,7 +34,7 @@ EXPORTS = ("mg_init", "mg_init_layout", "mg_layouts", "mg_free", "mg_last_error"
            "mg_batch_search_probes", "mg_keccak256", "mg_version", "mg_config", "mg_translate",
            "mg_asm_digest", "mg_asm_digest_layout", "mg_last_kernel_ms", "mg_jit_attach",
            "mg_jit_detach", "mg_runtime_info", "mg_census", "mg_repair", "mg_repair_mutate_host",
-           "mg_walk", "mg_walk_score_host")
+           "mg_walk", "mg_walk_score_host", "mg_walk_tree", "mg_walk_tree_score_host")
 
 
 def layouts() -> Dict[int, Tuple[int, int]]:
@@ -124,6 +124,9 @@ def load_library(path: str = _LIB_PATH, check_digest: bool = True):
         lib.mg_walk.argtypes = [p, p, p, u32, u32, u32, p, u32, u64, u32, u32, u32, p, p, p,
                                 C.POINTER(u32), p, C.POINTER(u32)]
         lib.mg_walk_score_host.argtypes = [p, p, p, u32, u32, u64, p, p]
+        lib.mg_walk_tree.argtypes = [p, p, p, u32, u32, u32, p, u32, p, p, u32, u32, u64, u32, u32,
+                                     u32, p, p, p, C.POINTER(u32), p, C.POINTER(u32)]
+        lib.mg_walk_tree_score_host.argtypes = [p, p, p, p, u32, p, u32, p, u32, u32, u64, p, p]
         lib.mg_batch_create.argtypes = [p, C.POINTER(p), u32, C.POINTER(p)]
         lib.mg_batch_free.argtypes = [p]
         lib.mg_batch_free.restype = None
@@ -379,6 +382,45 @@ class Engine:
         return WalkResult(out[:, :n_leaves], nfail.astype(np.int64), cost.astype(np.int64),
                           int(rounds.value), trace, int(winner.value), self.last_kernel_ms())
 
+    def walk_tree(self, lp: LoadedProgram, starts: np.ndarray, n_roots: int, trees, seed: int,
+                  lanes: int = 4096, max_rounds: int = 64, sync_every: int = 8,
+                  mask_probe0: int = 0, n_resid: Optional[int] = None):
+        """Scored walk with tree distances (mg_walk_tree):
+        :meth:`walk` on a program that carries, from probe ``mask_probe0`` on,
+        its root mask, the atom mask and the residual probes of ``trees``
+        (``repair.distance_trees``; ``n_resid``: how many residual probes the
+        program has, by default the trees'): a
+        :class:`mythril_amd.repair.WalkResult`."""
+        from .repair import WalkResult
+        n_leaves = len(lp.program.leaves)
+        starts = np.ascontiguousarray(starts, dtype=np.uint32)
+        if starts.ndim != 3 or starts.shape[1:] != (n_leaves, 8):
+            raise ValueError("starts must be (walkers, n_leaves, 8)")
+        walkers = starts.shape[0]
+        roots = np.ascontiguousarray(trees.roots, dtype=np.uint32)
+        atoms = np.ascontiguousarray(trees.atoms, dtype=np.uint32)
+        code = np.ascontiguousarray(trees.code, dtype=np.uint32)
+        if roots.shape != (max(0, int(n_roots)),) and 1 <= int(n_roots) <= 1024:
+            raise ValueError("trees.roots must have n_roots entries")
+        n_resid = len(trees.probes) if n_resid is None else n_resid
+        w1, r1 = max(1, min(walkers, 64)), max(1, min(int(max_rounds), 1 << 16))
+        out = np.zeros((w1, max(1, n_leaves), 8), dtype=np.uint32)
+        nfail, cost = np.zeros(w1, dtype=np.uint32), np.zeros(w1, dtype=np.uint32)
+        trace = np.zeros((w1, r1, 2), dtype=np.uint32)
+        rounds, winner = C.c_uint32(0), C.c_uint32(0)
+        rc = self.lib.mg_walk_tree(self._ctx, lp.handle,
+                                   _ptr(starts) if starts.size else _ptr(out), walkers,
+                                   max(0, int(n_roots)), mask_probe0,
+                                   _ptr(roots) if roots.size else _ptr(nfail), atoms.size,
+                                   _ptr(atoms) if atoms.size else None,
+                                   _ptr(code) if code.size else None, code.size,
+                                   max(0, int(n_resid)), seed & (2**64 - 1), lanes, max_rounds,
+                                   sync_every, _ptr(out), _ptr(nfail), _ptr(cost),
+                                   C.byref(rounds), _ptr(trace), C.byref(winner))
+        self._check(rc, "mg_walk_tree")
+        return WalkResult(out[:, :n_leaves], nfail.astype(np.int64), cost.astype(np.int64),
+                          int(rounds.value), trace, int(winner.value), self.last_kernel_ms())
+
     def witness(self, lp: LoadedProgram, seed: int, index: int):
         """Leaves and probe values of candidate ``index`` (one lane): what a
         solve-mode program's model needs besides the generated leaves."""
@@ -559,6 +601,41 @@ def walk_score_host(masks: np.ndarray, resid: Optional[np.ndarray], table: np.nd
                                 _ptr(nfail), _ptr(cost))
     if rc != 0:
         raise EngineError("mg_walk_score_host failed (%d)" % rc)
+    return nfail[:n], cost[:n]
+
+
+def walk_tree_score_host(masks: np.ndarray, amasks: Optional[np.ndarray],
+                         resid: Optional[np.ndarray], trees, n_roots: int,
+                         n_resid: Optional[int] = None):
+    """Host-only (no GPU): ``(nfail, cost)`` (n,) u32 of the lanes of root-mask
+    probes ``masks``, atom-mask probes ``amasks`` and residual probes
+    ``resid`` (each (.., 8, n) u32) from the library's own tree scoring
+    (mg_walk_tree_score_host; ``repair.tree_score_ref`` is its specification);
+    ``trees``: roots, atoms and code (``repair.Trees``)."""
+    lib = load_library()
+    masks = np.ascontiguousarray(masks, dtype=np.uint32)
+    n = masks.shape[2]
+    have = 0 if resid is None else resid.shape[0]
+    n_resid = have if n_resid is None else n_resid
+    resid = None if not have else np.ascontiguousarray(resid, dtype=np.uint32)
+    roots = np.ascontiguousarray(trees.roots, dtype=np.uint32)
+    atoms = np.ascontiguousarray(trees.atoms, dtype=np.uint32)
+    code = np.ascontiguousarray(trees.code, dtype=np.uint32)
+    if atoms.size:
+        amasks = np.ascontiguousarray(amasks, dtype=np.uint32)
+        if amasks.ndim != 3 or amasks.shape[1:] != (8, n) or amasks.shape[0] * 256 < atoms.size:
+            raise ValueError("amasks must be (ceil(n_atoms / 256), 8, n)")
+    if roots.size < n_roots or masks.shape[0] * 256 < n_roots or (
+            have and resid.shape[1:] != (8, n)) or n_resid > have:
+        raise EngineError("mg_walk_tree_score_host: tables or rows shorter than n_roots, n_resid")
+    nfail, cost = np.zeros(max(1, n), dtype=np.uint32), np.zeros(max(1, n), dtype=np.uint32)
+    rc = lib.mg_walk_tree_score_host(_ptr(masks), _ptr(amasks) if atoms.size else None,
+                                     _ptr(resid), _ptr(roots) if roots.size else None, n_roots,
+                                     _ptr(atoms) if atoms.size else None, atoms.size,
+                                     _ptr(code) if code.size else None, code.size, n_resid, n,
+                                     _ptr(nfail), _ptr(cost))
+    if rc != 0:
+        raise EngineError("mg_walk_tree_score_host failed (%d)" % rc)
     return nfail[:n], cost[:n]
 
 

@@ -190,9 +190,10 @@ SHAPE_GATE = True
 REFUTE = True              # host refutation before compiling (refute.py)
 # opt-in (MYTHRIL_GPU_REPAIR=1): a group the search missed is handed to the
 # local search (repair.py) while search budget remains;
-# MYTHRIL_GPU_REPAIR=2: to the scored walk of REPAIR_WALKERS walkers (§3.10)
+# MYTHRIL_GPU_REPAIR=2: to the scored walk of REPAIR_WALKERS walkers (§3.10);
+# MYTHRIL_GPU_REPAIR=3: to that walk scored by distance trees (§3.11)
 REPAIR = False
-REPAIR_SCORED = False
+REPAIR_SCORED = False      # repair_group's `scored`: False, True or "tree"
 REPAIR_WALKERS = 16
 SHAPE_MIN, SHAPE_FLOOR, SHAPE_PROBE = 4, 1.0 / 16, 8
 
@@ -207,7 +208,8 @@ def configure_from_env(env=None) -> None:
     ``MYTHRIL_GPU_REFUTE=0`` the host refutation (refute.py),
     ``MYTHRIL_GPU_REPAIR=1`` turns the local search of missed groups on
     (repair.py; off by default), ``MYTHRIL_GPU_REPAIR=2`` its scored walk of
-    several walkers instead."""
+    several walkers instead, ``MYTHRIL_GPU_REPAIR=3`` that walk scored by
+    distance trees."""
     global GPU_ENABLED, DEVICES, SEARCH_CANDIDATES, SEARCH_BUDGET_MS, SHAPE_GATE, REFUTE, REPAIR
     global REPAIR_SCORED
     import os
@@ -224,8 +226,8 @@ def configure_from_env(env=None) -> None:
     SHAPE_GATE = env.get("MYTHRIL_GPU_ADAPTIVE", "1").strip().lower() not in ("0", "off", "false",
                                                                              "no")
     REFUTE = env.get("MYTHRIL_GPU_REFUTE", "1").strip().lower() not in ("0", "off", "false", "no")
-    REPAIR_SCORED = env.get("MYTHRIL_GPU_REPAIR", "0").strip() == "2"
-    REPAIR = REPAIR_SCORED or env.get("MYTHRIL_GPU_REPAIR", "0").strip().lower() in (
+    REPAIR_SCORED = {"2": True, "3": "tree"}.get(env.get("MYTHRIL_GPU_REPAIR", "0").strip(), False)
+    REPAIR = bool(REPAIR_SCORED) or env.get("MYTHRIL_GPU_REPAIR", "0").strip().lower() in (
         "1", "on", "true", "yes")
 
 
@@ -828,7 +830,7 @@ def gpu_search(nodes: Sequence[N.Node], budget_ms: float):
 
 def _repair_misses(buckets, hits, budget_ms: float, t_start: float):
     """``hits`` with every missed group the local search repairs
-    (``repair.repair_group``, MYTHRIL_GPU_REPAIR=1, or 2: scored) replaced by (0, its
+    (``repair.repair_group``, MYTHRIL_GPU_REPAIR=1, 2: scored, 3: trees) replaced by (0, its
     assignment), as long as search budget remains; stops at the first group
     it cannot repair (the query is a miss then).  The witness goes through
     ``_accept`` like any other."""
@@ -1184,7 +1186,8 @@ def repair_miss(constraints, **kw) -> dict:
     """Census, then local search from its best candidate, per independent
     group of ``constraints`` (``mythril_amd/repair.py`` ``repair``; keywords
     ``n_cand``, ``form``, ``lanes``, ``max_rounds``, ``device``, and
-    ``scored``, ``walkers`` for the scored walk of DESIGN.md §3.10): ``groups``
+    ``scored``, ``walkers`` for the scored walk of DESIGN.md §3.10, ``scored="tree"``
+    for its tree distances of §3.11): ``groups``
     and, when every group was repaired, the joined ``model``.  Touches no
     memo, gate or counter; the model is not verified by z3 here."""
     from .repair import repair

@@ -285,12 +285,17 @@ class WalkResult:
 
 
 def walk_ref(values_fn: Callable, leafgen, consts, starts, table, seed: int, lanes: int = 4096,
-             max_rounds: int = 64, sync_every: int = 8) -> WalkResult:
+             max_rounds: int = 64, sync_every: int = 8, score: Optional[Callable] = None
+             ) -> WalkResult:
     """The whole loop as ``mg_walk`` runs it.  ``values_fn`` maps an SoA leaf
     array ``(n_leaves, 8, n)`` to ``(bits (n, n_roots) bool, resid (n_resid,
     8, n) u32)``: the verdicts and the residual values.  Walker w moves under
     the seed ``seed ^ w * CW``; all walkers stop at the first sync after one
-    of them has no failing root."""
+    of them has no failing root.
+
+    ``score``: another scoring of the same loop (``mg_walk_tree``): called
+    with what ``values_fn`` returns, it gives ``(nfail, cost)`` per lane, and
+    ``table`` is not read (:func:`tree_scoring`)."""
     bases = np.ascontiguousarray(starts, dtype=np.uint32).copy()
     walkers = bases.shape[0]
     if not 1 <= walkers <= MAX_WALKERS or bases.shape[2:] != (8,):
@@ -304,8 +309,11 @@ def walk_ref(values_fn: Callable, leafgen, consts, starts, table, seed: int, lan
         while r < stop:
             nb = np.concatenate([mutate_ref(leafgen, consts, bases[w], seed ^ (w * CW & M64), r,
                                             lanes) for w in range(walkers)], axis=2)
-            bits, resid = values_fn(nb)
-            nfail, cost = _score_bits(bits, resid, table)
+            if score is None:
+                bits, resid = values_fn(nb)
+                nfail, cost = _score_bits(bits, resid, table)
+            else:
+                nfail, cost = score(*values_fn(nb))
             for w in range(walkers):
                 nf, co = nfail[w * lanes:(w + 1) * lanes], cost[w * lanes:(w + 1) * lanes]
                 lane = int(np.lexsort((co, nf))[0])       # stable: the lowest lane of the minimum
@@ -321,6 +329,392 @@ def walk_ref(values_fn: Callable, leafgen, consts, starts, table, seed: int, lan
 
 
 # ---------------------------------------------------------------------------
+# distance trees: branch distance through and, or, ite and
+# store chains
+# ---------------------------------------------------------------------------
+
+# the constants of csrc/mg_walk_tree.h
+WT_TREE = 1 << 31
+WT_END, WT_ATOM, WT_AND, WT_OR, WT_PUSH_INF = range(5)
+WT_INF = 1023
+MAX_ATOMS, ROOT_ATOMS, ROOT_WORDS, ROOT_DEPTH, WT_STACK = 1024, 32, 64, 8, 8
+
+_NEGATED_ORDER = {"bvult": "bvuge", "bvule": "bvugt", "bvugt": "bvule", "bvuge": "bvult",
+                  "bvslt": "bvsge", "bvsle": "bvsgt", "bvsgt": "bvsle", "bvsge": "bvslt"}
+_TRUE, _FALSE = ("true",), ("false",)
+
+
+def _atom(node, pol: bool, kind: int = FLAT, resid=None):
+    """An atom: the Boolean ``node`` (``not node`` when ``pol`` is False)
+    holds, else it is ``kind``'s distance of ``resid`` away."""
+    return ("atom", (node.id, pol), kind, node, pol, resid)
+
+
+def _join(op: str, children):
+    """AND / OR of trees, flattened, constants folded."""
+    unit, zero = (_TRUE, _FALSE) if op == "and" else (_FALSE, _TRUE)
+    out = []
+    for c in children:
+        if c == unit:
+            continue
+        if c == zero:
+            return zero
+        out.extend(c[1] if c[0] == op else [c])
+    return unit if not out else out[0] if len(out) == 1 else (op, out)
+
+
+def _measure(t):
+    """(distinct atom keys, code words without END, stack, depth) of a tree
+    as :func:`_emit` writes it (n children: n - 1 binary folds)."""
+    if t[0] == "atom":
+        return {t[1]}, 1, 1, 1
+    if t[0] in ("true", "false"):
+        return set(), 1, 1, 1
+    keys, words, stack, depth = set(), len(t[1]) - 1, 0, 0
+    for i, c in enumerate(t[1]):
+        k, w, s, d = _measure(c)
+        keys |= k
+        words += w
+        stack = max(stack, s + (1 if i else 0))
+        depth = max(depth, d + 1)
+    return keys, words, stack, depth
+
+
+def _chunk(a, hi: int, lo: int):
+    """``extract(hi, lo, a)`` with numerals and aligned concats simplified."""
+    from .smt import node as N
+    if lo == 0 and hi == a.width - 1:
+        return a
+    if a.op == "bvnum":
+        return N.bv_num(a.params[0] >> lo, hi - lo + 1)
+    if a.op == "concat":
+        parts, top = [], a.width
+        for arg in a.args:                               # high first
+            base = top - arg.width
+            if base <= hi and lo < top:
+                parts.append(_chunk(arg, min(hi, top - 1) - base, max(lo, base) - base))
+            top = base
+        return N.concat(*parts)
+    return N.extract(hi, lo, a)
+
+
+class _TreeBuilder:
+    """The rules of DESIGN.md §3.11 on one root."""
+
+    def __init__(self):
+        self.work = 0
+
+    def flat(self, node, pol):
+        return _atom(node, pol)
+
+    def fits(self, t, level):
+        keys, words, stack, depth = _measure(t)
+        return (len(keys) <= ROOT_ATOMS and words + 1 <= ROOT_WORDS and stack <= WT_STACK
+                and level - 1 + depth <= ROOT_DEPTH)
+
+    def capped(self, t, level, node, pol):
+        """``t``, or one FLAT atom of the subterm when its expansion exceeds
+        the root's budget."""
+        return t if self.fits(t, level) else self.flat(node, pol)
+
+    def join(self, op, parts, level, node, pol):
+        """AND / OR of the lazily built ``parts`` (callables of a level); a
+        node that outgrows the budget while it is built collapses at once."""
+        out = []
+        for p in parts:
+            out.append(p(level + 1))
+            if sum(len(_measure(c)[0]) for c in out) > 4 * ROOT_ATOMS:
+                return self.flat(node, pol)
+        return self.capped(_join(op, out), level, node, pol)
+
+    def boolean(self, c, pol: bool, level: int):
+        """The tree of ``c`` (``not c`` when ``pol`` is False)."""
+        from .smt import node as N
+        c, neg = peel(c)
+        pol = pol != neg
+        op = c.op
+        if op in ("true", "false"):
+            return _TRUE if (op == "true") == pol else _FALSE
+        if level > ROOT_DEPTH:
+            return self.flat(c, pol)
+        if op in ("and", "or"):
+            kind = op if pol else ("or" if op == "and" else "and")       # De Morgan
+            return self.join(kind, [lambda lv, a=a: self.boolean(a, pol, lv) for a in c.args],
+                             level, c, pol)
+        if op == "=>":
+            a, b = c.args
+            return self.join("or" if pol else "and",
+                             [lambda lv: self.boolean(a, not pol, lv),
+                              lambda lv: self.boolean(b, pol, lv)], level, c, pol)
+        if op == "ite" and c.is_bool():
+            g, x, y = c.args
+            arm = lambda cond, v: lambda lv: self.join(
+                "and", [lambda l2: self.boolean(g, cond, l2), lambda l2: self.boolean(v, pol, l2)],
+                lv, c, pol)
+            return self.join("or", [arm(True, x), arm(False, y)], level, c, pol)
+        if op == "=" and c.args[0].is_bv():
+            return self.equality(c.args[0], c.args[1], pol, level)
+        if op in _NEGATED_ORDER:
+            if not pol:                                  # not (a < b): b <= a
+                c = N.bv_cmp(_NEGATED_ORDER[op], *c.args)
+            r = _difference(c)
+            return self.flat(c, True) if r is None else _atom(c, True, MAGNITUDE, r)
+        return self.flat(c, pol)                         # Bool xor, Bool =, distinct, a variable ..
+
+    def cases(self, a):
+        """``[(conditions, value)]`` when ``a`` is a bit-vector ite or a read
+        of a store chain: ``a`` is ``value`` where every ``(Bool node,
+        polarity)`` of ``conditions`` holds; else None.  A chain is one flat
+        case split: key k hits and the keys above it miss."""
+        from .smt import node as N
+        if a.op == "ite":
+            g, x, y = a.args
+            return [([(g, True)], x), ([(g, False)], y)]
+        if a.op != "select" or a.args[0].op not in ("store", "K"):
+            return None
+        arr, j = a.args
+        out, missed = [], []
+        while arr.op == "store":
+            below, i, v = arr.args
+            hit = N.eq(i, j)
+            out.append((missed + [(hit, True)], v))
+            missed = missed + [(hit, False)]
+            arr = below
+        out.append((missed, arr.args[0] if arr.op == "K" else N.select(arr, j)))
+        return out
+
+    def equality(self, a, b, pol: bool, level: int):
+        """``a = b`` (``a != b`` when ``pol`` is False) of bit-vectors."""
+        from .smt import node as N
+        whole = N.eq(a, b)
+        self.work += 1
+        if a.op == "bvnum" and b.op == "bvnum":
+            return _TRUE if (a.params[0] == b.params[0]) == pol else _FALSE
+        if level > ROOT_DEPTH or self.work > 4096:
+            return self.flat(whole, pol)
+        for x, y in ((a, b), (b, a)):
+            split = self.cases(x)
+            if split is None:
+                continue
+            arm = lambda conds, v: lambda lv: self.join(
+                "and", [lambda l2, g=g, p=p: self.boolean(g, p, l2) for g, p in conds]
+                + [lambda l2: self.equality(v, y, pol, l2)], lv, whole, pol)
+            return self.join("or", [arm(conds, v) for conds, v in split], level, whole, pol)
+        if not pol:
+            return self.flat(whole, False)               # an inequality has no distance
+        if a.op == "apply" and b.op == "apply" and a.params == b.params:     # congruence
+            return self.join("or", [lambda lv: self.equality(a.args[0], b.args[0], True, lv),
+                                    lambda lv: self.distance(a, b, lv)], level, whole, True)
+        return self.distance(a, b, level)
+
+    def distance(self, a, b, level: int):
+        """Positive ``a = b`` with no case split left."""
+        from .smt import node as N
+        w = a.width
+        if w > RESIDUAL_BITS:                            # extract first, then xor
+            parts = [lambda lv, lo=lo: self.equality(_chunk(a, min(lo + RESIDUAL_BITS, w) - 1, lo),
+                                                     _chunk(b, min(lo + RESIDUAL_BITS, w) - 1, lo),
+                                                     True, lv)
+                     for lo in range(0, w, RESIDUAL_BITS)]
+            return self.join("and", parts, level, N.eq(a, b), True)
+        if a.op == "bvnum" and b.op == "bvnum":
+            return _TRUE if a.params[0] == b.params[0] else _FALSE
+        if w == 1:
+            return self.flat(N.eq(a, b), True)
+        return _atom(N.eq(a, b), True, HAMMING, N.bv_op("bvxor", a, b))
+
+
+@dataclass
+class Trees:
+    """The tables of ``mg_walk_tree`` (``csrc/mg_walk_tree.h``) for a list of
+    constraints: probe order ``[root mask | atom mask | residuals]``."""
+    roots: np.ndarray          # (n_roots,) u32: kind << 16 | probe, or WT_TREE | offset in code
+    atoms: np.ndarray          # (n_atoms,) u32: kind << 16 | residual probe
+    code: np.ndarray           # (n_code,) u32: op << 16 | argument, postfix
+    atom_nodes: list           # the Bool node of every atom's truth bit (census.mask_probes)
+    probes: list               # the residual probe nodes, one per distinct term
+    shapes: list               # per root its tree: ("atom", index) | ("and" | "or", [..]) | ("false",)
+
+    @property
+    def n_atoms(self) -> int:
+        return len(self.atoms)
+
+    @property
+    def n_resid(self) -> int:
+        return len(self.probes)
+
+    def is_tree(self, k: int) -> bool:
+        return bool(int(self.roots[k]) & WT_TREE)
+
+    def kind(self, k: int) -> int:
+        """A simple root's kind."""
+        return int(self.roots[k]) >> 16
+
+    def listing(self, k: int, depth: int = 3, state=None) -> str:
+        """Root ``k``'s tree, indented, every atom with its kind and its
+        s-expression to ``depth``; ``state``: per atom (holds, distance) on
+        some assignment, shown with each atom."""
+        from .smt import node as N
+        names = ("FLAT", "HAMMING", "MAGNITUDE")
+        lines = []
+
+        def walk(t, ind):
+            if t[0] == "atom":
+                e = int(self.atoms[t[1]])
+                now = "" if state is None else (
+                    " [holds]" if state[t[1]][0] else " [%d away]" % state[t[1]][1])
+                lines.append("%satom %d %s%s %s" % ("  " * ind, t[1], names[e >> 16], now,
+                                                     N.to_sexpr(self.atom_nodes[t[1]], depth)))
+            elif t[0] in ("and", "or"):
+                lines.append("  " * ind + t[0].upper())
+                for c in t[1]:
+                    walk(c, ind + 1)
+            else:
+                lines.append("  " * ind + t[0].upper())
+        walk(self.shapes[k], 0)
+        return "\n".join(lines)
+
+
+def simple_trees(table) -> Trees:
+    """A residual table of :func:`residuals` as all-simple ``Trees``."""
+    table = np.ascontiguousarray(table, dtype=np.uint32)
+    return Trees(table, np.zeros(0, dtype=np.uint32), np.zeros(0, dtype=np.uint32), [], [],
+                 [("simple",)] * len(table))
+
+
+def distance_trees(constraints: Sequence) -> Trees:
+    """The distance trees of ``constraints``.  A root's cost
+    when it fails is the branch distance of its Boolean structure: AND = sum,
+    OR = minimum, negation pushed to the atoms, bit-vector ``ite`` and reads
+    of store chains as case splits, UF congruence as one more OR arm; atoms
+    are the three kinds of :func:`residuals`.  A root that is one atom is a
+    simple entry, exactly a :func:`residuals` table entry (but a negated order
+    is the opposite order, ``MAGNITUDE``).  Atoms are shared across roots by
+    (node, polarity), residual probes by term; past ``MAX_ATOMS`` atoms the
+    remaining roots stay simple (:func:`classify`)."""
+    from .smt import node as N
+    probes, pindex = [], {}
+    atom_nodes, atoms, aindex = [], [], {}
+    roots, code, shapes = [], [], []
+
+    def entry(kind, resid):
+        if resid is None or kind == FLAT:
+            return FLAT << 16
+        if resid.id not in pindex:
+            pindex[resid.id] = len(probes)
+            probes.append(resid)
+        return kind << 16 | pindex[resid.id]
+
+    def emit(t):
+        if t[0] == "atom":
+            _, key, kind, node, pol, resid = t
+            if key not in aindex:
+                aindex[key] = len(atoms)
+                atoms.append(entry(kind, resid))
+                atom_nodes.append(node if pol else N.bool_op("not", node))
+            code.append(WT_ATOM << 16 | aindex[key])
+            return ("atom", aindex[key])
+        if t[0] == "false":
+            code.append(WT_PUSH_INF << 16)
+            return ("false",)
+        op = WT_AND if t[0] == "and" else WT_OR
+        kids = []
+        for i, c in enumerate(t[1]):
+            kids.append(emit(c))
+            if i:
+                code.append(op << 16 | 2)
+        return (t[0], kids)
+
+    for c in constraints:
+        t = _TreeBuilder().boolean(c, True, 1)
+        if t[0] in ("and", "or") and len(aindex) + len(_measure(t)[0] - set(aindex)) > MAX_ATOMS:
+            kind, r = classify(c)
+            roots.append(entry(kind, r))
+            shapes.append(("simple",))
+        elif t[0] in ("and", "or"):
+            roots.append(WT_TREE | len(code))
+            shapes.append(emit(t))
+            code.append(WT_END << 16)
+        else:                                            # one atom, or a constant
+            roots.append(entry(t[2], t[5]) if t[0] == "atom" else FLAT << 16)
+            shapes.append(("simple",))
+    return Trees(np.array(roots, dtype=np.uint32), np.array(atoms, dtype=np.uint32),
+                 np.array(code, dtype=np.uint32), atom_nodes, probes, shapes)
+
+
+def _distances(resid: np.ndarray, n: int):
+    """(popcount, bit length) (n_resid, n) int64 of residual values."""
+    resid = np.ascontiguousarray(resid, dtype="<u4")
+    pop = np.unpackbits(resid.view(np.uint8).reshape(resid.shape[0], 8, n, 4),
+                        axis=3).sum(axis=(1, 3)).astype(np.int64)
+    length = np.zeros(pop.shape, dtype=np.int64)
+    for i in range(8):
+        limb = resid[:, i, :]
+        length = np.where(limb != 0, 32 * i + np.frexp(limb.astype(np.float64))[1], length)
+    return pop, length
+
+
+def _tree_score_bits(bits, abits, resid, trees: Trees) -> tuple:
+    """(nfail, cost) int64 (n,) of root verdicts ``bits`` (n, n_roots) bool,
+    atom verdicts ``abits`` (n, n_atoms) bool and residual values."""
+    fail = ~np.asarray(bits, dtype=bool)
+    n, n_roots = fail.shape
+    pop = length = None
+    if resid is not None and len(resid):
+        pop, length = _distances(resid, n)
+
+    def dist(e):
+        kind, p = int(e) >> 16, int(e) & 0xFFFF
+        return (np.ones(n, dtype=np.int64) if kind == FLAT else
+                np.maximum(1, pop[p]) if kind == HAMMING else 1 + length[p])
+
+    cost = np.zeros(n, dtype=np.int64)
+    for k in np.flatnonzero(fail.any(axis=0)):
+        e = int(trees.roots[k])
+        if not e & WT_TREE:
+            cost += fail[:, k] * dist(e)
+            continue
+        stack, pc = [], e & ~WT_TREE
+        while True:
+            op, arg = int(trees.code[pc]) >> 16, int(trees.code[pc]) & 0xFFFF
+            pc += 1
+            if op == WT_END:
+                break
+            if op == WT_ATOM:
+                stack.append(np.where(abits[:, arg], 0, dist(trees.atoms[arg])))
+            elif op == WT_PUSH_INF:
+                stack.append(np.full(n, WT_INF, dtype=np.int64))
+            else:
+                args = stack[len(stack) - arg:]
+                del stack[len(stack) - arg:]
+                stack.append(np.minimum(WT_INF, np.sum(args, axis=0)) if op == WT_AND
+                             else np.min(args, axis=0))
+        cost += fail[:, k] * np.clip(stack[0], 1, WT_INF)
+    return fail.sum(axis=1).astype(np.int64), cost
+
+
+def tree_score_ref(masks: np.ndarray, amasks, resid, trees: Trees, n_roots: int) -> tuple:
+    """The key ``(nfail, cost)`` of every lane from host root-mask probes
+    ``masks``, atom-mask probes ``amasks`` (n_amask, 8, n) u32 and residual
+    probes ``resid`` — the specification of ``csrc/mg_walk_tree.h``.  A
+    failing simple root costs what :func:`score_ref` says; a failing tree root
+    ``clamp(value of its program, 1, 1023)``: ``ATOM i`` is 0 where atom i's
+    bit is set, else its distance; ``AND`` the sum saturating at 1023, ``OR``
+    the minimum, ``INF`` 1023."""
+    from .census import mask_bits
+    bits = mask_bits(masks, n_roots)
+    abits = (mask_bits(amasks, trees.n_atoms) if trees.n_atoms
+             else np.zeros((bits.shape[0], 0), dtype=bool))
+    return _tree_score_bits(bits, abits, resid, trees)
+
+
+def tree_scoring(trees: Trees) -> Callable:
+    """The ``score`` argument of :func:`walk_ref` for ``trees``: its
+    ``values_fn`` then returns ``(bits, abits, resid)``."""
+    return lambda bits, abits, resid: _tree_score_bits(bits, abits, resid, trees)
+
+
+# ---------------------------------------------------------------------------
 # repair a missed group
 # ---------------------------------------------------------------------------
 
@@ -329,7 +723,7 @@ REPAIRED, STUCK = "repaired", "stuck"
 
 def repair_group(nodes: Sequence, n_cand: int = 1 << 16, form: str = "search", lanes: int = 4096,
                  max_rounds: int = 64, device: int = 0, seed: Optional[int] = None,
-                 sync_every: int = 8, scored: bool = False, walkers: int = 1) -> dict:
+                 sync_every: int = 8, scored=False, walkers: int = 1) -> dict:
     """Census, then local search, of ONE independent group (root k =
     ``nodes[k]``): the statuses of ``census.explain_group`` for a group that
     launches nothing, else ``repaired`` with ``assignment`` (a model of the
@@ -350,7 +744,17 @@ def repair_group(nodes: Sequence, n_cand: int = 1 << 16, form: str = "search", l
     duplicates, then ``best_index`` again; ``table`` is the residual table
     and, when the walk is stuck, ``failing`` the roots its winner still
     fails.  The verdict is the same fresh evaluation, of the winner's
-    leaves."""
+    leaves.
+
+    ``scored="tree"``: the same walk scored by distance trees
+    (``mg_walk_tree``): the program carries the root mask,
+    the atom mask and the residual probes of :func:`distance_trees`
+    (``trees`` in the result), same starts, same acceptance.  When that
+    program does not compile, or the compiler folds a probe away, the group
+    falls back to the table of ``scored=True`` and then to the count;
+    ``scoring`` says which ran: ``"tree"``, ``"table"`` or ``"count"``.  A
+    stuck tree walk also reports ``atom_state``: per atom whether it holds on
+    the winner and, if not, its distance."""
     from . import census as CS
     from . import model as M
     from .assign import unpack
@@ -370,14 +774,28 @@ def repair_group(nodes: Sequence, n_cand: int = 1 << 16, form: str = "search", l
         return out
     # (built before the mask: a program's schedule follows the node ids, and a
     # wide mask leaves the compiler's spill budget little room)
+    trees = distance_trees(nodes) if scored == "tree" else None
     resid, table = residuals(nodes) if scored else ([], flat_table(len(nodes)))
+    n_amask = 0
     try:
         ground = M._ground_value(CS._compile(nodes, (), form))
         if ground is not None:
             out["status"] = CS.GROUND_TRUE if ground else CS.GROUND_FALSE
             return out
         masked = CS._compile(nodes, CS.mask_probes(nodes), form)
-        if resid:
+        if trees is not None:
+            # the atom mask and the trees' residuals; else the table's, below
+            extra = CS.mask_probes(trees.atom_nodes) + trees.probes
+            try:
+                with_trees = CS._compile(nodes, CS.mask_probes(nodes) + extra, form)
+            except Unsupported:
+                with_trees = None
+            if with_trees is not None and \
+                    with_trees.n_user_probes == masked.n_user_probes + len(extra):
+                masked, resid, n_amask = with_trees, trees.probes, CS.n_mask_probes(trees.n_atoms)
+            else:
+                trees = None
+        if resid and trees is None:
             # residuals the compiler folds or cannot place: the walkers rank by
             # the count alone
             try:
@@ -393,7 +811,9 @@ def repair_group(nodes: Sequence, n_cand: int = 1 << 16, form: str = "search", l
         out.update(status=CS.UNSUPPORTED, why=str(e))
         return out
     n_mask = CS.n_mask_probes(len(nodes))
-    if masked.n_user_probes != n_mask + len(resid):
+    if scored:
+        out["scoring"] = "tree" if trees is not None else "table" if resid else "count"
+    if masked.n_user_probes != n_mask + n_amask + len(resid):
         out["status"] = CS.DEAD if masked.n_user_probes == 0 else CS.UNSUPPORTED
         out["why"] = "%d mask probes compiled to %d" % (n_mask, masked.n_user_probes)
         return out
@@ -420,9 +840,14 @@ def repair_group(nodes: Sequence, n_cand: int = 1 << 16, form: str = "search", l
         picks = (picks + [c.best_index] * walkers)[:walkers]
         starts = np.stack([leaves if i == c.best_index else eng.witness(full, M.SEARCH_SEED, i)[0]
                            for i in picks])
-        wide = eng.load(CS.census_view(masked, n_mask + len(resid)), gens, prog_seed=0)
-        res = eng.walk(wide, starts, len(nodes), table, len(resid), seed, lanes, max_rounds,
-                       sync_every)
+        wide = eng.load(CS.census_view(masked, n_mask + n_amask + len(resid)), gens, prog_seed=0)
+        if trees is not None:
+            res = eng.walk_tree(wide, starts, len(nodes), trees, seed, lanes, max_rounds,
+                                sync_every)
+            out["trees"] = trees
+        else:
+            res = eng.walk(wide, starts, len(nodes), table, len(resid), seed, lanes, max_rounds,
+                           sync_every)
         out.update(starts=picks, repair=res, table=table)
         if res.nfail[res.winner]:
             # which roots the winner still fails (one lane of the full program)
@@ -430,6 +855,15 @@ def repair_group(nodes: Sequence, n_cand: int = 1 << 16, form: str = "search", l
                                  want_probes=True)
             holds = CS.mask_bits(probes[:n_mask], len(nodes))[0]
             out["failing"] = [int(k) for k in np.flatnonzero(~holds)]
+            if trees is not None and trees.n_atoms:
+                # per atom: does it hold on the winner, and how far is it if not
+                first = n_mask + n_amask
+                abits = CS.mask_bits(probes[n_mask:first], trees.n_atoms)[0]
+                # (lane i fails atom i alone, the atoms scored as simple roots)
+                dist = _tree_score_bits(~np.eye(trees.n_atoms, dtype=bool), None, np.repeat(
+                    probes[first:first + len(resid)], trees.n_atoms, axis=2),
+                    simple_trees(trees.atoms))[1]
+                out["atom_state"] = [(bool(h), 0 if h else int(d)) for h, d in zip(abits, dist)]
             return out
         leaves = res.leaves[res.winner]
     elif c.best_nfail:

@@ -25,6 +25,12 @@ usage: tools/miss_census.py --workload {c1,c3,c3o,c4,c5} --query N
            trace of (failing constraints, cost), the outcome, what the winner
            still fails, and the device time per round of one walker and of N
            beside mg_repair's on the same group
+       ... --walk-tree [--walkers N] [--lanes L] [--rounds R]
+           after the census, the same walk scored by distance trees (DESIGN.md
+           §3.11): which scoring ran, roots by kind, simple or tree, atoms and
+           residual probes, every walker's trace, the tree of each root the
+           winner still fails (AND / OR / atoms with depth-3 s-expressions),
+           and the device time per round beside mg_walk's and mg_repair's
        tools/miss_census.py [workload] [n]
            the older census: which of a stream's first n queries the batched
            search misses, grouped by the shape of their newest constraint
@@ -274,6 +280,85 @@ def show_walk(rows, lanes):
             g.get("repair_ms_per_round")))
 
 
+def tree_rows(wl, qi, n_cand, lanes, rounds, walkers):
+    """Per independent group of the query: what ``repair.repair_group(scored=
+    "tree")`` did with ``walkers`` walkers (which scoring ran, roots by kind,
+    simple or tree, atoms and residual probes, every walker's trace, the tree
+    of each root the winner still fails), and the device time per round of
+    mg_walk_tree beside mg_walk's and mg_repair's from the same start."""
+    import mythril_amd.model as M
+    from mythril_amd import repair as RP
+    from mythril_amd.smt import node as N
+    kinds = ("flat", "hamming", "magnitude")
+    rows = []
+    q = stream_query(wl, qi)
+    where = {}
+    for i, c in enumerate(q):
+        where.setdefault(c.id, []).append(i)
+    for group in M.dependence_buckets(q):
+        pos = [where[c.id].pop(0) for c in group]        # root k = constraint pos[k]
+        kw = dict(n_cand=n_cand, form="search", lanes=lanes, max_rounds=rounds)
+        g = RP.repair_group(group, scored="tree", walkers=walkers, **kw)
+        row = {"constraints": len(group), "status": g["status"], "scoring": g.get("scoring")}
+        if "why" in g:
+            row["why"] = g["why"]
+        res = g.get("repair")
+        if res is not None:
+            T = g.get("trees") or RP.simple_trees(g["table"])
+            n_roots = len(group)
+            simple = [k for k in range(n_roots) if not T.is_tree(k)]
+            row.update(starts=g["starts"], winner=res.winner, rounds=res.rounds, walkers=walkers,
+                       simple={k: sum(T.kind(r) == i for r in simple) for i, k in enumerate(kinds)},
+                       trees=n_roots - len(simple), atoms=T.n_atoms,
+                       atom_kinds={k: int((T.atoms >> 16 == i).sum()) for i, k in enumerate(kinds)},
+                       residual_probes=len(T.probes) if g.get("trees") else None,
+                       code_words=len(T.code),
+                       nfail=[int(v) for v in res.nfail], cost=[int(v) for v in res.cost],
+                       traces=[_runs(res.trace[w, :res.rounds]) for w in range(walkers)],
+                       tree_kernel_ms=round(res.kernel_ms, 3),
+                       tree_ms_per_round=round(res.kernel_ms / max(1, res.rounds), 4))
+            row["failing"] = [{"root": k, "constraint": pos[k],
+                               "tree": T.listing(k, 3, g.get("atom_state")) if T.is_tree(k) else
+                               "simple %s: %s" % (kinds[T.kind(k)], N.to_sexpr(group[k], 3))}
+                              for k in g.get("failing", [])]
+            table = RP.repair_group(group, scored=True, walkers=walkers, **kw).get("repair")
+            flat = RP.repair_group(group, **kw).get("repair")
+            if table is not None:
+                row["walk_ms_per_round"] = round(table.kernel_ms / max(1, table.rounds), 4)
+                row["walk_rounds"] = table.rounds
+            if flat is not None:
+                row["repair_ms_per_round"] = round(flat.kernel_ms / max(1, flat.rounds), 4)
+                row["repair_rounds"] = flat.rounds
+        rows.append(row)
+    return rows
+
+
+def show_tree(rows, lanes):
+    for gi, g in enumerate(rows):
+        print(" tree walk group %d: %d constraints -> %s%s; scoring: %s" % (
+            gi, g["constraints"], g["status"], (" (%s)" % g["why"]) if "why" in g else "",
+            g["scoring"]))
+        if "traces" not in g:
+            continue
+        print("  simple roots by kind: %s; %d tree roots, %d code words; atoms: %d (%s); "
+              "%s residual probes" % (
+                  " ".join("%s %d" % kv for kv in g["simple"].items()), g["trees"],
+                  g["code_words"], g["atoms"],
+                  " ".join("%s %d" % kv for kv in g["atom_kinds"].items()), g["residual_probes"]))
+        print("  %d walkers, %d rounds of %d lanes each; winner: walker %d" % (
+            g["walkers"], g["rounds"], lanes, g["winner"]))
+        for w, tr in enumerate(g["traces"]):
+            print("   walker %2d from candidate %d: ends %d/%d; nfail/cost per round: %s" % (
+                w, g["starts"][w], g["nfail"][w], g["cost"][w], tr))
+        for f in g["failing"]:
+            print("  the winner still fails constraint #%d (root %d):" % (f["constraint"], f["root"]))
+            for line in f["tree"].split("\n"):
+                print("     " + line)
+        print("  device time per round: mg_walk_tree x%d %.4f ms; mg_walk x%d %s ms; "
+              "mg_repair %s ms" % (g["walkers"], g["tree_ms_per_round"], g["walkers"],
+                                   g.get("walk_ms_per_round"), g.get("repair_ms_per_round")))
+
+
 def show(r):
     print("== %s query %d%s: %d constraints, %d candidates per group (%.0f ms in all)" % (
         r["workload"], r["query"], " (top-level ands split, i.j = conjunct j of constraint i)"
@@ -320,6 +405,8 @@ def main():
                     help="then run the local search from each group's best candidate")
     ap.add_argument("--walk", action="store_true",
                     help="then run the scored walk from each group's census starts")
+    ap.add_argument("--walk-tree", action="store_true",
+                    help="then run the walk scored by distance trees (DESIGN.md 3.11)")
     ap.add_argument("--walkers", type=int, default=16)
     ap.add_argument("--lanes", type=int, default=4096)
     ap.add_argument("--rounds", type=int, default=64)
@@ -341,6 +428,10 @@ def main():
         for r in reports:
             r["walk"] = walk_rows(r["workload"], r["query"], a.candidates, a.lanes, a.rounds,
                                   a.walkers)
+    if a.walk_tree:
+        for r in reports:
+            r["walk_tree"] = tree_rows(r["workload"], r["query"], a.candidates, a.lanes, a.rounds,
+                                       a.walkers)
     if a.json:
         print(json.dumps(reports, indent=1))
     else:
@@ -350,6 +441,8 @@ def main():
                 show_repair(r["repair"], a.lanes)
             if a.walk:
                 show_walk(r["walk"], a.lanes)
+            if a.walk_tree:
+                show_tree(r["walk_tree"], a.lanes)
 
 
 if __name__ == "__main__":
