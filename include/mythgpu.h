@@ -310,6 +310,55 @@ int mg_walk_tree_score_host(const uint32_t* masks, const uint32_t* amasks, const
                             uint32_t n_atoms, const uint32_t* code, uint32_t n_code,
                             uint32_t n_resid, uint64_t n, uint32_t* nfail, uint32_t* cost);
 
+/* Tree-scored walk with aimed moves: mg_walk_tree, but some
+ * lanes of a round apply a move aimed by a failing equality's residual.  A
+ * HAMMING atom a = b carries the residual probe R = a xor b; where a side is
+ * made of leaves, flipping in those leaves the bits set in R makes the atom
+ * hold.  The aim table lists such sides (mythril_amd/repair.py aim_table
+ * builds it, aim_mutate_ref is the specification, csrc/mg_walk_aim.h fixes
+ * the lane layout):
+ *   entries [n_entries][3]  residual probe, first piece, number of pieces
+ *   pieces  [n_pieces][4]   leaf, leaf_bit, value_bit, len: the piece does
+ *                           leaf ^= ((R >> value_bit) & (2^len - 1)) << leaf_bit
+ * R is the entry's residual under the walker's current base: on adoption the
+ * adopted lane's residual values are kept per walker, so aimed lanes exist
+ * from round 1 on.  With L the entries whose R is not zero, in table order,
+ * and n1 = min(|L|, lanes / 8): lanes 1 .. n1 are the base with entry
+ * L[(j - 1 + r * n1) mod |L|] applied, lanes n1 + 1 .. 2 * n1 the same entry
+ * for j - n1 with mg_repair's moves of lane j written over it, every other
+ * lane is mg_repair's neighbour.  With no entry the walk is mg_walk_tree bit
+ * for bit.  Scoring, rounds, walkers, outputs and workspace are those of
+ * mg_walk_tree.  Refused without a launch: what mg_walk_tree refuses, and an
+ * aim table mg_walk_aim_ok refuses (more than 256 entries, a residual index
+ * at or above n_resid, an entry without pieces, with more than 64 or with
+ * pieces outside the piece array, a leaf at or above n_leaves, leaf_bit + len
+ * above the leaf's width, value_bit + len above 256). */
+int mg_walk_aim(mg_ctx* ctx, const mg_prog* prog,
+                const uint32_t* starts /*[walkers][n_leaves][8]*/, uint32_t walkers,
+                uint32_t n_roots, uint32_t mask_probe0, const uint32_t* roots /*[n_roots]*/,
+                uint32_t n_atoms, const uint32_t* atoms /*[n_atoms] or NULL*/,
+                const uint32_t* code /*[n_code] or NULL*/, uint32_t n_code, uint32_t n_resid,
+                const uint32_t* entries /*[n_entries][3] or NULL*/, uint32_t n_entries,
+                const uint32_t* pieces /*[n_pieces][4] or NULL*/, uint32_t n_pieces,
+                uint64_t seed, uint32_t lanes, uint32_t max_rounds, uint32_t sync_every,
+                uint32_t* out_leaves /*[walkers][n_leaves][8]*/,
+                uint32_t* out_nfail /*[walkers]*/, uint32_t* out_cost /*[walkers]*/,
+                uint32_t* out_rounds, uint32_t* trace /*[walkers][max_rounds][2] or NULL*/,
+                uint32_t* out_winner);
+/* Host-only (no GPU): mg_repair_mutate_host for mg_walk_aim's lane function.
+ * rvals: the residual values of the base ([n_resid][8]; NULL: round 0, no
+ * residual known, every lane is mg_repair's); moves ([n_lanes][5] or NULL):
+ * the four words of mg_repair_mutate_host (the number of moves is 0 where
+ * mg_repair's moves do not apply), then the aimed entry or 0xFFFFFFFF.
+ * MG_E_ARG for what mg_repair_mutate_host refuses and for an aim table
+ * mg_walk_aim refuses. */
+int mg_walk_aim_mutate_host(const mg_leafgen* leaves, uint32_t n_leaves, const uint32_t* consts,
+                            uint32_t n_consts, const uint32_t* base /*[n_leaves][8]*/,
+                            const uint32_t* rvals /*[n_resid][8] or NULL*/, uint32_t n_resid,
+                            const uint32_t* entries, uint32_t n_entries, const uint32_t* pieces,
+                            uint32_t n_pieces, uint64_t seed, uint32_t r, uint32_t lanes,
+                            uint32_t lane0, uint32_t n_lanes, uint32_t* out, uint32_t* moves);
+
 /* Corpus batches: many programs, one launch.  Device-pointer API for
  * resident benchmarking; stream is a hipStream_t (NULL = the context's own
  * stream, which the synchronous calls also use).

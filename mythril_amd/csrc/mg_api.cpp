@@ -27,6 +27,7 @@
 #include "mg_repair.h"
 #include "mg_walk.h"
 #include "mg_walk_tree.h"
+#include "mg_walk_aim.h"
 
 // the interpreter of each register layout (mg_interp_asm.hip, one
 // translation unit per layout; mg_find_layout lists them)
@@ -90,6 +91,25 @@ hipError_t mg_launch_walk_tree_pick(const uint32_t* d_masks, const uint32_t* d_a
                                     const uint32_t* d_consts, uint32_t n_leaves, uint64_t seed,
                                     uint32_t r, uint32_t max_rounds, mg_walk_state* d_state,
                                     uint32_t* d_trace, hipStream_t stream);
+// the round of mg_walk_aim (mg_walk_aim.hip): the mutate and
+// the adopt step know the aim table; the score kernel is mg_walk_tree's
+hipError_t mg_launch_walk_aim_round(const uint32_t* d_bases, const mg_leafgen* d_gen,
+                                    const uint32_t* d_consts, uint32_t n_leaves, uint64_t seed,
+                                    uint32_t r, uint32_t lanes, uint32_t walkers,
+                                    const uint32_t* d_entries, uint32_t n_entries,
+                                    const uint32_t* d_pieces, const uint32_t* d_rstate,
+                                    uint32_t n_resid, const uint32_t* d_lives, uint32_t* d_leaves,
+                                    hipStream_t stream);
+hipError_t mg_launch_walk_aim_pick(const uint32_t* d_masks, const uint32_t* d_amasks,
+                                   const uint32_t* d_resid, const uint32_t* d_roots,
+                                   const uint32_t* d_atoms, const uint32_t* d_code, uint32_t lanes,
+                                   uint32_t walkers, uint32_t n_roots, uint32_t* d_bases,
+                                   const mg_leafgen* d_gen, const uint32_t* d_consts,
+                                   uint32_t n_leaves, uint64_t seed, uint32_t r,
+                                   uint32_t max_rounds, const uint32_t* d_entries,
+                                   uint32_t n_entries, const uint32_t* d_pieces, uint32_t n_resid,
+                                   uint32_t* d_rstate, uint32_t* d_lives, mg_walk_state* d_state,
+                                   uint32_t* d_trace, hipStream_t stream);
 
 
 struct mg_ctx {
@@ -998,7 +1018,8 @@ static bool walk_table_ok(const uint32_t* table, uint32_t n_roots, uint32_t n_re
 }
 
 // what scores a walk's neighbours: the residual table of mg_walk (no atoms, no
-// code) or the tree tables of mg_walk_tree (table: its root entries)
+// code) or the tree tables of mg_walk_tree (table: its root entries); aim: the
+// round of mg_walk_aim with its aim table (tree scoring)
 struct walk_scoring {
     const uint32_t* table;
     const uint32_t* atoms;
@@ -1006,6 +1027,11 @@ struct walk_scoring {
     const uint32_t* code;
     uint32_t n_code;
     bool tree;
+    bool aim;
+    const uint32_t* entries;
+    uint32_t n_entries;
+    const uint32_t* pieces;
+    uint32_t n_pieces;
 };
 
 // The scored walk.  Rounds are queued back to back;
@@ -1019,7 +1045,8 @@ static int walk_run(mg_ctx* ctx, const mg_prog* prog, const uint32_t* starts, ui
                     uint32_t* out_winner) {
     const uint32_t* table = sc.table;
     if (!ctx || !prog || !starts || !table || !out_leaves || !out_nfail || !out_cost ||
-        !out_rounds || !out_winner || (sc.n_atoms && !sc.atoms) || (sc.n_code && !sc.code))
+        !out_rounds || !out_winner || (sc.n_atoms && !sc.atoms) || (sc.n_code && !sc.code) ||
+        (sc.n_entries && !sc.entries) || (sc.n_pieces && !sc.pieces))
         return fail(ctx, MG_E_ARG, "null argument");
     if (prog->n_leaves == 0) return fail(ctx, MG_E_ARG, "walk: the program has no leaves");
     if (walkers < 1 || walkers > MG_WALK_MAX_WALKERS)
@@ -1050,6 +1077,12 @@ static int walk_run(mg_ctx* ctx, const mg_prog* prog, const uint32_t* starts, ui
         return fail(ctx, MG_E_ARG, "walk: a table entry names an unknown kind or a residual "
                     "probe at or above %u", n_resid);
     }
+    if (sc.aim && !mg_walk_aim_ok(sc.entries, sc.n_entries, sc.pieces, sc.n_pieces,
+                                  prog->leafgen.data(), prog->n_leaves, n_resid))
+        return fail(ctx, MG_E_ARG, "walk_aim: malformed aim table (mg_walk_aim_ok: at most %u "
+                    "entries of 1..%u pieces inside the piece array, residual and leaf indices, "
+                    "bit ranges inside the leaf and the residual)", MG_AIM_MAX_ENTRIES,
+                    MG_AIM_MAX_PIECES);
     const uint64_t total = (uint64_t)walkers * lanes;
     if (total > MG_CENSUS_MAX_PROBE_BYTES / 32 / prog->n_probes)
         return fail(ctx, MG_E_ARG, "walk: %u probes x %u walkers x %u lanes exceed a %zu MiB "
@@ -1067,12 +1100,17 @@ static int walk_run(mg_ctx* ctx, const mg_prog* prog, const uint32_t* starts, ui
                  trace_b = (size_t)walkers * max_rounds * 8, root_b = words * 8,
                  leaf_b = (size_t)n_leaves * 8 * total * 4,
                  probe_b = (size_t)prog->n_probes * 8 * total * 4,
-                 atom_b = (size_t)sc.n_atoms * 4, code_b = (size_t)sc.n_code * 4;
+                 atom_b = (size_t)sc.n_atoms * 4, code_b = (size_t)sc.n_code * 4,
+                 entry_b = (size_t)sc.n_entries * 12, piece_b = (size_t)sc.n_pieces * 16,
+                 rstate_b = sc.aim ? (size_t)walkers * n_resid * 32 : 0,
+                 live_b = sc.aim ? (size_t)walkers * MG_AIM_LIVE_WORDS * 4 : 0;
     const size_t off_base = align(state_b), off_gen = off_base + align(base_b),
                  off_table = off_gen + align(gen_b), off_trace = off_table + align(table_b),
                  off_root = off_trace + align(trace_b), off_leaf = off_root + align(root_b),
                  off_probe = off_leaf + align(leaf_b), off_atom = off_probe + align(probe_b),
-                 off_code = off_atom + align(atom_b), bytes = off_code + align(code_b);
+                 off_code = off_atom + align(atom_b), off_entry = off_code + align(code_b),
+                 off_piece = off_entry + align(entry_b), off_rstate = off_piece + align(piece_b),
+                 off_live = off_rstate + align(rstate_b), bytes = off_live + align(live_b);
     void* ws;
     int rc = workspace(ctx, bytes + 256, &ws);
     if (rc) return rc;
@@ -1086,6 +1124,10 @@ static int walk_run(mg_ctx* ctx, const mg_prog* prog, const uint32_t* starts, ui
     uint32_t* d_probes = (uint32_t*)(w + off_probe);
     uint32_t* d_atoms = (uint32_t*)(w + off_atom);
     uint32_t* d_code = (uint32_t*)(w + off_code);
+    uint32_t* d_entries = (uint32_t*)(w + off_entry);
+    uint32_t* d_pieces = (uint32_t*)(w + off_piece);
+    uint32_t* d_rstate = (uint32_t*)(w + off_rstate);
+    uint32_t* d_lives = (uint32_t*)(w + off_live);
     HIPCHECK(ctx, hipMemsetAsync(d_state, 0xFF, state_b, ctx->stream));
     HIPCHECK(ctx, hipMemsetAsync(d_trace, 0, trace_b, ctx->stream));
     HIPCHECK(ctx, hipMemcpyAsync(d_bases, starts, base_b, hipMemcpyHostToDevice, ctx->stream));
@@ -1098,6 +1140,14 @@ static int walk_run(mg_ctx* ctx, const mg_prog* prog, const uint32_t* starts, ui
     if (code_b)
         HIPCHECK(ctx, hipMemcpyAsync(d_code, sc.code, code_b, hipMemcpyHostToDevice,
                                      ctx->stream));
+    if (entry_b)
+        HIPCHECK(ctx, hipMemcpyAsync(d_entries, sc.entries, entry_b, hipMemcpyHostToDevice,
+                                     ctx->stream));
+    if (piece_b)
+        HIPCHECK(ctx, hipMemcpyAsync(d_pieces, sc.pieces, piece_b, hipMemcpyHostToDevice,
+                                     ctx->stream));
+    if (rstate_b) HIPCHECK(ctx, hipMemsetAsync(d_rstate, 0, rstate_b, ctx->stream));
+    if (live_b) HIPCHECK(ctx, hipMemsetAsync(d_lives, 0, live_b, ctx->stream));
     mg_run run = empty_run();
     run.leaves = d_leaves;
     run.root_bits = (uint64_t*)(w + off_root);
@@ -1116,10 +1166,23 @@ static int walk_run(mg_ctx* ctx, const mg_prog* prog, const uint32_t* starts, ui
     while (r < max_rounds && !done) {
         const uint32_t stop = max_rounds - r < sync_every ? max_rounds : r + sync_every;
         for (; r < stop; ++r) {
-            HIPCHECK(ctx, mg_launch_walk_round(d_bases, d_gen, d_consts, n_leaves, seed, r, lanes,
-                                               walkers, d_leaves, ctx->stream));
+            if (sc.aim)
+                HIPCHECK(ctx, mg_launch_walk_aim_round(d_bases, d_gen, d_consts, n_leaves, seed, r,
+                                                       lanes, walkers, d_entries, sc.n_entries,
+                                                       d_pieces, d_rstate, n_resid, d_lives,
+                                                       d_leaves, ctx->stream));
+            else
+                HIPCHECK(ctx, mg_launch_walk_round(d_bases, d_gen, d_consts, n_leaves, seed, r,
+                                                   lanes, walkers, d_leaves, ctx->stream));
             HIPCHECK(ctx, launch(ctx, 0, prog->d_desc, 1, run, prog->n_lds, ctx->stream));
-            if (sc.tree)
+            if (sc.aim)
+                HIPCHECK(ctx, mg_launch_walk_aim_pick(d_masks, d_amasks, d_resid, d_table, d_atoms,
+                                                      d_code, lanes, walkers, n_roots, d_bases,
+                                                      d_gen, d_consts, n_leaves, seed, r,
+                                                      max_rounds, d_entries, sc.n_entries,
+                                                      d_pieces, n_resid, d_rstate, d_lives,
+                                                      d_state, d_trace, ctx->stream));
+            else if (sc.tree)
                 HIPCHECK(ctx, mg_launch_walk_tree_pick(d_masks, d_amasks, d_resid, d_table,
                                                        d_atoms, d_code, lanes, walkers, n_roots,
                                                        d_bases, d_gen, d_consts, n_leaves, seed,
@@ -1178,6 +1241,62 @@ int mg_walk_tree(mg_ctx* ctx, const mg_prog* prog, const uint32_t* starts, uint3
     return walk_run(ctx, prog, starts, walkers, n_roots, mask_probe0, sc, n_resid, seed, lanes,
                     max_rounds, sync_every, out_leaves, out_nfail, out_cost, out_rounds, trace,
                     out_winner);
+}
+
+// The tree-scored walk with aimed moves: mg_walk_tree with
+// the mutate and adopt kernels of mg_walk_aim.hip and their aim table.
+int mg_walk_aim(mg_ctx* ctx, const mg_prog* prog, const uint32_t* starts, uint32_t walkers,
+                uint32_t n_roots, uint32_t mask_probe0, const uint32_t* roots, uint32_t n_atoms,
+                const uint32_t* atoms, const uint32_t* code, uint32_t n_code, uint32_t n_resid,
+                const uint32_t* entries, uint32_t n_entries, const uint32_t* pieces,
+                uint32_t n_pieces, uint64_t seed, uint32_t lanes, uint32_t max_rounds,
+                uint32_t sync_every, uint32_t* out_leaves, uint32_t* out_nfail,
+                uint32_t* out_cost, uint32_t* out_rounds, uint32_t* trace, uint32_t* out_winner) {
+    const walk_scoring sc = {roots, atoms, n_atoms, code, n_code, true, true,
+                             entries, n_entries, pieces, n_pieces};
+    return walk_run(ctx, prog, starts, walkers, n_roots, mask_probe0, sc, n_resid, seed, lanes,
+                    max_rounds, sync_every, out_leaves, out_nfail, out_cost, out_rounds, trace,
+                    out_winner);
+}
+
+// Host only: lanes lane0 .. lane0 + n_lanes - 1 of round r of the lane
+// function of mg_walk_aim.h, as the mutate kernel writes them.
+int mg_walk_aim_mutate_host(const mg_leafgen* leaves, uint32_t n_leaves, const uint32_t* consts,
+                            uint32_t n_consts, const uint32_t* base, const uint32_t* rvals,
+                            uint32_t n_resid, const uint32_t* entries, uint32_t n_entries,
+                            const uint32_t* pieces, uint32_t n_pieces, uint64_t seed, uint32_t r,
+                            uint32_t lanes, uint32_t lane0, uint32_t n_lanes, uint32_t* out,
+                            uint32_t* moves) {
+    if (!leaves || !base || !out || (n_consts && !consts) || n_leaves == 0) return MG_E_ARG;
+    if (lanes < 1 || lanes > MG_REPAIR_MAX_LANES || r >= MG_REPAIR_MAX_ROUNDS) return MG_E_ARG;
+    if (lane0 > lanes || n_lanes > lanes - lane0) return MG_E_ARG;
+    for (uint32_t i = 0; i < n_leaves; ++i) {
+        if (leaves[i].width < 1 || leaves[i].width > MG_MAX_WIDTH) return MG_E_ARG;
+        if ((uint64_t)leaves[i].pool_off + leaves[i].pool_n > n_consts) return MG_E_ARG;
+        uint32_t v[8];
+        memcpy(v, base + (size_t)i * 8, 32);
+        mg_repair_mask(v, leaves[i].width);
+        if (memcmp(v, base + (size_t)i * 8, 32)) return MG_E_ARG;     // a base beyond its width
+    }
+    if (!mg_walk_aim_ok(entries, n_entries, pieces, n_pieces, leaves, n_leaves, n_resid))
+        return MG_E_ARG;
+    uint32_t live[MG_AIM_LIVE_WORDS];
+    mg_walk_aim_live(entries, n_entries, rvals, live);
+    for (uint32_t a = 0; a < n_lanes; ++a) {
+        for (size_t i = 0; i < (size_t)n_leaves * 8; ++i) out[i * n_lanes + a] = base[i];
+        mg_repair_moves mv;
+        const uint32_t e = mg_walk_aim_lane(base, leaves, consts, n_leaves, seed, r, lane0 + a,
+                                            lanes, entries, pieces, rvals, live, out + a, n_lanes,
+                                            &mv);
+        if (moves) {
+            moves[5 * (size_t)a] = mv.n;
+            moves[5 * (size_t)a + 1] = mv.kind[0] | mv.kind[1] << 8;
+            moves[5 * (size_t)a + 2] = mv.leaf[0];
+            moves[5 * (size_t)a + 3] = mv.leaf[1];
+            moves[5 * (size_t)a + 4] = e;
+        }
+    }
+    return MG_OK;
 }
 
 // Host only: the tree scoring (mg_walk_tree.h) on n lanes of host rows, as

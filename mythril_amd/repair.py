@@ -285,8 +285,8 @@ class WalkResult:
 
 
 def walk_ref(values_fn: Callable, leafgen, consts, starts, table, seed: int, lanes: int = 4096,
-             max_rounds: int = 64, sync_every: int = 8, score: Optional[Callable] = None
-             ) -> WalkResult:
+             max_rounds: int = 64, sync_every: int = 8, score: Optional[Callable] = None,
+             aims=None) -> WalkResult:
     """The whole loop as ``mg_walk`` runs it.  ``values_fn`` maps an SoA leaf
     array ``(n_leaves, 8, n)`` to ``(bits (n, n_roots) bool, resid (n_resid,
     8, n) u32)``: the verdicts and the residual values.  Walker w moves under
@@ -295,7 +295,12 @@ def walk_ref(values_fn: Callable, leafgen, consts, starts, table, seed: int, lan
 
     ``score``: another scoring of the same loop (``mg_walk_tree``): called
     with what ``values_fn`` returns, it gives ``(nfail, cost)`` per lane, and
-    ``table`` is not read (:func:`tree_scoring`)."""
+    ``table`` is not read (:func:`tree_scoring`).
+
+    ``aims``: the aim table of ``mg_walk_aim`` (:func:`aim_table`): the
+    neighbours are those of :func:`aim_mutate_ref` under the residual values
+    of the walker's base — the last element of what ``values_fn`` returns, in
+    the column of the lane it adopted (none before round 0's adoption)."""
     bases = np.ascontiguousarray(starts, dtype=np.uint32).copy()
     walkers = bases.shape[0]
     if not 1 <= walkers <= MAX_WALKERS or bases.shape[2:] != (8,):
@@ -303,23 +308,31 @@ def walk_ref(values_fn: Callable, leafgen, consts, starts, table, seed: int, lan
     sync_every = sync_every or 8
     trace = np.zeros((walkers, max_rounds, 2), dtype=np.uint32)
     keys: List[Optional[tuple]] = [None] * walkers
+    rvals: List[Optional[np.ndarray]] = [None] * walkers
     r = 0
     while r < max_rounds and not any(k is not None and k[0] == 0 for k in keys):
         stop = max_rounds if max_rounds - r < sync_every else r + sync_every
         while r < stop:
-            nb = np.concatenate([mutate_ref(leafgen, consts, bases[w], seed ^ (w * CW & M64), r,
-                                            lanes) for w in range(walkers)], axis=2)
-            if score is None:
-                bits, resid = values_fn(nb)
-                nfail, cost = _score_bits(bits, resid, table)
+            if aims is None:
+                nb = np.concatenate([mutate_ref(leafgen, consts, bases[w], seed ^ (w * CW & M64),
+                                                r, lanes) for w in range(walkers)], axis=2)
             else:
-                nfail, cost = score(*values_fn(nb))
+                nb = np.concatenate([aim_mutate_ref(leafgen, consts, bases[w], rvals[w], aims,
+                                                    seed ^ (w * CW & M64), r, lanes)
+                                     for w in range(walkers)], axis=2)
+            values = values_fn(nb)
+            if score is None:
+                nfail, cost = _score_bits(values[0], values[1], table)
+            else:
+                nfail, cost = score(*values)
             for w in range(walkers):
                 nf, co = nfail[w * lanes:(w + 1) * lanes], cost[w * lanes:(w + 1) * lanes]
                 lane = int(np.lexsort((co, nf))[0])       # stable: the lowest lane of the minimum
                 key = (int(nf[lane]), int(co[lane]))
                 if keys[w] is None or key < keys[w]:
                     bases[w], keys[w] = nb[:, :, w * lanes + lane], key
+                    if aims is not None:
+                        rvals[w] = np.ascontiguousarray(values[-1][:, :, w * lanes + lane])
                 trace[w, r] = key
             r += 1
     nfail = np.array([k[0] for k in keys], dtype=np.int64)
@@ -715,6 +728,223 @@ def tree_scoring(trees: Trees) -> Callable:
 
 
 # ---------------------------------------------------------------------------
+# aimed moves: a failing equality's residual says which bits
+# of which leaves to flip
+# ---------------------------------------------------------------------------
+
+# the constants of csrc/mg_walk_aim.h
+AIM_MAX_ENTRIES, AIM_MAX_PIECES, AIM_NONE = 256, 64, 0xFFFFFFFF
+
+
+@dataclass
+class Aims:
+    """The aim table of ``mg_walk_aim`` (``csrc/mg_walk_aim.h``)."""
+    entries: np.ndarray        # (n_entries, 3) u32: residual probe, first piece, pieces
+    pieces: np.ndarray         # (n_pieces, 4) u32: leaf, leaf_bit, value_bit, len
+    sides: list                # per entry: which side of its probe's xor it moves (0: a, 1: b)
+
+    def __len__(self) -> int:
+        return len(self.entries)
+
+    def of(self, e: int) -> list:
+        """Entry ``e``'s pieces as (leaf, leaf_bit, value_bit, len) tuples."""
+        _, off, cnt = (int(x) for x in self.entries[e])
+        return [tuple(int(x) for x in row) for row in self.pieces[off:off + cnt]]
+
+
+def no_aims() -> Aims:
+    return Aims(np.zeros((0, 3), dtype=np.uint32), np.zeros((0, 4), dtype=np.uint32), [])
+
+
+def make_aims(entries) -> Aims:
+    """``Aims`` of ``[(residual probe, [(leaf, leaf_bit, value_bit, len), ..]), ..]``."""
+    rows, pieces = [], []
+    for p, ps in entries:
+        rows.append((p, len(pieces), len(ps)))
+        pieces.extend(ps)
+    return Aims(np.array(rows, dtype=np.uint32).reshape(-1, 3),
+                np.array(pieces, dtype=np.uint32).reshape(-1, 4), [0] * len(rows))
+
+
+def _fold_key(i, subst) -> Optional[int]:
+    """The value of a read's index when it is a numeral, a node the presets
+    replace by one, or a sum of such; else None."""
+    if i.op == "bvnum":
+        return i.params[0]
+    if i.id in subst:
+        return subst[i.id] % (1 << i.width)
+    if i.op == "bvadd":
+        parts = [_fold_key(a, subst) for a in i.args]
+        return None if None in parts else sum(parts) % (1 << i.width)
+    return None
+
+
+def aim_pieces(t, program) -> Optional[list]:
+    """The pieces ``[(leaf, leaf_bit, value_bit, len)]`` of the bit-vector
+    term ``t`` as a destination, ``value_bit`` relative to
+    ``t``'s bit 0; None when ``t`` does not resolve.  A numeral resolves to no
+    piece."""
+    leaves = {(l.kind, l.source, l.entry, l.chunk): i for i, l in enumerate(program.leaves)}
+    subst = getattr(program.presets, "subst", None) or {}
+
+    def cells(kind, source, entry, width):
+        out = []
+        for k in range((width + RESIDUAL_BITS - 1) // RESIDUAL_BITS):
+            li = leaves.get((kind, source, entry, k))
+            if li is None or program.leaves[li].width != min(RESIDUAL_BITS,
+                                                             width - RESIDUAL_BITS * k):
+                return None
+            out.append((li, 0, RESIDUAL_BITS * k, program.leaves[li].width))
+        return out
+
+    def go(t):
+        if t.op == "bvnum":
+            return []
+        if t.op == "var" and t.is_bv():
+            return cells("var", t.params[0], 0, t.width)
+        if t.op == "concat":
+            out, off = [], t.width
+            for a in t.args:                             # high first
+                off -= a.width
+                ps = go(a)
+                if ps is None:
+                    return None
+                out += [(l, lb, vb + off, n) for l, lb, vb, n in ps]
+            return out
+        if t.op == "extract":
+            hi, lo = t.params
+            ps = go(t.args[0])
+            if ps is None:
+                return None
+            out = []
+            for l, lb, vb, n in ps:
+                s, e = max(vb, lo), min(vb + n, hi + 1)
+                if s < e:
+                    out.append((l, lb + s - vb, s - lo, e - s))
+            return out
+        if t.op == "zero_extend":
+            return go(t.args[0])
+        if t.op == "ite" and t.is_bv():                  # the guard is ignored: a proposal
+            _, x, y = t.args
+            if x.op == "bvnum" or y.op == "bvnum":
+                return go(y if x.op == "bvnum" else x)
+            return None
+        if t.op == "select" and t.args[0].op == "array":
+            name = t.args[0].params[0]
+            key = _fold_key(t.args[1], subst)
+            ckeys = list(program.table_ckeys.get(name, []))
+            if key is None or key not in ckeys:
+                return None
+            return cells("cval", name, ckeys.index(key), t.width)
+        return None
+    return go(t)
+
+
+def aim_refusal(t, program) -> Optional[str]:
+    """Why :func:`aim_pieces` does not resolve ``t`` (the first subterm no
+    rule takes, with the rule that refused it), None when it resolves."""
+    if aim_pieces(t, program) is not None:
+        return None
+    if t.op in ("concat", "extract", "zero_extend"):
+        return next(r for r in (aim_refusal(a, program) for a in t.args) if r)
+    if t.op == "ite" and t.is_bv():
+        _, x, y = t.args
+        if x.op == "bvnum" or y.op == "bvnum":
+            return aim_refusal(y if x.op == "bvnum" else x, program)
+        return "ite: neither arm is a numeral"
+    if t.op == "var":
+        return "variable %s is not a leaf of the program" % t.params[0]
+    if t.op == "select" and t.args[0].op == "array":
+        name = t.args[0].params[0]
+        key = _fold_key(t.args[1], getattr(program.presets, "subst", None) or {})
+        if key is None:
+            return "select(%s, .): the key (%s) is not a numeral under the presets" % (
+                name, t.args[1].op)
+        return "select(%s, %d): the program does not read that constant key" % (name, key)
+    if t.op == "select":
+        return "select of a %s" % t.args[0].op
+    return "%s is not a destination" % t.op
+
+
+def aim_table(trees: Trees, program) -> Aims:
+    """The aim table of ``trees`` on the compiled ``program`` (DESIGN.md
+    §3.12): for every residual probe ``bvxor(a, b)`` that a HAMMING atom or a
+    simple HAMMING root of ``trees`` reads, in probe order, one entry per side
+    (``a``, then ``b``) that :func:`aim_pieces` resolves to 1 .. 64 pieces
+    none of whose leaves the program derives; at most 256 entries, the first
+    ones."""
+    used = set()
+    for e in list(trees.atoms) + [r for r in trees.roots if not int(r) & WT_TREE]:
+        if int(e) >> 16 == HAMMING:
+            used.add(int(e) & 0xFFFF)
+    rows, pieces, sides = [], [], []
+    for p in sorted(used):
+        node = trees.probes[p]
+        if node.op != "bvxor" or len(node.args) != 2:
+            continue
+        for side, t in enumerate(node.args):
+            ps = aim_pieces(t, program)
+            if not ps or len(ps) > AIM_MAX_PIECES or any(l in program.derived for l, *_ in ps):
+                continue
+            if len(rows) < AIM_MAX_ENTRIES:
+                rows.append((p, len(pieces), len(ps)))
+                pieces.extend(ps)
+                sides.append(side)
+    return Aims(np.array(rows, dtype=np.uint32).reshape(-1, 3),
+                np.array(pieces, dtype=np.uint32).reshape(-1, 4), sides)
+
+
+def aim_picks_ref(rvals, aims: Aims, r: int, lanes: int) -> np.ndarray:
+    """(lanes,) int64: the entry lane j of round ``r`` applies under the base's
+    residual values ``rvals`` ((n_resid, 8) u32, None in round 0), or
+    ``AIM_NONE``.  L = the entries whose residual is not zero, in table order,
+    n1 = min(|L|, lanes // 8): lanes 1 .. n1 and n1 + 1 .. 2 n1 take
+    L[(j' - 1 + r n1) mod |L|], j' = j or j - n1."""
+    out = np.full(lanes, AIM_NONE, dtype=np.int64)
+    if rvals is None or not len(aims):
+        return out
+    rv = np.asarray(rvals, dtype=np.uint32).reshape(-1, 8)
+    live = [e for e in range(len(aims)) if rv[int(aims.entries[e, 0])].any()]
+    n1 = min(len(live), lanes // 8)
+    for j in range(1, 2 * n1 + 1):
+        out[j] = live[((j if j <= n1 else j - n1) - 1 + r * n1) % len(live)]
+    return out
+
+
+def aim_mutate_ref(leafgen, consts, base, rvals, aims: Aims, seed: int, r: int,
+                   lanes: int) -> np.ndarray:
+    """``[n_leaves][8][lanes]`` u32: the neighbours of ``base`` that round
+    ``r`` of ``mg_walk_aim`` evaluates — the specification of
+    ``csrc/mg_walk_aim.h``.  Lane 0 is the base; a lane with an entry
+    (:func:`aim_picks_ref`) has every piece of it applied to the base, ``leaf
+    ^= ((R >> value_bit) & mask(len)) << leaf_bit`` with R the entry's
+    residual value; the first n1 of them are that and nothing else, the next
+    n1 then take the moves of :func:`moves_ref` for their lane, computed from
+    the base and written over the aimed result; every other lane is
+    :func:`mutate_ref`'s."""
+    base = np.ascontiguousarray(base, dtype=np.uint32).reshape(-1, 8)
+    picks = aim_picks_ref(rvals, aims, r, lanes)
+    n1 = int((picks != AIM_NONE).sum()) // 2
+    out = np.repeat(base[:, :, None], lanes, axis=2)
+    moves = moves_ref(leafgen, consts, base, seed, r, lanes)
+    bvals = _ints(base)
+    rv = _ints(np.asarray(rvals, dtype=np.uint32).reshape(-1, 8)) if n1 else []
+    for lane in range(lanes):
+        cur = {}
+        if picks[lane] != AIM_NONE:
+            e = int(picks[lane])
+            R = rv[int(aims.entries[e, 0])]
+            for leaf, leaf_bit, value_bit, n in aims.of(e):
+                cur[leaf] = cur.get(leaf, bvals[leaf]) ^ ((R >> value_bit & ((1 << n) - 1)) << leaf_bit)
+        if lane > n1:
+            for leaf, _, v in moves[lane]:
+                cur[leaf] = v
+        for leaf, v in cur.items():
+            out[leaf, :, lane] = np.frombuffer(v.to_bytes(32, "little"), dtype="<u4")
+    return out
+
+
+# ---------------------------------------------------------------------------
 # repair a missed group
 # ---------------------------------------------------------------------------
 
@@ -754,7 +984,14 @@ def repair_group(nodes: Sequence, n_cand: int = 1 << 16, form: str = "search", l
     falls back to the table of ``scored=True`` and then to the count;
     ``scoring`` says which ran: ``"tree"``, ``"table"`` or ``"count"``.  A
     stuck tree walk also reports ``atom_state``: per atom whether it holds on
-    the winner and, if not, its distance."""
+    the winner and, if not, its distance.
+
+    ``scored="aim"``: the tree-scored walk with aimed moves (``mg_walk_aim``,
+    DESIGN.md §3.12): compiled as ``"tree"``, then the aim table of
+    :func:`aim_table` on the compiled program (``aims`` in the result); with
+    no entry, and where ``"tree"`` falls back, it runs as ``"tree"`` does;
+    ``scoring`` is ``"aim"`` when aimed moves ran, and ``program`` is the
+    compiled program whose leaves the table names."""
     from . import census as CS
     from . import model as M
     from .assign import unpack
@@ -774,7 +1011,7 @@ def repair_group(nodes: Sequence, n_cand: int = 1 << 16, form: str = "search", l
         return out
     # (built before the mask: a program's schedule follows the node ids, and a
     # wide mask leaves the compiler's spill budget little room)
-    trees = distance_trees(nodes) if scored == "tree" else None
+    trees = distance_trees(nodes) if scored in ("tree", "aim") else None
     resid, table = residuals(nodes) if scored else ([], flat_table(len(nodes)))
     n_amask = 0
     try:
@@ -811,8 +1048,13 @@ def repair_group(nodes: Sequence, n_cand: int = 1 << 16, form: str = "search", l
         out.update(status=CS.UNSUPPORTED, why=str(e))
         return out
     n_mask = CS.n_mask_probes(len(nodes))
+    aims = aim_table(trees, masked) if scored == "aim" and trees is not None else None
     if scored:
-        out["scoring"] = "tree" if trees is not None else "table" if resid else "count"
+        out["scoring"] = ("aim" if aims is not None and len(aims) else
+                          "tree" if trees is not None else "table" if resid else "count")
+    if scored == "aim":
+        out["aims"] = aims if aims is not None else no_aims()
+        out["program"] = masked                          # what the table's leaves index
     if masked.n_user_probes != n_mask + n_amask + len(resid):
         out["status"] = CS.DEAD if masked.n_user_probes == 0 else CS.UNSUPPORTED
         out["why"] = "%d mask probes compiled to %d" % (n_mask, masked.n_user_probes)
@@ -841,7 +1083,11 @@ def repair_group(nodes: Sequence, n_cand: int = 1 << 16, form: str = "search", l
         starts = np.stack([leaves if i == c.best_index else eng.witness(full, M.SEARCH_SEED, i)[0]
                            for i in picks])
         wide = eng.load(CS.census_view(masked, n_mask + n_amask + len(resid)), gens, prog_seed=0)
-        if trees is not None:
+        if trees is not None and aims is not None and len(aims):
+            res = eng.walk_aim(wide, starts, len(nodes), trees, aims, seed, lanes, max_rounds,
+                               sync_every)
+            out["trees"] = trees
+        elif trees is not None:
             res = eng.walk_tree(wide, starts, len(nodes), trees, seed, lanes, max_rounds,
                                 sync_every)
             out["trees"] = trees

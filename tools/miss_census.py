@@ -31,6 +31,14 @@ usage: tools/miss_census.py --workload {c1,c3,c3o,c4,c5} --query N
            residual probes, every walker's trace, the tree of each root the
            winner still fails (AND / OR / atoms with depth-3 s-expressions),
            and the device time per round beside mg_walk's and mg_repair's
+       ... --walk-aim [--walkers N] [--lanes L] [--rounds R]
+           after the census, the tree-scored walk with aimed moves (DESIGN.md
+           §3.12): the aim table (per entry its residual probe, side, pieces
+           and destination), per rule that refused a side of a HAMMING
+           residual the number of sides and an example (--json: every side),
+           every walker's trace, the tree of each root
+           the winner still fails, and the device time per round beside
+           mg_walk_tree's from the same starts
        tools/miss_census.py [workload] [n]
            the older census: which of a stream's first n queries the batched
            search misses, grouped by the shape of their newest constraint
@@ -359,6 +367,104 @@ def show_tree(rows, lanes):
                                    g.get("walk_ms_per_round"), g.get("repair_ms_per_round")))
 
 
+def aim_rows(wl, qi, n_cand, lanes, rounds, walkers):
+    """Per independent group of the query: what ``repair.repair_group(scored=
+    "aim")`` did with ``walkers`` walkers (the aim table, what refused the
+    residuals without an entry, every walker's trace, the tree of each root the
+    winner still fails), and the device time per round of mg_walk_aim beside
+    mg_walk_tree's from the same starts."""
+    import mythril_amd.model as M
+    from mythril_amd import repair as RP
+    from mythril_amd.smt import node as N
+    kinds = ("flat", "hamming", "magnitude")
+    rows = []
+    q = stream_query(wl, qi)
+    where = {}
+    for i, c in enumerate(q):
+        where.setdefault(c.id, []).append(i)
+    for group in M.dependence_buckets(q):
+        pos = [where[c.id].pop(0) for c in group]        # root k = constraint pos[k]
+        kw = dict(n_cand=n_cand, form="search", lanes=lanes, max_rounds=rounds)
+        g = RP.repair_group(group, scored="aim", walkers=walkers, **kw)
+        row = {"constraints": len(group), "status": g["status"], "scoring": g.get("scoring")}
+        if "why" in g:
+            row["why"] = g["why"]
+        res, T, A = g.get("repair"), g.get("trees"), g.get("aims")
+        if res is not None and T is not None:
+            row.update(starts=g["starts"], winner=res.winner, rounds=res.rounds, walkers=walkers,
+                       atoms=T.n_atoms, residual_probes=len(T.probes),
+                       nfail=[int(v) for v in res.nfail], cost=[int(v) for v in res.cost],
+                       traces=[_runs(res.trace[w, :res.rounds]) for w in range(walkers)],
+                       aim_kernel_ms=round(res.kernel_ms, 3),
+                       aim_ms_per_round=round(res.kernel_ms / max(1, res.rounds), 4))
+            row["entries"] = [{"probe": int(A.entries[e, 0]), "side": "ab"[A.sides[e]],
+                               "pieces": int(A.entries[e, 2]),
+                               "destination": N.to_sexpr(
+                                   T.probes[int(A.entries[e, 0])].args[A.sides[e]], 3)}
+                              for e in range(len(A))]
+            prog = g["program"]
+            used = sorted({int(e) & 0xFFFF for e in list(T.atoms) +
+                           [r for r in T.roots if not int(r) & RP.WT_TREE]
+                           if int(e) >> 16 == RP.HAMMING})
+            have = {(int(A.entries[e, 0]), A.sides[e]) for e in range(len(A))}
+            row["refused"] = []
+            for p in used:
+                for side, t in enumerate(T.probes[p].args):
+                    if (p, side) in have:
+                        continue
+                    ps = RP.aim_pieces(t, prog)
+                    why = RP.aim_refusal(t, prog) or (
+                        "no piece" if not ps else "%d pieces" % len(ps) if len(ps) > 64 else
+                        "a leaf the construction derives")
+                    row["refused"].append({"probe": p, "side": "ab"[side], "why": why,
+                                           "term": N.to_sexpr(t, 3)})
+            row["failing"] = [{"root": k, "constraint": pos[k],
+                               "tree": T.listing(k, 3, g.get("atom_state")) if T.is_tree(k) else
+                               "simple %s: %s" % (kinds[T.kind(k)], N.to_sexpr(group[k], 3))}
+                              for k in g.get("failing", [])]
+            tree = RP.repair_group(group, scored="tree", walkers=walkers, **kw).get("repair")
+            if tree is not None:
+                row["tree_ms_per_round"] = round(tree.kernel_ms / max(1, tree.rounds), 4)
+                row["tree_rounds"] = tree.rounds
+                row["tree_end"] = [int(tree.nfail[tree.winner]), int(tree.cost[tree.winner])]
+        rows.append(row)
+    return rows
+
+
+def show_aim(rows, lanes):
+    for gi, g in enumerate(rows):
+        print(" aimed walk group %d: %d constraints -> %s%s; scoring: %s" % (
+            gi, g["constraints"], g["status"], (" (%s)" % g["why"]) if "why" in g else "",
+            g["scoring"]))
+        if "traces" not in g:
+            continue
+        print("  %d atoms, %d residual probes; aim table: %d entries" % (
+            g["atoms"], g["residual_probes"], len(g["entries"])))
+        for e in g["entries"]:
+            print("   entry: residual %d side %s, %d pieces: %.160s" % (
+                e["probe"], e["side"], e["pieces"], e["destination"]))
+        # (--json lists every refused side; here one line per rule)
+        rules = collections.OrderedDict()
+        for e in g["refused"]:
+            rules.setdefault(e["why"], []).append(e)
+        for why, es in rules.items():
+            print("   no entry: %d sides: %s, e.g. residual %d side %s: %.120s" % (
+                len(es), why, es[0]["probe"], es[0]["side"], es[0]["term"]))
+        print("  %d walkers, %d rounds of %d lanes each; winner: walker %d" % (
+            g["walkers"], g["rounds"], lanes, g["winner"]))
+        for w, tr in enumerate(g["traces"]):
+            print("   walker %2d from candidate %d: ends %d/%d; nfail/cost per round: %s" % (
+                w, g["starts"][w], g["nfail"][w], g["cost"][w], tr))
+        for f in g["failing"]:
+            print("  the winner still fails constraint #%d (root %d):" % (f["constraint"], f["root"]))
+            for line in f["tree"].split("\n"):
+                print("     " + line)
+        print("  device time per round: mg_walk_aim x%d %.4f ms; mg_walk_tree x%d %s ms "
+              "(%s rounds, ends %s)" % (g["walkers"], g["aim_ms_per_round"], g["walkers"],
+                                        g.get("tree_ms_per_round"), g.get("tree_rounds"),
+                                        g.get("tree_end")))
+
+
 def show(r):
     print("== %s query %d%s: %d constraints, %d candidates per group (%.0f ms in all)" % (
         r["workload"], r["query"], " (top-level ands split, i.j = conjunct j of constraint i)"
@@ -407,6 +513,8 @@ def main():
                     help="then run the scored walk from each group's census starts")
     ap.add_argument("--walk-tree", action="store_true",
                     help="then run the walk scored by distance trees (DESIGN.md 3.11)")
+    ap.add_argument("--walk-aim", action="store_true",
+                    help="then run the tree-scored walk with aimed moves (DESIGN.md 3.12)")
     ap.add_argument("--walkers", type=int, default=16)
     ap.add_argument("--lanes", type=int, default=4096)
     ap.add_argument("--rounds", type=int, default=64)
@@ -432,6 +540,10 @@ def main():
         for r in reports:
             r["walk_tree"] = tree_rows(r["workload"], r["query"], a.candidates, a.lanes, a.rounds,
                                        a.walkers)
+    if a.walk_aim:
+        for r in reports:
+            r["walk_aim"] = aim_rows(r["workload"], r["query"], a.candidates, a.lanes, a.rounds,
+                                     a.walkers)
     if a.json:
         print(json.dumps(reports, indent=1))
     else:
@@ -443,6 +555,8 @@ def main():
                 show_walk(r["walk"], a.lanes)
             if a.walk_tree:
                 show_tree(r["walk_tree"], a.lanes)
+            if a.walk_aim:
+                show_aim(r["walk_aim"], a.lanes)
 
 
 if __name__ == "__main__":
