@@ -359,6 +359,56 @@ int mg_walk_aim_mutate_host(const mg_leafgen* leaves, uint32_t n_leaves, const u
                             uint32_t n_pieces, uint64_t seed, uint32_t r, uint32_t lanes,
                             uint32_t lane0, uint32_t n_lanes, uint32_t* out, uint32_t* moves);
 
+/* Tree-scored walk with moves aimed by equalities and orders (DESIGN.md
+ * §3.13): mg_walk_aim with a wider aim table.  A MAGNITUDE atom lo < hi or
+ * lo <= hi carries the residual probe D = lo - hi; where a side is made of
+ * leaves, lo := lo - D - s or hi := hi + D + s (s = 1 for a strict order)
+ * makes the atom hold (mythril_amd/repair.py bound_table builds the table,
+ * bound_mutate_ref is the specification, csrc/mg_walk_bound.h the code):
+ *   entries [n_entries][5]  residual probe, first piece, number of pieces,
+ *                           mode (0 XOR, 1 LOW, 2 LOW_STRICT, 3 HIGH,
+ *                           4 HIGH_STRICT), truth (1 << 31 | i: bit i of the
+ *                           atom mask, else bit k of the root mask; 0 for XOR)
+ *   pieces  [n_pieces][4]   as for mg_walk_aim
+ *   fixed   [n_entries][8]  the numeral bits of an order entry's side (0 for XOR)
+ * An XOR entry acts and is live as in mg_walk_aim.  An order entry is live
+ * iff its truth bit is clear on the walker's base (the adopted lane's mask
+ * rows are kept per walker); it gathers V = fixed | the pieces' bits of the
+ * base, takes T = V - D - s (LOW) or V + D + s (HIGH) mod 2^256 and writes
+ * T's bits back through the pieces.  Lane layout, scoring, rounds, walkers,
+ * outputs and workspace are those of mg_walk_aim; with XOR entries only the
+ * walk is mg_walk_aim bit for bit.  Refused without a launch: what
+ * mg_walk_aim refuses, a mode above 4, a truth index at or above n_atoms
+ * (n_roots), an XOR entry with a truth or fixed word set, and a null table
+ * with a non-zero count. */
+int mg_walk_bound(mg_ctx* ctx, const mg_prog* prog,
+                  const uint32_t* starts /*[walkers][n_leaves][8]*/, uint32_t walkers,
+                  uint32_t n_roots, uint32_t mask_probe0, const uint32_t* roots /*[n_roots]*/,
+                  uint32_t n_atoms, const uint32_t* atoms /*[n_atoms] or NULL*/,
+                  const uint32_t* code /*[n_code] or NULL*/, uint32_t n_code, uint32_t n_resid,
+                  const uint32_t* entries /*[n_entries][5] or NULL*/, uint32_t n_entries,
+                  const uint32_t* pieces /*[n_pieces][4] or NULL*/, uint32_t n_pieces,
+                  const uint32_t* fixed /*[n_entries][8] or NULL*/,
+                  uint64_t seed, uint32_t lanes, uint32_t max_rounds, uint32_t sync_every,
+                  uint32_t* out_leaves /*[walkers][n_leaves][8]*/,
+                  uint32_t* out_nfail /*[walkers]*/, uint32_t* out_cost /*[walkers]*/,
+                  uint32_t* out_rounds, uint32_t* trace /*[walkers][max_rounds][2] or NULL*/,
+                  uint32_t* out_winner);
+/* Host-only (no GPU): mg_walk_aim_mutate_host for mg_walk_bound's lane
+ * function.  rvals: the base's residual values, mvals: its mask state, the
+ * root-mask words ([ceil(n_roots / 256) * 8]) then the atom-mask words
+ * ([ceil(n_atoms / 256) * 8]); either NULL: round 0, every lane is
+ * mg_repair's.  MG_E_ARG for what mg_walk_aim_mutate_host refuses and for a
+ * table mg_walk_bound refuses. */
+int mg_walk_bound_mutate_host(const mg_leafgen* leaves, uint32_t n_leaves, const uint32_t* consts,
+                              uint32_t n_consts, const uint32_t* base /*[n_leaves][8]*/,
+                              const uint32_t* rvals /*[n_resid][8] or NULL*/, uint32_t n_resid,
+                              const uint32_t* mvals, uint32_t n_roots, uint32_t n_atoms,
+                              const uint32_t* entries, uint32_t n_entries, const uint32_t* pieces,
+                              uint32_t n_pieces, const uint32_t* fixed, uint64_t seed, uint32_t r,
+                              uint32_t lanes, uint32_t lane0, uint32_t n_lanes, uint32_t* out,
+                              uint32_t* moves);
+
 /* Corpus batches: many programs, one launch.  Device-pointer API for
  * resident benchmarking; stream is a hipStream_t (NULL = the context's own
  * stream, which the synchronous calls also use).

@@ -28,6 +28,7 @@
 #include "mg_walk.h"
 #include "mg_walk_tree.h"
 #include "mg_walk_aim.h"
+#include "mg_walk_bound.h"
 
 // the interpreter of each register layout (mg_interp_asm.hip, one
 // translation unit per layout; mg_find_layout lists them)
@@ -110,6 +111,27 @@ hipError_t mg_launch_walk_aim_pick(const uint32_t* d_masks, const uint32_t* d_am
                                    uint32_t n_entries, const uint32_t* d_pieces, uint32_t n_resid,
                                    uint32_t* d_rstate, uint32_t* d_lives, mg_walk_state* d_state,
                                    uint32_t* d_trace, hipStream_t stream);
+// the round of mg_walk_bound (mg_walk_bound.hip): mg_walk_aim's
+// with the wider table, the side's fixed bits and the walkers' mask state
+hipError_t mg_launch_walk_bound_round(const uint32_t* d_bases, const mg_leafgen* d_gen,
+                                      const uint32_t* d_consts, uint32_t n_leaves, uint64_t seed,
+                                      uint32_t r, uint32_t lanes, uint32_t walkers,
+                                      const uint32_t* d_entries, uint32_t n_entries,
+                                      const uint32_t* d_pieces, const uint32_t* d_fixed,
+                                      const uint32_t* d_rstate, uint32_t n_resid,
+                                      const uint32_t* d_lives, uint32_t* d_leaves,
+                                      hipStream_t stream);
+hipError_t mg_launch_walk_bound_pick(const uint32_t* d_masks, const uint32_t* d_amasks,
+                                     const uint32_t* d_resid, const uint32_t* d_roots,
+                                     const uint32_t* d_atoms, const uint32_t* d_code,
+                                     uint32_t lanes, uint32_t walkers, uint32_t n_roots,
+                                     uint32_t n_atoms, uint32_t* d_bases, const mg_leafgen* d_gen,
+                                     const uint32_t* d_consts, uint32_t n_leaves, uint64_t seed,
+                                     uint32_t r, uint32_t max_rounds, const uint32_t* d_entries,
+                                     uint32_t n_entries, const uint32_t* d_pieces,
+                                     const uint32_t* d_fixed, uint32_t n_resid, uint32_t* d_rstate,
+                                     uint32_t* d_mstate, uint32_t* d_lives, mg_walk_state* d_state,
+                                     uint32_t* d_trace, hipStream_t stream);
 
 
 struct mg_ctx {
@@ -1019,7 +1041,8 @@ static bool walk_table_ok(const uint32_t* table, uint32_t n_roots, uint32_t n_re
 
 // what scores a walk's neighbours: the residual table of mg_walk (no atoms, no
 // code) or the tree tables of mg_walk_tree (table: its root entries); aim: the
-// round of mg_walk_aim with its aim table (tree scoring)
+// round of mg_walk_aim with its aim table (tree scoring); bound: the round of
+// mg_walk_bound, whose entries have 5 words and a fixed value each
 struct walk_scoring {
     const uint32_t* table;
     const uint32_t* atoms;
@@ -1032,6 +1055,8 @@ struct walk_scoring {
     uint32_t n_entries;
     const uint32_t* pieces;
     uint32_t n_pieces;
+    bool bound;
+    const uint32_t* fixed;
 };
 
 // The scored walk.  Rounds are queued back to back;
@@ -1048,6 +1073,8 @@ static int walk_run(mg_ctx* ctx, const mg_prog* prog, const uint32_t* starts, ui
         !out_rounds || !out_winner || (sc.n_atoms && !sc.atoms) || (sc.n_code && !sc.code) ||
         (sc.n_entries && !sc.entries) || (sc.n_pieces && !sc.pieces))
         return fail(ctx, MG_E_ARG, "null argument");
+    if (sc.bound && sc.n_entries && !sc.fixed)
+        return fail(ctx, MG_E_ARG, "walk_bound: null fixed values with %u entries", sc.n_entries);
     if (prog->n_leaves == 0) return fail(ctx, MG_E_ARG, "walk: the program has no leaves");
     if (walkers < 1 || walkers > MG_WALK_MAX_WALKERS)
         return fail(ctx, MG_E_ARG, "walk: %u walkers outside 1..%u", walkers, MG_WALK_MAX_WALKERS);
@@ -1077,7 +1104,14 @@ static int walk_run(mg_ctx* ctx, const mg_prog* prog, const uint32_t* starts, ui
         return fail(ctx, MG_E_ARG, "walk: a table entry names an unknown kind or a residual "
                     "probe at or above %u", n_resid);
     }
-    if (sc.aim && !mg_walk_aim_ok(sc.entries, sc.n_entries, sc.pieces, sc.n_pieces,
+    if (sc.bound && !mg_walk_bound_ok(sc.entries, sc.n_entries, sc.pieces, sc.n_pieces, sc.fixed,
+                                      prog->leafgen.data(), prog->n_leaves, n_resid, n_roots,
+                                      sc.n_atoms))
+        return fail(ctx, MG_E_ARG, "walk_bound: malformed aim table (mg_walk_bound_ok: what "
+                    "mg_walk_aim_ok checks, a mode above %u, a truth index outside the %u atoms "
+                    "or %u roots, an XOR entry with a truth or fixed word)", MG_BOUND_HIGH_STRICT,
+                    sc.n_atoms, n_roots);
+    if (sc.aim && !sc.bound && !mg_walk_aim_ok(sc.entries, sc.n_entries, sc.pieces, sc.n_pieces,
                                   prog->leafgen.data(), prog->n_leaves, n_resid))
         return fail(ctx, MG_E_ARG, "walk_aim: malformed aim table (mg_walk_aim_ok: at most %u "
                     "entries of 1..%u pieces inside the piece array, residual and leaf indices, "
@@ -1101,16 +1135,20 @@ static int walk_run(mg_ctx* ctx, const mg_prog* prog, const uint32_t* starts, ui
                  leaf_b = (size_t)n_leaves * 8 * total * 4,
                  probe_b = (size_t)prog->n_probes * 8 * total * 4,
                  atom_b = (size_t)sc.n_atoms * 4, code_b = (size_t)sc.n_code * 4,
-                 entry_b = (size_t)sc.n_entries * 12, piece_b = (size_t)sc.n_pieces * 16,
+                 entry_b = (size_t)sc.n_entries * (sc.bound ? 20 : 12), piece_b = (size_t)sc.n_pieces * 16,
                  rstate_b = sc.aim ? (size_t)walkers * n_resid * 32 : 0,
-                 live_b = sc.aim ? (size_t)walkers * MG_AIM_LIVE_WORDS * 4 : 0;
+                 live_b = sc.aim ? (size_t)walkers * MG_AIM_LIVE_WORDS * 4 : 0,
+                 fixed_b = sc.bound ? (size_t)sc.n_entries * 32 : 0,
+                 mstate_b = sc.bound ? (size_t)walkers * 4 * (MG_BOUND_MASK_WORDS(n_roots) +
+                                                              MG_BOUND_MASK_WORDS(sc.n_atoms)) : 0;
     const size_t off_base = align(state_b), off_gen = off_base + align(base_b),
                  off_table = off_gen + align(gen_b), off_trace = off_table + align(table_b),
                  off_root = off_trace + align(trace_b), off_leaf = off_root + align(root_b),
                  off_probe = off_leaf + align(leaf_b), off_atom = off_probe + align(probe_b),
                  off_code = off_atom + align(atom_b), off_entry = off_code + align(code_b),
                  off_piece = off_entry + align(entry_b), off_rstate = off_piece + align(piece_b),
-                 off_live = off_rstate + align(rstate_b), bytes = off_live + align(live_b);
+                 off_live = off_rstate + align(rstate_b), off_fixed = off_live + align(live_b),
+                 off_mstate = off_fixed + align(fixed_b), bytes = off_mstate + align(mstate_b);
     void* ws;
     int rc = workspace(ctx, bytes + 256, &ws);
     if (rc) return rc;
@@ -1128,6 +1166,8 @@ static int walk_run(mg_ctx* ctx, const mg_prog* prog, const uint32_t* starts, ui
     uint32_t* d_pieces = (uint32_t*)(w + off_piece);
     uint32_t* d_rstate = (uint32_t*)(w + off_rstate);
     uint32_t* d_lives = (uint32_t*)(w + off_live);
+    uint32_t* d_fixed = (uint32_t*)(w + off_fixed);
+    uint32_t* d_mstate = (uint32_t*)(w + off_mstate);
     HIPCHECK(ctx, hipMemsetAsync(d_state, 0xFF, state_b, ctx->stream));
     HIPCHECK(ctx, hipMemsetAsync(d_trace, 0, trace_b, ctx->stream));
     HIPCHECK(ctx, hipMemcpyAsync(d_bases, starts, base_b, hipMemcpyHostToDevice, ctx->stream));
@@ -1148,6 +1188,10 @@ static int walk_run(mg_ctx* ctx, const mg_prog* prog, const uint32_t* starts, ui
                                      ctx->stream));
     if (rstate_b) HIPCHECK(ctx, hipMemsetAsync(d_rstate, 0, rstate_b, ctx->stream));
     if (live_b) HIPCHECK(ctx, hipMemsetAsync(d_lives, 0, live_b, ctx->stream));
+    if (fixed_b)
+        HIPCHECK(ctx, hipMemcpyAsync(d_fixed, sc.fixed, fixed_b, hipMemcpyHostToDevice,
+                                     ctx->stream));
+    if (mstate_b) HIPCHECK(ctx, hipMemsetAsync(d_mstate, 0, mstate_b, ctx->stream));
     mg_run run = empty_run();
     run.leaves = d_leaves;
     run.root_bits = (uint64_t*)(w + off_root);
@@ -1166,7 +1210,12 @@ static int walk_run(mg_ctx* ctx, const mg_prog* prog, const uint32_t* starts, ui
     while (r < max_rounds && !done) {
         const uint32_t stop = max_rounds - r < sync_every ? max_rounds : r + sync_every;
         for (; r < stop; ++r) {
-            if (sc.aim)
+            if (sc.bound)
+                HIPCHECK(ctx, mg_launch_walk_bound_round(d_bases, d_gen, d_consts, n_leaves, seed,
+                                                         r, lanes, walkers, d_entries,
+                                                         sc.n_entries, d_pieces, d_fixed, d_rstate,
+                                                         n_resid, d_lives, d_leaves, ctx->stream));
+            else if (sc.aim)
                 HIPCHECK(ctx, mg_launch_walk_aim_round(d_bases, d_gen, d_consts, n_leaves, seed, r,
                                                        lanes, walkers, d_entries, sc.n_entries,
                                                        d_pieces, d_rstate, n_resid, d_lives,
@@ -1175,7 +1224,15 @@ static int walk_run(mg_ctx* ctx, const mg_prog* prog, const uint32_t* starts, ui
                 HIPCHECK(ctx, mg_launch_walk_round(d_bases, d_gen, d_consts, n_leaves, seed, r,
                                                    lanes, walkers, d_leaves, ctx->stream));
             HIPCHECK(ctx, launch(ctx, 0, prog->d_desc, 1, run, prog->n_lds, ctx->stream));
-            if (sc.aim)
+            if (sc.bound)
+                HIPCHECK(ctx, mg_launch_walk_bound_pick(d_masks, d_amasks, d_resid, d_table,
+                                                        d_atoms, d_code, lanes, walkers, n_roots,
+                                                        sc.n_atoms, d_bases, d_gen, d_consts,
+                                                        n_leaves, seed, r, max_rounds, d_entries,
+                                                        sc.n_entries, d_pieces, d_fixed, n_resid,
+                                                        d_rstate, d_mstate, d_lives, d_state,
+                                                        d_trace, ctx->stream));
+            else if (sc.aim)
                 HIPCHECK(ctx, mg_launch_walk_aim_pick(d_masks, d_amasks, d_resid, d_table, d_atoms,
                                                       d_code, lanes, walkers, n_roots, d_bases,
                                                       d_gen, d_consts, n_leaves, seed, r,
@@ -1259,6 +1316,23 @@ int mg_walk_aim(mg_ctx* ctx, const mg_prog* prog, const uint32_t* starts, uint32
                     out_winner);
 }
 
+// The tree-scored walk with moves aimed by equalities and orders (DESIGN.md
+// §3.13): mg_walk_aim with the kernels of mg_walk_bound.hip and their table.
+int mg_walk_bound(mg_ctx* ctx, const mg_prog* prog, const uint32_t* starts, uint32_t walkers,
+                  uint32_t n_roots, uint32_t mask_probe0, const uint32_t* roots, uint32_t n_atoms,
+                  const uint32_t* atoms, const uint32_t* code, uint32_t n_code, uint32_t n_resid,
+                  const uint32_t* entries, uint32_t n_entries, const uint32_t* pieces,
+                  uint32_t n_pieces, const uint32_t* fixed, uint64_t seed, uint32_t lanes,
+                  uint32_t max_rounds, uint32_t sync_every, uint32_t* out_leaves,
+                  uint32_t* out_nfail, uint32_t* out_cost, uint32_t* out_rounds, uint32_t* trace,
+                  uint32_t* out_winner) {
+    const walk_scoring sc = {roots, atoms, n_atoms, code, n_code, true, true,
+                             entries, n_entries, pieces, n_pieces, true, fixed};
+    return walk_run(ctx, prog, starts, walkers, n_roots, mask_probe0, sc, n_resid, seed, lanes,
+                    max_rounds, sync_every, out_leaves, out_nfail, out_cost, out_rounds, trace,
+                    out_winner);
+}
+
 // Host only: lanes lane0 .. lane0 + n_lanes - 1 of round r of the lane
 // function of mg_walk_aim.h, as the mutate kernel writes them.
 int mg_walk_aim_mutate_host(const mg_leafgen* leaves, uint32_t n_leaves, const uint32_t* consts,
@@ -1288,6 +1362,48 @@ int mg_walk_aim_mutate_host(const mg_leafgen* leaves, uint32_t n_leaves, const u
         const uint32_t e = mg_walk_aim_lane(base, leaves, consts, n_leaves, seed, r, lane0 + a,
                                             lanes, entries, pieces, rvals, live, out + a, n_lanes,
                                             &mv);
+        if (moves) {
+            moves[5 * (size_t)a] = mv.n;
+            moves[5 * (size_t)a + 1] = mv.kind[0] | mv.kind[1] << 8;
+            moves[5 * (size_t)a + 2] = mv.leaf[0];
+            moves[5 * (size_t)a + 3] = mv.leaf[1];
+            moves[5 * (size_t)a + 4] = e;
+        }
+    }
+    return MG_OK;
+}
+
+// Host only: the same of the lane function of mg_walk_bound.h.
+int mg_walk_bound_mutate_host(const mg_leafgen* leaves, uint32_t n_leaves, const uint32_t* consts,
+                              uint32_t n_consts, const uint32_t* base, const uint32_t* rvals,
+                              uint32_t n_resid, const uint32_t* mvals, uint32_t n_roots,
+                              uint32_t n_atoms, const uint32_t* entries, uint32_t n_entries,
+                              const uint32_t* pieces, uint32_t n_pieces, const uint32_t* fixed,
+                              uint64_t seed, uint32_t r, uint32_t lanes, uint32_t lane0,
+                              uint32_t n_lanes, uint32_t* out, uint32_t* moves) {
+    if (!leaves || !base || !out || (n_consts && !consts) || n_leaves == 0) return MG_E_ARG;
+    if (lanes < 1 || lanes > MG_REPAIR_MAX_LANES || r >= MG_REPAIR_MAX_ROUNDS) return MG_E_ARG;
+    if (lane0 > lanes || n_lanes > lanes - lane0) return MG_E_ARG;
+    if (n_roots > MG_WT_MAX_ROOTS || n_atoms > MG_WT_MAX_ATOMS) return MG_E_ARG;
+    for (uint32_t i = 0; i < n_leaves; ++i) {
+        if (leaves[i].width < 1 || leaves[i].width > MG_MAX_WIDTH) return MG_E_ARG;
+        if ((uint64_t)leaves[i].pool_off + leaves[i].pool_n > n_consts) return MG_E_ARG;
+        uint32_t v[8];
+        memcpy(v, base + (size_t)i * 8, 32);
+        mg_repair_mask(v, leaves[i].width);
+        if (memcmp(v, base + (size_t)i * 8, 32)) return MG_E_ARG;     // a base beyond its width
+    }
+    if (!mg_walk_bound_ok(entries, n_entries, pieces, n_pieces, fixed, leaves, n_leaves, n_resid,
+                          n_roots, n_atoms))
+        return MG_E_ARG;
+    uint32_t live[MG_AIM_LIVE_WORDS];
+    mg_walk_bound_live(entries, n_entries, rvals, mvals, MG_BOUND_MASK_WORDS(n_roots), live);
+    for (uint32_t a = 0; a < n_lanes; ++a) {
+        for (size_t i = 0; i < (size_t)n_leaves * 8; ++i) out[i * n_lanes + a] = base[i];
+        mg_repair_moves mv;
+        const uint32_t e = mg_walk_bound_lane(base, leaves, consts, n_leaves, seed, r, lane0 + a,
+                                              lanes, entries, pieces, fixed, rvals, live, out + a,
+                                              n_lanes, &mv);
         if (moves) {
             moves[5 * (size_t)a] = mv.n;
             moves[5 * (size_t)a + 1] = mv.kind[0] | mv.kind[1] << 8;

@@ -286,7 +286,7 @@ class WalkResult:
 
 def walk_ref(values_fn: Callable, leafgen, consts, starts, table, seed: int, lanes: int = 4096,
              max_rounds: int = 64, sync_every: int = 8, score: Optional[Callable] = None,
-             aims=None) -> WalkResult:
+             aims=None, bounds=None) -> WalkResult:
     """The whole loop as ``mg_walk`` runs it.  ``values_fn`` maps an SoA leaf
     array ``(n_leaves, 8, n)`` to ``(bits (n, n_roots) bool, resid (n_resid,
     8, n) u32)``: the verdicts and the residual values.  Walker w moves under
@@ -300,7 +300,12 @@ def walk_ref(values_fn: Callable, leafgen, consts, starts, table, seed: int, lan
     ``aims``: the aim table of ``mg_walk_aim`` (:func:`aim_table`): the
     neighbours are those of :func:`aim_mutate_ref` under the residual values
     of the walker's base — the last element of what ``values_fn`` returns, in
-    the column of the lane it adopted (none before round 0's adoption)."""
+    the column of the lane it adopted (none before round 0's adoption).
+
+    ``bounds``: the table of ``mg_walk_bound`` (:func:`bound_table`) instead:
+    the neighbours are those of :func:`bound_mutate_ref` under the adopted
+    lane's residual values, root bits (the first element of what ``values_fn``
+    returns) and atom bits (the second of three; none without tree scoring)."""
     bases = np.ascontiguousarray(starts, dtype=np.uint32).copy()
     walkers = bases.shape[0]
     if not 1 <= walkers <= MAX_WALKERS or bases.shape[2:] != (8,):
@@ -313,7 +318,11 @@ def walk_ref(values_fn: Callable, leafgen, consts, starts, table, seed: int, lan
     while r < max_rounds and not any(k is not None and k[0] == 0 for k in keys):
         stop = max_rounds if max_rounds - r < sync_every else r + sync_every
         while r < stop:
-            if aims is None:
+            if bounds is not None:
+                nb = np.concatenate([bound_mutate_ref(leafgen, consts, bases[w], rvals[w], bounds,
+                                                      seed ^ (w * CW & M64), r, lanes)
+                                     for w in range(walkers)], axis=2)
+            elif aims is None:
                 nb = np.concatenate([mutate_ref(leafgen, consts, bases[w], seed ^ (w * CW & M64),
                                                 r, lanes) for w in range(walkers)], axis=2)
             else:
@@ -331,7 +340,13 @@ def walk_ref(values_fn: Callable, leafgen, consts, starts, table, seed: int, lan
                 key = (int(nf[lane]), int(co[lane]))
                 if keys[w] is None or key < keys[w]:
                     bases[w], keys[w] = nb[:, :, w * lanes + lane], key
-                    if aims is not None:
+                    if bounds is not None:
+                        at = w * lanes + lane
+                        rvals[w] = (np.ascontiguousarray(values[-1][:, :, at]),
+                                    np.array(values[0][at], dtype=bool),
+                                    np.array(values[1][at] if len(values) == 3 else [],
+                                             dtype=bool))
+                    elif aims is not None:
                         rvals[w] = np.ascontiguousarray(values[-1][:, :, w * lanes + lane])
                 trace[w, r] = key
             r += 1
@@ -784,6 +799,15 @@ def aim_pieces(t, program) -> Optional[list]:
     term ``t`` as a destination, ``value_bit`` relative to
     ``t``'s bit 0; None when ``t`` does not resolve.  A numeral resolves to no
     piece."""
+    side = _resolve_side(t, program)
+    return None if side is None else side[0]
+
+
+def _resolve_side(t, program) -> Optional[tuple]:
+    """``(pieces, fixed)`` of ``t`` by the rules of :func:`aim_pieces`;
+    ``fixed``: the bits of ``t`` that numerals give (a numeral, or a numeral
+    operand of a concat, at its offset; the numeral arm of an ``ite`` gives
+    none), as an int."""
     leaves = {(l.kind, l.source, l.entry, l.chunk): i for i, l in enumerate(program.leaves)}
     subst = getattr(program.presets, "subst", None) or {}
 
@@ -797,37 +821,43 @@ def aim_pieces(t, program) -> Optional[list]:
             out.append((li, 0, RESIDUAL_BITS * k, program.leaves[li].width))
         return out
 
+    def leafy(ps):
+        return None if ps is None else (ps, 0)
+
     def go(t):
         if t.op == "bvnum":
-            return []
+            return [], t.params[0] % (1 << t.width)
         if t.op == "var" and t.is_bv():
-            return cells("var", t.params[0], 0, t.width)
+            return leafy(cells("var", t.params[0], 0, t.width))
         if t.op == "concat":
-            out, off = [], t.width
+            out, fixed, off = [], 0, t.width
             for a in t.args:                             # high first
                 off -= a.width
-                ps = go(a)
-                if ps is None:
+                side = go(a)
+                if side is None:
                     return None
-                out += [(l, lb, vb + off, n) for l, lb, vb, n in ps]
-            return out
+                out += [(l, lb, vb + off, n) for l, lb, vb, n in side[0]]
+                fixed |= side[1] << off
+            return out, fixed
         if t.op == "extract":
             hi, lo = t.params
-            ps = go(t.args[0])
-            if ps is None:
+            side = go(t.args[0])
+            if side is None:
                 return None
             out = []
-            for l, lb, vb, n in ps:
+            for l, lb, vb, n in side[0]:
                 s, e = max(vb, lo), min(vb + n, hi + 1)
                 if s < e:
                     out.append((l, lb + s - vb, s - lo, e - s))
-            return out
+            return out, side[1] >> lo & ((1 << (hi - lo + 1)) - 1)
         if t.op == "zero_extend":
             return go(t.args[0])
         if t.op == "ite" and t.is_bv():                  # the guard is ignored: a proposal
             _, x, y = t.args
             if x.op == "bvnum" or y.op == "bvnum":
-                return go(y if x.op == "bvnum" else x)
+                side = go(y if x.op == "bvnum" else x)
+                # (an arm that is itself a numeral: no piece, and no fixed bit)
+                return side if side is None or side[0] else ([], 0)
             return None
         if t.op == "select" and t.args[0].op == "array":
             name = t.args[0].params[0]
@@ -835,7 +865,7 @@ def aim_pieces(t, program) -> Optional[list]:
             ckeys = list(program.table_ckeys.get(name, []))
             if key is None or key not in ckeys:
                 return None
-            return cells("cval", name, ckeys.index(key), t.width)
+            return leafy(cells("cval", name, ckeys.index(key), t.width))
         return None
     return go(t)
 
@@ -945,6 +975,232 @@ def aim_mutate_ref(leafgen, consts, base, rvals, aims: Aims, seed: int, r: int,
 
 
 # ---------------------------------------------------------------------------
+# aims for orders: a failing order's difference says what
+# value one of its sides must take
+# ---------------------------------------------------------------------------
+
+# the constants of csrc/mg_walk_bound.h
+BOUND_XOR, BOUND_LOW, BOUND_LOW_STRICT, BOUND_HIGH, BOUND_HIGH_STRICT = range(5)
+BOUND_ATOM = 1 << 31
+_STRICT = ("bvult", "bvslt", "bvugt", "bvsgt")
+M256 = (1 << 256) - 1
+
+
+@dataclass
+class Bounds:
+    """The table of ``mg_walk_bound`` (``csrc/mg_walk_bound.h``)."""
+    entries: np.ndarray        # (n, 5) u32: residual probe, first piece, pieces, mode, truth
+    pieces: np.ndarray         # (m, 4) u32: leaf, leaf_bit, value_bit, len
+    fixed: np.ndarray          # (n, 8) u32: the numeral bits of an order entry's side
+    sides: list                # per entry: XOR: the side of the xor it moves; order: 0 lo, 1 hi
+    n_roots: int = 0           # what the truth indices are below
+    n_atoms: int = 0
+
+    def __len__(self) -> int:
+        return len(self.entries)
+
+    @property
+    def n_order(self) -> int:
+        return int((self.entries[:, 3] != BOUND_XOR).sum()) if len(self.entries) else 0
+
+    def of(self, e: int) -> list:
+        """Entry ``e``'s pieces as (leaf, leaf_bit, value_bit, len) tuples."""
+        _, off, cnt = (int(x) for x in self.entries[e, :3])
+        return [tuple(int(x) for x in row) for row in self.pieces[off:off + cnt]]
+
+    def fixed_of(self, e: int) -> int:
+        return _ints(self.fixed[e:e + 1])[0]
+
+
+def _u256(v: int) -> np.ndarray:
+    return np.frombuffer((v & M256).to_bytes(32, "little"), dtype="<u4")
+
+
+def make_bounds(entries, n_roots: int = 0, n_atoms: int = 0) -> Bounds:
+    """``Bounds`` of ``[(residual probe, pieces, mode, truth, fixed int), ..]``
+    (an aim-table pair ``(probe, pieces)`` is an XOR entry)."""
+    rows, pieces, fixed, sides = [], [], [], []
+    for ent in entries:
+        p, ps, mode, truth, fx = tuple(ent) + (BOUND_XOR, 0, 0)[len(ent) - 2:]
+        rows.append((p, len(pieces), len(ps), mode, truth))
+        pieces.extend(ps)
+        fixed.append(_u256(fx))
+        sides.append(1 if mode >= BOUND_HIGH else 0)
+    return Bounds(np.array(rows, dtype=np.uint32).reshape(-1, 5),
+                  np.array(pieces, dtype=np.uint32).reshape(-1, 4),
+                  np.array(fixed, dtype=np.uint32).reshape(-1, 8), sides, n_roots, n_atoms)
+
+
+def bounds_of_aims(aims: Aims, n_roots: int = 0, n_atoms: int = 0) -> Bounds:
+    """An aim table as XOR entries."""
+    n = len(aims)
+    entries = np.zeros((n, 5), dtype=np.uint32)
+    entries[:, :3] = aims.entries
+    return Bounds(entries, np.array(aims.pieces, dtype=np.uint32).reshape(-1, 4),
+                  np.zeros((n, 8), dtype=np.uint32), list(aims.sides), n_roots, n_atoms)
+
+
+def bound_mask_words(bits) -> np.ndarray:
+    """Mask bits as the words of their mask probes' rows (``census.mask_probes``:
+    bit k is bit k % 32 of word k / 32), ``ceil(n / 256) * 8`` u32."""
+    bits = np.asarray(bits, dtype=bool)
+    out = np.zeros((len(bits) + 255) // 256 * 256, dtype=bool)
+    out[:len(bits)] = bits
+    return np.packbits(out.reshape(-1, 32), axis=1, bitorder="little").view("<u4").reshape(-1)
+
+
+def order_sides(node, negated: bool = False):
+    """``(lo, hi, strict)`` of an order atom (of the opposite order when
+    ``negated``), oriented as :func:`_difference` orients it (its residual is
+    ``lo - hi``), or None."""
+    if node.op not in _LESS + _GREATER:
+        return None
+    op = _NEGATED_ORDER[node.op] if negated else node.op
+    lo, hi = node.args if op in _LESS else node.args[::-1]
+    return lo, hi, op in _STRICT
+
+
+def _order_probe(trees: Trees, lo, hi) -> Optional[int]:
+    """The ``bvsub(lo, hi)`` among ``trees.probes``, by its operands' ids."""
+    for p, d in enumerate(trees.probes):
+        if d.op == "bvsub" and len(d.args) == 2 and (d.args[0].id, d.args[1].id) == (lo.id, hi.id):
+            return p
+    return None
+
+
+def bound_side(t, program) -> Optional[tuple]:
+    """``(pieces, fixed)`` of one side of an order as a destination (DESIGN.md
+    §3.13), or None: the side does not resolve, has no piece or more than 64,
+    or one of its leaves is derived by the program."""
+    side = _resolve_side(t, program)
+    if side is None or not side[0] or len(side[0]) > AIM_MAX_PIECES or \
+            any(l in program.derived for l, *_ in side[0]):
+        return None
+    return side
+
+
+def bound_table(constraints: Sequence, trees: Trees, program) -> Bounds:
+    """The table of ``mg_walk_bound``: the entries of
+    :func:`aim_table` as XOR entries, in its order; then, for every MAGNITUDE
+    atom of ``trees`` in atom order and after them for every simple MAGNITUDE
+    root in root order (not one that is simple only because ``MAX_ATOMS`` was
+    exceeded), an entry for side ``lo`` (LOW, LOW_STRICT for a strict order)
+    and one for side ``hi`` (HIGH, HIGH_STRICT) where :func:`bound_side`
+    resolves it.  At most 256 entries, the first ones."""
+    constraints = list(constraints)
+    aims = aim_table(trees, program)
+    rows = [(int(p), aims.of(e), BOUND_XOR, 0, 0) for e, (p, _, _) in enumerate(aims.entries)]
+    sides = list(aims.sides)
+
+    def order(node, truth, negated=False):
+        got = order_sides(node, negated)
+        if got is None:
+            return
+        lo, hi, strict = got
+        p = _order_probe(trees, lo, hi)
+        if p is None:
+            return
+        for side, t in enumerate((lo, hi)):
+            res = bound_side(t, program)
+            if res is not None:
+                rows.append((p, res[0], (BOUND_LOW, BOUND_HIGH)[side] + int(strict), truth, res[1]))
+                sides.append(side)
+
+    for i, e in enumerate(trees.atoms):
+        if int(e) >> 16 == MAGNITUDE:
+            order(trees.atom_nodes[i], BOUND_ATOM | i)
+    for k, c in enumerate(constraints):
+        if trees.is_tree(k) or trees.kind(k) != MAGNITUDE:
+            continue
+        d, neg = peel(c)
+        if d.op not in _NEGATED_ORDER:                   # the classify fallback of a tree
+            continue
+        order(d, k, neg)
+    out = make_bounds(rows[:AIM_MAX_ENTRIES], len(constraints), trees.n_atoms)
+    out.sides = sides[:AIM_MAX_ENTRIES]
+    return out
+
+
+def bound_live_ref(state, bounds: Bounds) -> list:
+    """L: the live entries in table order under ``state`` = (residual values
+    (n_resid, 8) u32, root bits, atom bits) of the walker's base; empty for
+    None (round 0).  An XOR entry is live iff its residual is not zero, an
+    order entry iff its truth bit is clear."""
+    if state is None:
+        return []
+    rv = np.asarray(state[0], dtype=np.uint32).reshape(-1, 8)
+    live = []
+    for e in range(len(bounds)):
+        p, _, _, mode, truth = (int(x) for x in bounds.entries[e])
+        if mode == BOUND_XOR:
+            on = bool(rv[p].any())
+        elif truth & BOUND_ATOM:
+            on = not state[2][truth & ~BOUND_ATOM]
+        else:
+            on = not state[1][truth]
+        if on:
+            live.append(e)
+    return live
+
+
+def bound_picks_ref(state, bounds: Bounds, r: int, lanes: int) -> np.ndarray:
+    """(lanes,) int64: the entry lane j of round ``r`` applies, or ``AIM_NONE``:
+    :func:`aim_picks_ref`'s layout over the live list of :func:`bound_live_ref`."""
+    out = np.full(lanes, AIM_NONE, dtype=np.int64)
+    live = bound_live_ref(state, bounds)
+    n1 = min(len(live), lanes // 8)
+    for j in range(1, 2 * n1 + 1):
+        out[j] = live[((j if j <= n1 else j - n1) - 1 + r * n1) % len(live)]
+    return out
+
+
+def bound_mutate_ref(leafgen, consts, base, state, bounds: Bounds, seed: int, r: int,
+                     lanes: int) -> np.ndarray:
+    """``[n_leaves][8][lanes]`` u32: the neighbours of ``base`` that round
+    ``r`` of ``mg_walk_bound`` evaluates — the specification of
+    ``csrc/mg_walk_bound.h``.  :func:`aim_mutate_ref` with the picks of
+    :func:`bound_picks_ref`; an XOR entry acts as there, an order entry with
+    residual value D and s = 1 if strict else 0 gathers ``V = fixed | OR
+    ((base[leaf] >> leaf_bit) & mask(len)) << value_bit`` from the base, takes
+    ``T = V - D - s`` (LOW) or ``V + D + s`` (HIGH) mod 2^256 and, in piece
+    order, replaces bits ``leaf_bit ..`` of the lane's current value of the
+    leaf by ``(T >> value_bit) & mask(len)``."""
+    base = np.ascontiguousarray(base, dtype=np.uint32).reshape(-1, 8)
+    picks = bound_picks_ref(state, bounds, r, lanes)
+    n1 = int((picks != AIM_NONE).sum()) // 2
+    out = np.repeat(base[:, :, None], lanes, axis=2)
+    moves = moves_ref(leafgen, consts, base, seed, r, lanes)
+    bvals = _ints(base)
+    rv = _ints(np.asarray(state[0], dtype=np.uint32).reshape(-1, 8)) if n1 else []
+    for lane in range(lanes):
+        cur = {}
+        if picks[lane] != AIM_NONE:
+            e = int(picks[lane])
+            p, _, _, mode, _ = (int(x) for x in bounds.entries[e])
+            R = rv[p]
+            if mode == BOUND_XOR:
+                for leaf, leaf_bit, value_bit, n in bounds.of(e):
+                    cur[leaf] = cur.get(leaf, bvals[leaf]) ^ (
+                        (R >> value_bit & ((1 << n) - 1)) << leaf_bit)
+            else:
+                V = bounds.fixed_of(e)
+                for leaf, leaf_bit, value_bit, n in bounds.of(e):
+                    V |= (bvals[leaf] >> leaf_bit & ((1 << n) - 1)) << value_bit
+                s = 1 if mode in (BOUND_LOW_STRICT, BOUND_HIGH_STRICT) else 0
+                T = (V - R - s if mode <= BOUND_LOW_STRICT else V + R + s) & M256
+                for leaf, leaf_bit, value_bit, n in bounds.of(e):
+                    m = (1 << n) - 1
+                    cur[leaf] = (cur.get(leaf, bvals[leaf]) & ~(m << leaf_bit)) | (
+                        (T >> value_bit & m) << leaf_bit)
+        if lane > n1:
+            for leaf, _, v in moves[lane]:
+                cur[leaf] = v
+        for leaf, v in cur.items():
+            out[leaf, :, lane] = np.frombuffer(v.to_bytes(32, "little"), dtype="<u4")
+    return out
+
+
+# ---------------------------------------------------------------------------
 # repair a missed group
 # ---------------------------------------------------------------------------
 
@@ -991,7 +1247,13 @@ def repair_group(nodes: Sequence, n_cand: int = 1 << 16, form: str = "search", l
     :func:`aim_table` on the compiled program (``aims`` in the result); with
     no entry, and where ``"tree"`` falls back, it runs as ``"tree"`` does;
     ``scoring`` is ``"aim"`` when aimed moves ran, and ``program`` is the
-    compiled program whose leaves the table names."""
+    compiled program whose leaves the table names.
+
+    ``scored="bound"``: the same with aims for orders too (``mg_walk_bound``,
+    DESIGN.md §3.13): compiled as ``"tree"``, then the table of
+    :func:`bound_table` on the compiled program (``bounds`` in the result);
+    ``scoring`` is ``"bound"`` when the table has an order entry, else the
+    group runs exactly as ``scored="aim"`` does."""
     from . import census as CS
     from . import model as M
     from .assign import unpack
@@ -1011,7 +1273,7 @@ def repair_group(nodes: Sequence, n_cand: int = 1 << 16, form: str = "search", l
         return out
     # (built before the mask: a program's schedule follows the node ids, and a
     # wide mask leaves the compiler's spill budget little room)
-    trees = distance_trees(nodes) if scored in ("tree", "aim") else None
+    trees = distance_trees(nodes) if scored in ("tree", "aim", "bound") else None
     resid, table = residuals(nodes) if scored else ([], flat_table(len(nodes)))
     n_amask = 0
     try:
@@ -1048,11 +1310,19 @@ def repair_group(nodes: Sequence, n_cand: int = 1 << 16, form: str = "search", l
         out.update(status=CS.UNSUPPORTED, why=str(e))
         return out
     n_mask = CS.n_mask_probes(len(nodes))
-    aims = aim_table(trees, masked) if scored == "aim" and trees is not None else None
+    aims = aim_table(trees, masked) if scored in ("aim", "bound") and trees is not None else None
+    bounds = bound_table(nodes, trees, masked) if scored == "bound" and trees is not None else None
+    if bounds is not None and not bounds.n_order:
+        bounds = None
+    if scored == "bound":
+        out["bounds"] = bounds if bounds is not None else (
+            bounds_of_aims(aims if aims is not None else no_aims(), len(nodes),
+                           trees.n_atoms if trees is not None else 0))
     if scored:
-        out["scoring"] = ("aim" if aims is not None and len(aims) else
+        out["scoring"] = ("bound" if bounds is not None else
+                          "aim" if aims is not None and len(aims) else
                           "tree" if trees is not None else "table" if resid else "count")
-    if scored == "aim":
+    if scored in ("aim", "bound"):
         out["aims"] = aims if aims is not None else no_aims()
         out["program"] = masked                          # what the table's leaves index
     if masked.n_user_probes != n_mask + n_amask + len(resid):
@@ -1083,7 +1353,11 @@ def repair_group(nodes: Sequence, n_cand: int = 1 << 16, form: str = "search", l
         starts = np.stack([leaves if i == c.best_index else eng.witness(full, M.SEARCH_SEED, i)[0]
                            for i in picks])
         wide = eng.load(CS.census_view(masked, n_mask + n_amask + len(resid)), gens, prog_seed=0)
-        if trees is not None and aims is not None and len(aims):
+        if trees is not None and bounds is not None:
+            res = eng.walk_bound(wide, starts, len(nodes), trees, bounds, seed, lanes, max_rounds,
+                                 sync_every)
+            out["trees"] = trees
+        elif trees is not None and aims is not None and len(aims):
             res = eng.walk_aim(wide, starts, len(nodes), trees, aims, seed, lanes, max_rounds,
                                sync_every)
             out["trees"] = trees

@@ -39,6 +39,13 @@ usage: tools/miss_census.py --workload {c1,c3,c3o,c4,c5} --query N
            every walker's trace, the tree of each root
            the winner still fails, and the device time per round beside
            mg_walk_tree's from the same starts
+       ... --walk-bound [--walkers N] [--lanes L] [--rounds R]
+           after the census, that walk with aims for orders too (DESIGN.md
+           §3.13): the table's order entries (residual probe, mode, truth bit,
+           pieces, fixed bits, destination), per order atom and simple order
+           root the rule that refused each side without an entry, every
+           walker's trace, the tree of each root the winner still fails, and
+           the device time per round beside mg_walk_aim's from the same starts
        tools/miss_census.py [workload] [n]
            the older census: which of a stream's first n queries the batched
            search misses, grouped by the shape of their newest constraint
@@ -465,6 +472,123 @@ def show_aim(rows, lanes):
                                         g.get("tree_end")))
 
 
+def bound_rows(wl, qi, n_cand, lanes, rounds, walkers):
+    """Per independent group of the query: what ``repair.repair_group(scored=
+    "bound")`` did with ``walkers`` walkers (the table's order entries, per
+    order atom and simple order root what refused each side without an entry,
+    every walker's trace, the tree of each root the winner still fails), and
+    the device time per round of mg_walk_bound beside mg_walk_aim's from the
+    same starts."""
+    import mythril_amd.model as M
+    from mythril_amd import repair as RP
+    from mythril_amd.smt import node as N
+    kinds = ("flat", "hamming", "magnitude")
+    modes = ("xor", "low", "low_strict", "high", "high_strict")
+    rows = []
+    q = stream_query(wl, qi)
+    where = {}
+    for i, c in enumerate(q):
+        where.setdefault(c.id, []).append(i)
+    for group in M.dependence_buckets(q):
+        pos = [where[c.id].pop(0) for c in group]        # root k = constraint pos[k]
+        kw = dict(n_cand=n_cand, form="search", lanes=lanes, max_rounds=rounds)
+        g = RP.repair_group(group, scored="bound", walkers=walkers, **kw)
+        row = {"constraints": len(group), "status": g["status"], "scoring": g.get("scoring")}
+        if "why" in g:
+            row["why"] = g["why"]
+        res, T, B = g.get("repair"), g.get("trees"), g.get("bounds")
+        if res is not None and T is not None:
+            row.update(starts=g["starts"], winner=res.winner, rounds=res.rounds, walkers=walkers,
+                       atoms=T.n_atoms, residual_probes=len(T.probes),
+                       nfail=[int(v) for v in res.nfail], cost=[int(v) for v in res.cost],
+                       traces=[_runs(res.trace[w, :res.rounds]) for w in range(walkers)],
+                       bound_kernel_ms=round(res.kernel_ms, 3),
+                       bound_ms_per_round=round(res.kernel_ms / max(1, res.rounds), 4))
+            row["xor_entries"] = len(B) - B.n_order
+            row["entries"] = []
+            for e in range(len(B)):
+                p, _, cnt, mode, truth = (int(x) for x in B.entries[e])
+                if mode == RP.BOUND_XOR:
+                    continue
+                row["entries"].append({
+                    "probe": p, "mode": modes[mode], "pieces": cnt,
+                    "truth": ("atom %d" % (truth & ~RP.BOUND_ATOM)) if truth & RP.BOUND_ATOM
+                    else "root %d" % truth,
+                    "fixed": "%#x" % B.fixed_of(e),
+                    "destination": N.to_sexpr(T.probes[p].args[B.sides[e]], 3)})
+            prog = g["program"]
+            # every order atom, then every simple order root: the side without an entry
+            orders = [("atom %d" % i, RP.order_sides(T.atom_nodes[i]))
+                      for i, e in enumerate(T.atoms) if int(e) >> 16 == RP.MAGNITUDE]
+            for k, c in enumerate(group):
+                if not T.is_tree(k) and T.kind(k) == RP.MAGNITUDE:
+                    d, neg = RP.peel(c)
+                    orders.append(("root %d" % k, RP.order_sides(d, neg)))
+            row["orders"] = len(orders)
+            row["refused"] = []
+            for name, sides in orders:
+                if sides is None:
+                    row["refused"].append({"order": name, "side": "-", "term": "",
+                                           "why": "a simple root of the classify fallback"})
+                    continue
+                for side, t in zip(("lo", "hi"), sides[:2]):
+                    if RP.bound_side(t, prog) is not None:
+                        continue
+                    ps = RP.aim_pieces(t, prog)
+                    why = RP.aim_refusal(t, prog) or (
+                        "no piece" if not ps else "%d pieces" % len(ps) if len(ps) > 64 else
+                        "a leaf the construction derives")
+                    row["refused"].append({"order": name, "side": side, "why": why,
+                                           "term": N.to_sexpr(t, 3)})
+            row["failing"] = [{"root": k, "constraint": pos[k],
+                               "tree": T.listing(k, 3, g.get("atom_state")) if T.is_tree(k) else
+                               "simple %s: %s" % (kinds[T.kind(k)], N.to_sexpr(group[k], 3))}
+                              for k in g.get("failing", [])]
+            aim = RP.repair_group(group, scored="aim", walkers=walkers, **kw).get("repair")
+            if aim is not None:
+                row["aim_ms_per_round"] = round(aim.kernel_ms / max(1, aim.rounds), 4)
+                row["aim_rounds"] = aim.rounds
+                row["aim_end"] = [int(aim.nfail[aim.winner]), int(aim.cost[aim.winner])]
+        rows.append(row)
+    return rows
+
+
+def show_bound(rows, lanes):
+    for gi, g in enumerate(rows):
+        print(" bound walk group %d: %d constraints -> %s%s; scoring: %s" % (
+            gi, g["constraints"], g["status"], (" (%s)" % g["why"]) if "why" in g else "",
+            g["scoring"]))
+        if "traces" not in g:
+            continue
+        print("  %d atoms, %d residual probes; table: %d XOR entries, %d order entries for %d "
+              "orders" % (g["atoms"], g["residual_probes"], g["xor_entries"], len(g["entries"]),
+                          g["orders"]))
+        for e in g["entries"]:
+            print("   entry: residual %d %s (%s), %d pieces, fixed %s: %.140s" % (
+                e["probe"], e["mode"], e["truth"], e["pieces"], e["fixed"], e["destination"]))
+        # (--json lists every refused side; here one line per rule)
+        rules = collections.OrderedDict()
+        for e in g["refused"]:
+            rules.setdefault(e["why"], []).append(e)
+        for why, es in rules.items():
+            print("   no entry: %d sides: %s, e.g. %s side %s: %.120s" % (
+                len(es), why, es[0]["order"], es[0]["side"], es[0]["term"]))
+        print("  %d walkers, %d rounds of %d lanes each; winner: walker %d" % (
+            g["walkers"], g["rounds"], lanes, g["winner"]))
+        for w, tr in enumerate(g["traces"]):
+            print("   walker %2d from candidate %d: ends %d/%d; nfail/cost per round: %s" % (
+                w, g["starts"][w], g["nfail"][w], g["cost"][w], tr))
+        for f in g["failing"]:
+            print("  the winner still fails constraint #%d (root %d):" % (f["constraint"], f["root"]))
+            for line in f["tree"].split("\n"):
+                print("     " + line)
+        print("  device time per round: mg_walk_%s x%d %.4f ms; mg_walk_aim x%d %s ms "
+              "(%s rounds, ends %s)" % ("bound" if g["scoring"] == "bound" else "aim", g["walkers"],
+                                        g["bound_ms_per_round"], g["walkers"],
+                                        g.get("aim_ms_per_round"), g.get("aim_rounds"),
+                                        g.get("aim_end")))
+
+
 def show(r):
     print("== %s query %d%s: %d constraints, %d candidates per group (%.0f ms in all)" % (
         r["workload"], r["query"], " (top-level ands split, i.j = conjunct j of constraint i)"
@@ -515,6 +639,8 @@ def main():
                     help="then run the walk scored by distance trees (DESIGN.md 3.11)")
     ap.add_argument("--walk-aim", action="store_true",
                     help="then run the tree-scored walk with aimed moves (DESIGN.md 3.12)")
+    ap.add_argument("--walk-bound", action="store_true",
+                    help="then run that walk with aims for orders too (DESIGN.md 3.13)")
     ap.add_argument("--walkers", type=int, default=16)
     ap.add_argument("--lanes", type=int, default=4096)
     ap.add_argument("--rounds", type=int, default=64)
@@ -544,6 +670,10 @@ def main():
         for r in reports:
             r["walk_aim"] = aim_rows(r["workload"], r["query"], a.candidates, a.lanes, a.rounds,
                                      a.walkers)
+    if a.walk_bound:
+        for r in reports:
+            r["walk_bound"] = bound_rows(r["workload"], r["query"], a.candidates, a.lanes,
+                                         a.rounds, a.walkers)
     if a.json:
         print(json.dumps(reports, indent=1))
     else:
@@ -557,6 +687,8 @@ def main():
                 show_tree(r["walk_tree"], a.lanes)
             if a.walk_aim:
                 show_aim(r["walk_aim"], a.lanes)
+            if a.walk_bound:
+                show_bound(r["walk_bound"], a.lanes)
 
 
 if __name__ == "__main__":

@@ -1,0 +1,35 @@
+"""Device time per round of mg_walk_bound beside mg_walk_aim on the same
+program, starts and XOR-only table (aim_cases `bytes`), in one run: aim, bound,
+aim alternating.  Prints median, min and max of kernel_ms / rounds."""
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+import numpy as np                                                   # noqa: E402
+import aim_cases as AC                                               # noqa: E402
+from mythril_amd import repair as RP                                 # noqa: E402
+from mythril_amd.engine import default_leafgen, get_engine           # noqa: E402
+
+name = "bytes"
+prog, T, A = AC.program(name), AC.trees(name), AC.aims(name)
+n_roots = len(AC.case(name)[0])
+B = RP.bounds_of_aims(A, n_roots, T.n_atoms)
+eng = get_engine(0, nreg=16)
+lp = eng.load(prog, default_leafgen(prog), prog_seed=0)
+for walkers in (1, 16):
+    starts = AC.starts(name, walkers)
+    aim = lambda: eng.walk_aim(lp, starts, n_roots, T, A, AC.SEED, 4096, 64)
+    bound = lambda: eng.walk_bound(lp, starts, n_roots, T, B, AC.SEED, 4096, 64)
+    a, b = aim(), bound()                                            # warm up, and the same walk
+    assert np.array_equal(a.leaves, b.leaves) and np.array_equal(a.trace, b.trace)
+    assert a.rounds == b.rounds
+    runs = {"aim_1": [], "bound": [], "aim_2": []}
+    for _ in range(40):
+        for key, fn in (("aim_1", aim), ("bound", bound), ("aim_2", aim)):
+            res = fn()
+            runs[key].append(res.kernel_ms / res.rounds)
+    for key, v in runs.items():
+        print("walkers %2d lanes 4096 rounds %d x40  %-6s ms/round: median %.4f min %.4f max %.4f"
+              % (walkers, a.rounds, key, statistics.median(v), min(v), max(v)))
