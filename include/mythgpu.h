@@ -409,6 +409,68 @@ int mg_walk_bound_mutate_host(const mg_leafgen* leaves, uint32_t n_leaves, const
                               uint32_t lanes, uint32_t lane0, uint32_t n_lanes, uint32_t* out,
                               uint32_t* moves);
 
+/* Tree-scored walk with aims that write the table entry a UF application
+ * reads: mg_walk_bound whose pieces may name a UF slot,
+ * 1 << 31 | u, instead of a leaf.  Slot u is one application; the leaf its
+ * pieces act on is resolved per walker at every adoption from the adopted
+ * base and the adopted lane's n_urows U rows — the probes after the residual
+ * probes: the arguments' 256-bit chunks, then the computed keys of
+ * argument-keyed entries (mythril_amd/repair.py uf_table builds the tables,
+ * uf_resolve_ref and uf_mutate_ref are the specification, csrc/mg_walk_uf.h
+ * the code):
+ *   slots [n_slots][2]  function, first U row of the argument
+ *   funcs [n_funcs][3]  first candidate, candidates, key chunks (1 .. 4)
+ *   cands [n_cands][6]  value leaf or 0xFFFFFFFF, key kind (0 CONST: a row of
+ *                       ukeys, 1 LEAF: a leaf, 2 PROBE: a U row, 3 ALWAYS),
+ *                       one key word per chunk
+ *   ukeys [n_ukeys][8]  the chunks of the constant keys
+ * The destination of a slot is the value leaf of the first candidate of its
+ * function whose key equals the argument; an entry with a slot piece that has
+ * none is not live.  With no slot piece the walk is mg_walk_bound bit for
+ * bit.  Refused without a launch: what mg_walk_bound refuses for leaf pieces;
+ * more than 64 slots, 64 functions, 256 candidates or 128 U rows; a slot,
+ * function, candidate, key or U-row index out of range; chunks outside
+ * 1 .. 4; value leaves of one function of different widths; a slot piece
+ * outside that width; U rows the program does not have; a null table with a
+ * non-zero count. */
+int mg_walk_uf(mg_ctx* ctx, const mg_prog* prog,
+               const uint32_t* starts /*[walkers][n_leaves][8]*/, uint32_t walkers,
+               uint32_t n_roots, uint32_t mask_probe0, const uint32_t* roots /*[n_roots]*/,
+               uint32_t n_atoms, const uint32_t* atoms /*[n_atoms] or NULL*/,
+               const uint32_t* code /*[n_code] or NULL*/, uint32_t n_code, uint32_t n_resid,
+               const uint32_t* entries /*[n_entries][5] or NULL*/, uint32_t n_entries,
+               const uint32_t* pieces /*[n_pieces][4] or NULL*/, uint32_t n_pieces,
+               const uint32_t* fixed /*[n_entries][8] or NULL*/,
+               const uint32_t* slots, uint32_t n_slots, const uint32_t* funcs, uint32_t n_funcs,
+               const uint32_t* cands, uint32_t n_cands, const uint32_t* ukeys, uint32_t n_ukeys,
+               uint32_t n_urows, uint64_t seed, uint32_t lanes, uint32_t max_rounds,
+               uint32_t sync_every, uint32_t* out_leaves /*[walkers][n_leaves][8]*/,
+               uint32_t* out_nfail /*[walkers]*/, uint32_t* out_cost /*[walkers]*/,
+               uint32_t* out_rounds, uint32_t* trace /*[walkers][max_rounds][2] or NULL*/,
+               uint32_t* out_winner);
+/* Host-only (no GPU): the destinations of the slots under base and the U rows
+ * urows, as the adopt kernel of mg_walk_uf resolves them; MG_E_ARG for tables
+ * mg_walk_uf refuses. */
+int mg_walk_uf_resolve_host(const mg_leafgen* leaves, uint32_t n_leaves,
+                            const uint32_t* base /*[n_leaves][8]*/,
+                            const uint32_t* urows /*[n_urows][8]*/, uint32_t n_urows,
+                            const uint32_t* slots, uint32_t n_slots, const uint32_t* funcs,
+                            uint32_t n_funcs, const uint32_t* cands, uint32_t n_cands,
+                            const uint32_t* ukeys, uint32_t n_ukeys, uint32_t* dest /*[n_slots]*/);
+/* Host-only (no GPU): mg_walk_bound_mutate_host for mg_walk_uf's lane
+ * function; dest: the slots' destinations under the base. */
+int mg_walk_uf_mutate_host(const mg_leafgen* leaves, uint32_t n_leaves, const uint32_t* consts,
+                           uint32_t n_consts, const uint32_t* base /*[n_leaves][8]*/,
+                           const uint32_t* rvals /*[n_resid][8] or NULL*/, uint32_t n_resid,
+                           const uint32_t* mvals, uint32_t n_roots, uint32_t n_atoms,
+                           const uint32_t* entries, uint32_t n_entries, const uint32_t* pieces,
+                           uint32_t n_pieces, const uint32_t* fixed, const uint32_t* slots,
+                           uint32_t n_slots, const uint32_t* funcs, uint32_t n_funcs,
+                           const uint32_t* cands, uint32_t n_cands, const uint32_t* ukeys,
+                           uint32_t n_ukeys, uint32_t n_urows, const uint32_t* dest /*[n_slots]*/,
+                           uint64_t seed, uint32_t r, uint32_t lanes, uint32_t lane0,
+                           uint32_t n_lanes, uint32_t* out, uint32_t* moves);
+
 /* Corpus batches: many programs, one launch.  Device-pointer API for
  * resident benchmarking; stream is a hipStream_t (NULL = the context's own
  * stream, which the synchronous calls also use).

@@ -29,6 +29,7 @@
 #include "mg_walk_tree.h"
 #include "mg_walk_aim.h"
 #include "mg_walk_bound.h"
+#include "mg_walk_uf.h"
 
 // the interpreter of each register layout (mg_interp_asm.hip, one
 // translation unit per layout; mg_find_layout lists them)
@@ -132,6 +133,29 @@ hipError_t mg_launch_walk_bound_pick(const uint32_t* d_masks, const uint32_t* d_
                                      const uint32_t* d_fixed, uint32_t n_resid, uint32_t* d_rstate,
                                      uint32_t* d_mstate, uint32_t* d_lives, mg_walk_state* d_state,
                                      uint32_t* d_trace, hipStream_t stream);
+// the round of mg_walk_uf (mg_walk_uf.hip): mg_walk_bound's
+// with the walkers' slot destinations, U rows and the UF tables
+hipError_t mg_launch_walk_uf_round(const uint32_t* d_bases, const mg_leafgen* d_gen,
+                                   const uint32_t* d_consts, uint32_t n_leaves, uint64_t seed,
+                                   uint32_t r, uint32_t lanes, uint32_t walkers,
+                                   const uint32_t* d_entries, uint32_t n_entries,
+                                   const uint32_t* d_pieces, const uint32_t* d_fixed,
+                                   const uint32_t* d_rstate, uint32_t n_resid,
+                                   const uint32_t* d_lives, const uint32_t* d_dests,
+                                   uint32_t n_slots, uint32_t* d_leaves, hipStream_t stream);
+hipError_t mg_launch_walk_uf_pick(const uint32_t* d_masks, const uint32_t* d_amasks,
+                                  const uint32_t* d_resid, const uint32_t* d_urows,
+                                  const uint32_t* d_roots, const uint32_t* d_atoms,
+                                  const uint32_t* d_code, uint32_t lanes, uint32_t walkers,
+                                  uint32_t n_roots, uint32_t n_atoms, uint32_t* d_bases,
+                                  const mg_leafgen* d_gen, const uint32_t* d_consts,
+                                  uint32_t n_leaves, uint64_t seed, uint32_t r,
+                                  uint32_t max_rounds, const uint32_t* d_entries,
+                                  uint32_t n_entries, const uint32_t* d_pieces,
+                                  const uint32_t* d_fixed, uint32_t n_resid, const mg_uf_tables& uf,
+                                  uint32_t* d_rstate, uint32_t* d_mstate, uint32_t* d_ustate,
+                                  uint32_t* d_dests, uint32_t* d_lives, mg_walk_state* d_state,
+                                  uint32_t* d_trace, hipStream_t stream);
 
 
 struct mg_ctx {
@@ -1042,7 +1066,8 @@ static bool walk_table_ok(const uint32_t* table, uint32_t n_roots, uint32_t n_re
 // what scores a walk's neighbours: the residual table of mg_walk (no atoms, no
 // code) or the tree tables of mg_walk_tree (table: its root entries); aim: the
 // round of mg_walk_aim with its aim table (tree scoring); bound: the round of
-// mg_walk_bound, whose entries have 5 words and a fixed value each
+// mg_walk_bound, whose entries have 5 words and a fixed value each; uf: the
+// round of mg_walk_uf, mg_walk_bound's with the UF tables uft (host pointers)
 struct walk_scoring {
     const uint32_t* table;
     const uint32_t* atoms;
@@ -1057,6 +1082,8 @@ struct walk_scoring {
     uint32_t n_pieces;
     bool bound;
     const uint32_t* fixed;
+    bool uf;
+    mg_uf_tables uft;
 };
 
 // The scored walk.  Rounds are queued back to back;
@@ -1104,7 +1131,21 @@ static int walk_run(mg_ctx* ctx, const mg_prog* prog, const uint32_t* starts, ui
         return fail(ctx, MG_E_ARG, "walk: a table entry names an unknown kind or a residual "
                     "probe at or above %u", n_resid);
     }
-    if (sc.bound && !mg_walk_bound_ok(sc.entries, sc.n_entries, sc.pieces, sc.n_pieces, sc.fixed,
+    if (sc.uf) {
+        if (sc.uft.n_urows > prog->n_probes - mask_probe0 - n_mask - n_amask - n_resid)
+            return fail(ctx, MG_E_ARG, "walk_uf: %u U rows after %u residual probes outside the "
+                        "program's %u probes", sc.uft.n_urows, n_resid, prog->n_probes);
+        if (!mg_walk_uf_ok(sc.entries, sc.n_entries, sc.pieces, sc.n_pieces, sc.fixed,
+                           prog->leafgen.data(), prog->n_leaves, n_resid, n_roots, sc.n_atoms,
+                           sc.uft))
+            return fail(ctx, MG_E_ARG, "walk_uf: malformed tables (mg_walk_uf_ok: what "
+                        "mg_walk_bound_ok checks for leaf pieces; at most %u slots, %u candidates "
+                        "and %u U rows, null tables, slot, function, candidate, key and U-row "
+                        "indices, 1..%u key chunks, one width per function's value leaves, a "
+                        "slot piece outside it)", MG_UF_MAX_SLOTS, MG_UF_MAX_CANDS,
+                        MG_UF_MAX_ROWS, MG_UF_MAX_CHUNKS);
+    }
+    if (sc.bound && !sc.uf && !mg_walk_bound_ok(sc.entries, sc.n_entries, sc.pieces, sc.n_pieces, sc.fixed,
                                       prog->leafgen.data(), prog->n_leaves, n_resid, n_roots,
                                       sc.n_atoms))
         return fail(ctx, MG_E_ARG, "walk_bound: malformed aim table (mg_walk_bound_ok: what "
@@ -1140,7 +1181,13 @@ static int walk_run(mg_ctx* ctx, const mg_prog* prog, const uint32_t* starts, ui
                  live_b = sc.aim ? (size_t)walkers * MG_AIM_LIVE_WORDS * 4 : 0,
                  fixed_b = sc.bound ? (size_t)sc.n_entries * 32 : 0,
                  mstate_b = sc.bound ? (size_t)walkers * 4 * (MG_BOUND_MASK_WORDS(n_roots) +
-                                                              MG_BOUND_MASK_WORDS(sc.n_atoms)) : 0;
+                                                              MG_BOUND_MASK_WORDS(sc.n_atoms)) : 0,
+                 slot_b = sc.uf ? (size_t)sc.uft.n_slots * 8 : 0,
+                 func_b = sc.uf ? (size_t)sc.uft.n_funcs * 12 : 0,
+                 cand_b = sc.uf ? (size_t)sc.uft.n_cands * 24 : 0,
+                 ukey_b = sc.uf ? (size_t)sc.uft.n_ukeys * 32 : 0,
+                 ustate_b = sc.uf ? (size_t)walkers * sc.uft.n_urows * 32 : 0,
+                 dest_b = sc.uf ? (size_t)walkers * sc.uft.n_slots * 4 : 0;
     const size_t off_base = align(state_b), off_gen = off_base + align(base_b),
                  off_table = off_gen + align(gen_b), off_trace = off_table + align(table_b),
                  off_root = off_trace + align(trace_b), off_leaf = off_root + align(root_b),
@@ -1148,7 +1195,10 @@ static int walk_run(mg_ctx* ctx, const mg_prog* prog, const uint32_t* starts, ui
                  off_code = off_atom + align(atom_b), off_entry = off_code + align(code_b),
                  off_piece = off_entry + align(entry_b), off_rstate = off_piece + align(piece_b),
                  off_live = off_rstate + align(rstate_b), off_fixed = off_live + align(live_b),
-                 off_mstate = off_fixed + align(fixed_b), bytes = off_mstate + align(mstate_b);
+                 off_mstate = off_fixed + align(fixed_b), off_slot = off_mstate + align(mstate_b),
+                 off_func = off_slot + align(slot_b), off_cand = off_func + align(func_b),
+                 off_ukey = off_cand + align(cand_b), off_ustate = off_ukey + align(ukey_b),
+                 off_dest = off_ustate + align(ustate_b), bytes = off_dest + align(dest_b);
     void* ws;
     int rc = workspace(ctx, bytes + 256, &ws);
     if (rc) return rc;
@@ -1168,6 +1218,14 @@ static int walk_run(mg_ctx* ctx, const mg_prog* prog, const uint32_t* starts, ui
     uint32_t* d_lives = (uint32_t*)(w + off_live);
     uint32_t* d_fixed = (uint32_t*)(w + off_fixed);
     uint32_t* d_mstate = (uint32_t*)(w + off_mstate);
+    uint32_t* d_ustate = (uint32_t*)(w + off_ustate);
+    uint32_t* d_dests = (uint32_t*)(w + off_dest);
+    // the UF tables as the kernels read them: device pointers, host counts
+    mg_uf_tables d_uf = sc.uft;
+    d_uf.slots = (const uint32_t*)(w + off_slot);
+    d_uf.funcs = (const uint32_t*)(w + off_func);
+    d_uf.cands = (const uint32_t*)(w + off_cand);
+    d_uf.ukeys = (const uint32_t*)(w + off_ukey);
     HIPCHECK(ctx, hipMemsetAsync(d_state, 0xFF, state_b, ctx->stream));
     HIPCHECK(ctx, hipMemsetAsync(d_trace, 0, trace_b, ctx->stream));
     HIPCHECK(ctx, hipMemcpyAsync(d_bases, starts, base_b, hipMemcpyHostToDevice, ctx->stream));
@@ -1192,6 +1250,20 @@ static int walk_run(mg_ctx* ctx, const mg_prog* prog, const uint32_t* starts, ui
         HIPCHECK(ctx, hipMemcpyAsync(d_fixed, sc.fixed, fixed_b, hipMemcpyHostToDevice,
                                      ctx->stream));
     if (mstate_b) HIPCHECK(ctx, hipMemsetAsync(d_mstate, 0, mstate_b, ctx->stream));
+    if (slot_b)
+        HIPCHECK(ctx, hipMemcpyAsync(w + off_slot, sc.uft.slots, slot_b, hipMemcpyHostToDevice,
+                                     ctx->stream));
+    if (func_b)
+        HIPCHECK(ctx, hipMemcpyAsync(w + off_func, sc.uft.funcs, func_b, hipMemcpyHostToDevice,
+                                     ctx->stream));
+    if (cand_b)
+        HIPCHECK(ctx, hipMemcpyAsync(w + off_cand, sc.uft.cands, cand_b, hipMemcpyHostToDevice,
+                                     ctx->stream));
+    if (ukey_b)
+        HIPCHECK(ctx, hipMemcpyAsync(w + off_ukey, sc.uft.ukeys, ukey_b, hipMemcpyHostToDevice,
+                                     ctx->stream));
+    if (ustate_b) HIPCHECK(ctx, hipMemsetAsync(d_ustate, 0, ustate_b, ctx->stream));
+    if (dest_b) HIPCHECK(ctx, hipMemsetAsync(d_dests, 0xFF, dest_b, ctx->stream));
     mg_run run = empty_run();
     run.leaves = d_leaves;
     run.root_bits = (uint64_t*)(w + off_root);
@@ -1202,6 +1274,7 @@ static int walk_run(mg_ctx* ctx, const mg_prog* prog, const uint32_t* starts, ui
     const uint32_t* d_masks = d_probes + (size_t)mask_probe0 * 8 * total;
     const uint32_t* d_amasks = d_masks + (size_t)n_mask * 8 * total;
     const uint32_t* d_resid = d_amasks + (size_t)n_amask * 8 * total;
+    const uint32_t* d_urows = d_resid + (size_t)n_resid * 8 * total;
     const uint32_t* d_consts = prog->h_desc.consts;       // the first n_consts entries: as loaded
     std::vector<mg_walk_state> h_state(walkers);
     bool done = false;
@@ -1210,7 +1283,13 @@ static int walk_run(mg_ctx* ctx, const mg_prog* prog, const uint32_t* starts, ui
     while (r < max_rounds && !done) {
         const uint32_t stop = max_rounds - r < sync_every ? max_rounds : r + sync_every;
         for (; r < stop; ++r) {
-            if (sc.bound)
+            if (sc.uf)
+                HIPCHECK(ctx, mg_launch_walk_uf_round(d_bases, d_gen, d_consts, n_leaves, seed, r,
+                                                      lanes, walkers, d_entries, sc.n_entries,
+                                                      d_pieces, d_fixed, d_rstate, n_resid,
+                                                      d_lives, d_dests, d_uf.n_slots, d_leaves,
+                                                      ctx->stream));
+            else if (sc.bound)
                 HIPCHECK(ctx, mg_launch_walk_bound_round(d_bases, d_gen, d_consts, n_leaves, seed,
                                                          r, lanes, walkers, d_entries,
                                                          sc.n_entries, d_pieces, d_fixed, d_rstate,
@@ -1224,7 +1303,15 @@ static int walk_run(mg_ctx* ctx, const mg_prog* prog, const uint32_t* starts, ui
                 HIPCHECK(ctx, mg_launch_walk_round(d_bases, d_gen, d_consts, n_leaves, seed, r,
                                                    lanes, walkers, d_leaves, ctx->stream));
             HIPCHECK(ctx, launch(ctx, 0, prog->d_desc, 1, run, prog->n_lds, ctx->stream));
-            if (sc.bound)
+            if (sc.uf)
+                HIPCHECK(ctx, mg_launch_walk_uf_pick(d_masks, d_amasks, d_resid, d_urows, d_table,
+                                                     d_atoms, d_code, lanes, walkers, n_roots,
+                                                     sc.n_atoms, d_bases, d_gen, d_consts,
+                                                     n_leaves, seed, r, max_rounds, d_entries,
+                                                     sc.n_entries, d_pieces, d_fixed, n_resid,
+                                                     d_uf, d_rstate, d_mstate, d_ustate, d_dests,
+                                                     d_lives, d_state, d_trace, ctx->stream));
+            else if (sc.bound)
                 HIPCHECK(ctx, mg_launch_walk_bound_pick(d_masks, d_amasks, d_resid, d_table,
                                                         d_atoms, d_code, lanes, walkers, n_roots,
                                                         sc.n_atoms, d_bases, d_gen, d_consts,
@@ -1333,6 +1420,29 @@ int mg_walk_bound(mg_ctx* ctx, const mg_prog* prog, const uint32_t* starts, uint
                     out_winner);
 }
 
+// The same with aims that write the table entry a UF application reads
+// (DESIGN.md §3.14): mg_walk_bound with the kernels of mg_walk_uf.hip, the UF
+// tables of mg_walk_uf.h and n_urows U rows after the residual probes.
+int mg_walk_uf(mg_ctx* ctx, const mg_prog* prog, const uint32_t* starts, uint32_t walkers,
+               uint32_t n_roots, uint32_t mask_probe0, const uint32_t* roots, uint32_t n_atoms,
+               const uint32_t* atoms, const uint32_t* code, uint32_t n_code, uint32_t n_resid,
+               const uint32_t* entries, uint32_t n_entries, const uint32_t* pieces,
+               uint32_t n_pieces, const uint32_t* fixed, const uint32_t* slots, uint32_t n_slots,
+               const uint32_t* funcs, uint32_t n_funcs, const uint32_t* cands, uint32_t n_cands,
+               const uint32_t* ukeys, uint32_t n_ukeys, uint32_t n_urows, uint64_t seed,
+               uint32_t lanes, uint32_t max_rounds, uint32_t sync_every, uint32_t* out_leaves,
+               uint32_t* out_nfail, uint32_t* out_cost, uint32_t* out_rounds, uint32_t* trace,
+               uint32_t* out_winner) {
+    if (ctx) HIPCHECK(ctx, hipSetDevice(ctx->device));
+    const walk_scoring sc = {roots, atoms, n_atoms, code, n_code, true, true,
+                             entries, n_entries, pieces, n_pieces, true, fixed, true,
+                             {slots, n_slots, funcs, n_funcs, cands, n_cands, ukeys, n_ukeys,
+                              n_urows}};
+    return walk_run(ctx, prog, starts, walkers, n_roots, mask_probe0, sc, n_resid, seed, lanes,
+                    max_rounds, sync_every, out_leaves, out_nfail, out_cost, out_rounds, trace,
+                    out_winner);
+}
+
 // Host only: lanes lane0 .. lane0 + n_lanes - 1 of round r of the lane
 // function of mg_walk_aim.h, as the mutate kernel writes them.
 int mg_walk_aim_mutate_host(const mg_leafgen* leaves, uint32_t n_leaves, const uint32_t* consts,
@@ -1404,6 +1514,78 @@ int mg_walk_bound_mutate_host(const mg_leafgen* leaves, uint32_t n_leaves, const
         const uint32_t e = mg_walk_bound_lane(base, leaves, consts, n_leaves, seed, r, lane0 + a,
                                               lanes, entries, pieces, fixed, rvals, live, out + a,
                                               n_lanes, &mv);
+        if (moves) {
+            moves[5 * (size_t)a] = mv.n;
+            moves[5 * (size_t)a + 1] = mv.kind[0] | mv.kind[1] << 8;
+            moves[5 * (size_t)a + 2] = mv.leaf[0];
+            moves[5 * (size_t)a + 3] = mv.leaf[1];
+            moves[5 * (size_t)a + 4] = e;
+        }
+    }
+    return MG_OK;
+}
+
+// Host only: the destinations of the slots (mg_walk_uf_resolve of
+// mg_walk_uf.h) under base ([n_leaves][8]) and U rows urows ([n_urows][8]),
+// as the adopt kernel computes them; gen: the leaf table the validator reads.
+int mg_walk_uf_resolve_host(const mg_leafgen* leaves, uint32_t n_leaves, const uint32_t* base,
+                            const uint32_t* urows, uint32_t n_urows, const uint32_t* slots,
+                            uint32_t n_slots, const uint32_t* funcs, uint32_t n_funcs,
+                            const uint32_t* cands, uint32_t n_cands, const uint32_t* ukeys,
+                            uint32_t n_ukeys, uint32_t* dest) {
+    if (!leaves || !base || n_leaves == 0 || (n_urows && !urows) || (n_slots && !dest))
+        return MG_E_ARG;
+    const mg_uf_tables t = {slots, n_slots, funcs, n_funcs, cands, n_cands, ukeys, n_ukeys,
+                            n_urows};
+    if (!mg_walk_uf_ok(nullptr, 0, nullptr, 0, nullptr, leaves, n_leaves, 0, 0, 0, t))
+        return MG_E_ARG;
+    for (uint32_t u = 0; u < n_slots; ++u)
+        dest[u] = mg_walk_uf_resolve(slots, funcs, cands, ukeys, u, base, urows, 1);
+    return MG_OK;
+}
+
+// Host only: mg_walk_bound_mutate_host of the lane function of mg_walk_uf.h;
+// dest: the destinations of the n_slots slots under the base (any value when
+// rvals or mvals is null: round 0).
+int mg_walk_uf_mutate_host(const mg_leafgen* leaves, uint32_t n_leaves, const uint32_t* consts,
+                           uint32_t n_consts, const uint32_t* base, const uint32_t* rvals,
+                           uint32_t n_resid, const uint32_t* mvals, uint32_t n_roots,
+                           uint32_t n_atoms, const uint32_t* entries, uint32_t n_entries,
+                           const uint32_t* pieces, uint32_t n_pieces, const uint32_t* fixed,
+                           const uint32_t* slots, uint32_t n_slots, const uint32_t* funcs,
+                           uint32_t n_funcs, const uint32_t* cands, uint32_t n_cands,
+                           const uint32_t* ukeys, uint32_t n_ukeys, uint32_t n_urows,
+                           const uint32_t* dest, uint64_t seed, uint32_t r, uint32_t lanes,
+                           uint32_t lane0, uint32_t n_lanes, uint32_t* out, uint32_t* moves) {
+    if (!leaves || !base || !out || (n_consts && !consts) || n_leaves == 0) return MG_E_ARG;
+    if (lanes < 1 || lanes > MG_REPAIR_MAX_LANES || r >= MG_REPAIR_MAX_ROUNDS) return MG_E_ARG;
+    if (lane0 > lanes || n_lanes > lanes - lane0) return MG_E_ARG;
+    if (n_roots > MG_WT_MAX_ROOTS || n_atoms > MG_WT_MAX_ATOMS) return MG_E_ARG;
+    if (n_slots && !dest) return MG_E_ARG;
+    for (uint32_t i = 0; i < n_leaves; ++i) {
+        if (leaves[i].width < 1 || leaves[i].width > MG_MAX_WIDTH) return MG_E_ARG;
+        if ((uint64_t)leaves[i].pool_off + leaves[i].pool_n > n_consts) return MG_E_ARG;
+        uint32_t v[8];
+        memcpy(v, base + (size_t)i * 8, 32);
+        mg_repair_mask(v, leaves[i].width);
+        if (memcmp(v, base + (size_t)i * 8, 32)) return MG_E_ARG;     // a base beyond its width
+    }
+    const mg_uf_tables t = {slots, n_slots, funcs, n_funcs, cands, n_cands, ukeys, n_ukeys,
+                            n_urows};
+    if (!mg_walk_uf_ok(entries, n_entries, pieces, n_pieces, fixed, leaves, n_leaves, n_resid,
+                       n_roots, n_atoms, t))
+        return MG_E_ARG;
+    for (uint32_t u = 0; u < n_slots; ++u)               // a destination is a leaf or none
+        if (dest[u] != MG_AIM_NONE && dest[u] >= n_leaves) return MG_E_ARG;
+    uint32_t live[MG_AIM_LIVE_WORDS];
+    mg_walk_uf_live(entries, n_entries, pieces, rvals, mvals, MG_BOUND_MASK_WORDS(n_roots), dest,
+                    live);
+    for (uint32_t a = 0; a < n_lanes; ++a) {
+        for (size_t i = 0; i < (size_t)n_leaves * 8; ++i) out[i * n_lanes + a] = base[i];
+        mg_repair_moves mv;
+        const uint32_t e = mg_walk_uf_lane(base, leaves, consts, n_leaves, seed, r, lane0 + a,
+                                           lanes, entries, pieces, fixed, rvals, live, dest,
+                                           out + a, n_lanes, &mv);
         if (moves) {
             moves[5 * (size_t)a] = mv.n;
             moves[5 * (size_t)a + 1] = mv.kind[0] | mv.kind[1] << 8;

@@ -286,7 +286,7 @@ class WalkResult:
 
 def walk_ref(values_fn: Callable, leafgen, consts, starts, table, seed: int, lanes: int = 4096,
              max_rounds: int = 64, sync_every: int = 8, score: Optional[Callable] = None,
-             aims=None, bounds=None) -> WalkResult:
+             aims=None, bounds=None, ufs=None) -> WalkResult:
     """The whole loop as ``mg_walk`` runs it.  ``values_fn`` maps an SoA leaf
     array ``(n_leaves, 8, n)`` to ``(bits (n, n_roots) bool, resid (n_resid,
     8, n) u32)``: the verdicts and the residual values.  Walker w moves under
@@ -305,7 +305,13 @@ def walk_ref(values_fn: Callable, leafgen, consts, starts, table, seed: int, lan
     ``bounds``: the table of ``mg_walk_bound`` (:func:`bound_table`) instead:
     the neighbours are those of :func:`bound_mutate_ref` under the adopted
     lane's residual values, root bits (the first element of what ``values_fn``
-    returns) and atom bits (the second of three; none without tree scoring)."""
+    returns) and atom bits (the second of three; none without tree scoring).
+
+    ``ufs``: with ``bounds``, the tables of ``mg_walk_uf`` (:func:`uf_table`):
+    ``values_fn`` returns ``(bits, abits, resid, urows)``, the walker keeps the
+    adopted lane's U rows ``urows[:, :, lane]`` and resolves its slots after
+    each adoption (:func:`uf_resolve_ref` on the new base), and the neighbours
+    are those of :func:`uf_mutate_ref`."""
     bases = np.ascontiguousarray(starts, dtype=np.uint32).copy()
     walkers = bases.shape[0]
     if not 1 <= walkers <= MAX_WALKERS or bases.shape[2:] != (8,):
@@ -318,7 +324,11 @@ def walk_ref(values_fn: Callable, leafgen, consts, starts, table, seed: int, lan
     while r < max_rounds and not any(k is not None and k[0] == 0 for k in keys):
         stop = max_rounds if max_rounds - r < sync_every else r + sync_every
         while r < stop:
-            if bounds is not None:
+            if ufs is not None:
+                nb = np.concatenate([uf_mutate_ref(leafgen, consts, bases[w], rvals[w], bounds,
+                                                   seed ^ (w * CW & M64), r, lanes)
+                                     for w in range(walkers)], axis=2)
+            elif bounds is not None:
                 nb = np.concatenate([bound_mutate_ref(leafgen, consts, bases[w], rvals[w], bounds,
                                                       seed ^ (w * CW & M64), r, lanes)
                                      for w in range(walkers)], axis=2)
@@ -330,6 +340,9 @@ def walk_ref(values_fn: Callable, leafgen, consts, starts, table, seed: int, lan
                                                     seed ^ (w * CW & M64), r, lanes)
                                      for w in range(walkers)], axis=2)
             values = values_fn(nb)
+            urows = None
+            if ufs is not None:
+                values, urows = values[:3], values[3]
             if score is None:
                 nfail, cost = _score_bits(values[0], values[1], table)
             else:
@@ -346,6 +359,8 @@ def walk_ref(values_fn: Callable, leafgen, consts, starts, table, seed: int, lan
                                     np.array(values[0][at], dtype=bool),
                                     np.array(values[1][at] if len(values) == 3 else [],
                                              dtype=bool))
+                        if ufs is not None:
+                            rvals[w] += (uf_resolve_ref(bases[w], urows[:, :, at], ufs),)
                     elif aims is not None:
                         rvals[w] = np.ascontiguousarray(values[-1][:, :, w * lanes + lane])
                 trace[w, r] = key
@@ -794,20 +809,23 @@ def _fold_key(i, subst) -> Optional[int]:
     return None
 
 
-def aim_pieces(t, program) -> Optional[list]:
+def aim_pieces(t, program, _slots=None) -> Optional[list]:
     """The pieces ``[(leaf, leaf_bit, value_bit, len)]`` of the bit-vector
     term ``t`` as a destination, ``value_bit`` relative to
     ``t``'s bit 0; None when ``t`` does not resolve.  A numeral resolves to no
     piece."""
-    side = _resolve_side(t, program)
+    side = _resolve_side(t, program, _slots)
     return None if side is None else side[0]
 
 
-def _resolve_side(t, program) -> Optional[tuple]:
+def _resolve_side(t, program, slots=None) -> Optional[tuple]:
     """``(pieces, fixed)`` of ``t`` by the rules of :func:`aim_pieces`;
     ``fixed``: the bits of ``t`` that numerals give (a numeral, or a numeral
     operand of a concat, at its offset; the numeral arm of an ``ite`` gives
-    none), as an int."""
+    none), as an int.  ``slots`` ({apply node id: slot}, :func:`uf_table`
+    alone passes it): an application with a slot u is the one piece ``(UF_SLOT
+    | u, 0, 0, width)``, and one at a numeral argument that is a constant key
+    of its function is that entry's ``cval`` leaf."""
     leaves = {(l.kind, l.source, l.entry, l.chunk): i for i, l in enumerate(program.leaves)}
     subst = getattr(program.presets, "subst", None) or {}
 
@@ -866,22 +884,48 @@ def _resolve_side(t, program) -> Optional[tuple]:
             if key is None or key not in ckeys:
                 return None
             return leafy(cells("cval", name, ckeys.index(key), t.width))
+        if t.op == "apply" and slots is not None:
+            if t.id in slots:
+                return [(UF_SLOT | slots[t.id], 0, 0, t.width)], 0
+            name, key = t.params[0], _fold_key(t.args[0], subst)
+            ckeys = list(program.table_ckeys.get(name, []))
+            if key is None or key not in ckeys:
+                return None
+            return leafy(cells("cval", name, ckeys.index(key), t.width))
         return None
     return go(t)
 
 
-def aim_refusal(t, program) -> Optional[str]:
+def aim_refusal(t, program, ufs=None) -> Optional[str]:
     """Why :func:`aim_pieces` does not resolve ``t`` (the first subterm no
-    rule takes, with the rule that refused it), None when it resolves."""
-    if aim_pieces(t, program) is not None:
+    rule takes, with the rule that refused it), None when it resolves.
+    ``ufs``: the tables of :func:`uf_table`; an ``apply`` then resolves where
+    it has a slot, and else the reason says why it got none."""
+    slots = None if ufs is None else ufs.slot_of
+    if aim_pieces(t, program, slots) is not None:
         return None
     if t.op in ("concat", "extract", "zero_extend"):
-        return next(r for r in (aim_refusal(a, program) for a in t.args) if r)
+        return next(r for r in (aim_refusal(a, program, ufs) for a in t.args) if r)
     if t.op == "ite" and t.is_bv():
         _, x, y = t.args
         if x.op == "bvnum" or y.op == "bvnum":
-            return aim_refusal(y if x.op == "bvnum" else x, program)
+            return aim_refusal(y if x.op == "bvnum" else x, program, ufs)
         return "ite: neither arm is a numeral"
+    if t.op == "apply" and ufs is not None:
+        name = t.params[0]
+        if t.width > RESIDUAL_BITS:
+            return "apply(%s): the range (%d bits) is wider than %d" % (name, t.width,
+                                                                        RESIDUAL_BITS)
+        if t.params[1] > RESIDUAL_BITS * UF_MAX_CHUNKS:
+            return "apply(%s): the domain (%d bits) is wider than %d" % (
+                name, t.params[1], RESIDUAL_BITS * UF_MAX_CHUNKS)
+        if t.args[0].op == "bvnum":
+            return "apply(%s, %d): the program does not read that constant key" % (
+                name, t.args[0].params[0])
+        if t.id in ufs.underived:
+            return "apply(%s): every candidate's value is a derived leaf" % name
+        return "apply(%s): over the cap of %d slots, %d candidates or %d U rows" % (
+            name, UF_MAX_SLOTS, UF_MAX_CANDS, UF_MAX_ROWS)
     if t.op == "var":
         return "variable %s is not a leaf of the program" % t.params[0]
     if t.op == "select" and t.args[0].op == "array":
@@ -896,7 +940,7 @@ def aim_refusal(t, program) -> Optional[str]:
     return "%s is not a destination" % t.op
 
 
-def aim_table(trees: Trees, program) -> Aims:
+def aim_table(trees: Trees, program, _slots=None) -> Aims:
     """The aim table of ``trees`` on the compiled ``program`` (DESIGN.md
     §3.12): for every residual probe ``bvxor(a, b)`` that a HAMMING atom or a
     simple HAMMING root of ``trees`` reads, in probe order, one entry per side
@@ -913,7 +957,7 @@ def aim_table(trees: Trees, program) -> Aims:
         if node.op != "bvxor" or len(node.args) != 2:
             continue
         for side, t in enumerate(node.args):
-            ps = aim_pieces(t, program)
+            ps = aim_pieces(t, program, _slots)
             if not ps or len(ps) > AIM_MAX_PIECES or any(l in program.derived for l, *_ in ps):
                 continue
             if len(rows) < AIM_MAX_ENTRIES:
@@ -1068,18 +1112,18 @@ def _order_probe(trees: Trees, lo, hi) -> Optional[int]:
     return None
 
 
-def bound_side(t, program) -> Optional[tuple]:
+def bound_side(t, program, _slots=None) -> Optional[tuple]:
     """``(pieces, fixed)`` of one side of an order as a destination (DESIGN.md
     §3.13), or None: the side does not resolve, has no piece or more than 64,
     or one of its leaves is derived by the program."""
-    side = _resolve_side(t, program)
+    side = _resolve_side(t, program, _slots)
     if side is None or not side[0] or len(side[0]) > AIM_MAX_PIECES or \
             any(l in program.derived for l, *_ in side[0]):
         return None
     return side
 
 
-def bound_table(constraints: Sequence, trees: Trees, program) -> Bounds:
+def bound_table(constraints: Sequence, trees: Trees, program, _slots=None) -> Bounds:
     """The table of ``mg_walk_bound``: the entries of
     :func:`aim_table` as XOR entries, in its order; then, for every MAGNITUDE
     atom of ``trees`` in atom order and after them for every simple MAGNITUDE
@@ -1088,7 +1132,7 @@ def bound_table(constraints: Sequence, trees: Trees, program) -> Bounds:
     and one for side ``hi`` (HIGH, HIGH_STRICT) where :func:`bound_side`
     resolves it.  At most 256 entries, the first ones."""
     constraints = list(constraints)
-    aims = aim_table(trees, program)
+    aims = aim_table(trees, program, _slots)
     rows = [(int(p), aims.of(e), BOUND_XOR, 0, 0) for e, (p, _, _) in enumerate(aims.entries)]
     sides = list(aims.sides)
 
@@ -1101,7 +1145,7 @@ def bound_table(constraints: Sequence, trees: Trees, program) -> Bounds:
         if p is None:
             return
         for side, t in enumerate((lo, hi)):
-            res = bound_side(t, program)
+            res = bound_side(t, program, _slots)
             if res is not None:
                 rows.append((p, res[0], (BOUND_LOW, BOUND_HIGH)[side] + int(strict), truth, res[1]))
                 sides.append(side)
@@ -1201,6 +1245,320 @@ def bound_mutate_ref(leafgen, consts, base, state, bounds: Bounds, seed: int, r:
 
 
 # ---------------------------------------------------------------------------
+# aims for UF outputs: a piece may name a UF slot, whose
+# destination leaf is resolved at every adoption
+# ---------------------------------------------------------------------------
+
+# the constants of csrc/mg_walk_uf.h
+UF_SLOT = 1 << 31
+UF_MAX_SLOTS, UF_MAX_FUNCS, UF_MAX_CANDS, UF_MAX_ROWS, UF_MAX_CHUNKS = 64, 64, 256, 128, 4
+UF_CONST, UF_LEAF, UF_PROBE, UF_ALWAYS = range(4)
+
+
+@dataclass
+class Ufs:
+    """The UF tables of ``mg_walk_uf`` (``csrc/mg_walk_uf.h``)."""
+    slots: np.ndarray          # (n_slots, 2) u32: function, first U row of the argument
+    funcs: np.ndarray          # (n_funcs, 3) u32: first candidate, candidates, key chunks
+    cands: np.ndarray          # (n_cands, 6) u32: value leaf | AIM_NONE, key kind, key words
+    ukeys: np.ndarray          # (n_ukeys, 8) u32: the chunks of the constant keys
+    n_urows: int = 0           # argument rows, then kept key rows
+    n_arg_rows: int = 0        # the argument probes the walk view keeps (the first ones)
+    keep: tuple = ()           # probe indices of the kept entry keys (uf_view)
+    apps: tuple = ()           # per slot its ``apply`` node
+    names: tuple = ()          # per function its name
+    slot_of: Optional[dict] = None      # apply node id -> slot
+    underived: frozenset = frozenset()  # apply node ids refused because every value is derived
+
+    def __len__(self) -> int:
+        return len(self.slots)
+
+
+def make_ufs(slots=(), funcs=(), cands=(), ukeys=(), n_urows: int = 0) -> Ufs:
+    """``Ufs`` of plain rows (``ukeys``: ints or 8-limb rows)."""
+    keys = [_u256(k) if isinstance(k, int) else k for k in ukeys]
+    return Ufs(np.array(slots, dtype=np.uint32).reshape(-1, 2),
+               np.array(funcs, dtype=np.uint32).reshape(-1, 3),
+               np.array(cands, dtype=np.uint32).reshape(-1, 6),
+               np.array(keys, dtype=np.uint32).reshape(-1, 8), n_urows, n_urows)
+
+
+def no_ufs() -> Ufs:
+    return make_ufs()
+
+
+def _read_probes(trees: Trees) -> list:
+    """The residual probes a HAMMING or MAGNITUDE atom or simple root of
+    ``trees`` reads, in probe order."""
+    used = set()
+    for e in list(trees.atoms) + [r for r in trees.roots if not int(r) & WT_TREE]:
+        if int(e) >> 16 in (HAMMING, MAGNITUDE):
+            used.add(int(e) & 0xFFFF)
+    return sorted(used)
+
+
+def _arg_chunks(t) -> list:
+    """The argument of the application ``t`` as 256-bit chunks, low first."""
+    a = t.args[0]
+    return [_chunk(a, min(lo + RESIDUAL_BITS, a.width) - 1, lo)
+            for lo in range(0, a.width, RESIDUAL_BITS)]
+
+
+def uf_probes(trees: Trees) -> tuple:
+    """``(apps, probes)`` from the nodes alone: the ``apply``
+    nodes met on either side of every residual probe ``bvxor(a, b)`` /
+    ``bvsub(lo, hi)`` that a HAMMING or MAGNITUDE atom or simple root of
+    ``trees`` reads, by the destination rules of :func:`aim_pieces` (through
+    ``concat``, ``extract``, ``zero_extend`` and an ``ite`` with a numeral
+    arm), distinct by id in first-seen order; kept where the range is at most
+    256 bits, the domain at most 1024 (4 chunks) and the argument no numeral;
+    at most 64, the first ones.  ``probes``: their arguments cut into 256-bit
+    chunks, low chunk first, to compile as user probes after the residuals."""
+    apps, seen = [], set()
+
+    def go(t):
+        if t.op == "apply":
+            if t.id not in seen:
+                seen.add(t.id)
+                apps.append(t)
+        elif t.op == "concat":
+            for a in t.args:
+                go(a)
+        elif t.op in ("extract", "zero_extend"):
+            go(t.args[0])
+        elif t.op == "ite" and t.is_bv():
+            _, x, y = t.args
+            if x.op == "bvnum" or y.op == "bvnum":
+                go(y if x.op == "bvnum" else x)
+
+    for p in _read_probes(trees):
+        node = trees.probes[p]
+        if node.op in ("bvxor", "bvsub") and len(node.args) == 2:
+            for t in node.args:
+                go(t)
+    apps = [t for t in apps if t.width <= RESIDUAL_BITS
+            and t.params[1] <= RESIDUAL_BITS * UF_MAX_CHUNKS and t.args[0].op != "bvnum"]
+    apps = apps[:UF_MAX_SLOTS]
+    return apps, [c for t in apps for c in _arg_chunks(t)]
+
+
+def uf_view(program, n_user: int, keep: Sequence[int]):
+    """``census.census_view`` extended: ``program`` with its first ``n_user``
+    probes kept, the ``OUT`` records of the probe indices in ``keep``
+    renumbered to ``n_user``, ``n_user + 1``, .. and every other ``OUT``
+    replaced by ``NOP``."""
+    import copy
+    from . import irdefs as I
+    keep = [int(k) for k in keep]
+    if not 1 <= n_user <= program.n_probes or any(not n_user <= k < program.n_probes for k in keep) \
+            or len(set(keep)) != len(keep):
+        raise ValueError("n_user %d or a kept probe outside the program's %d probes" % (
+            n_user, program.n_probes))
+    code = np.array(program.code, dtype=np.uint32, copy=True)
+    out = (code[:, 0] & 0xFF) == I.OUT
+    where = {k: n_user + i for i, k in enumerate(keep)}
+    for i in np.flatnonzero(out & (code[:, 2] >= n_user)):
+        k = int(code[i, 2])
+        if k in where:
+            code[i, 2] = where[k]
+        else:
+            code[i] = (I.NOP, 0, 0, 0)
+    view = copy.copy(program)
+    view.code = code
+    view.n_probes = n_user + len(keep)
+    return view
+
+
+def uf_table(constraints: Sequence, trees: Trees, program, apps: Sequence) -> tuple:
+    """``(Bounds, Ufs)`` of ``mg_walk_uf`` on ``program``,
+    compiled with the argument probes of ``apps`` (:func:`uf_probes`) as its
+    last user probes.  Per function the candidates stand in the table's
+    precedence order: the ``table_ckeys`` entries (CONST keys, value leaf kind
+    ``cval``), then the leaf-keyed (eval form: LEAF keys) or argument-keyed
+    (solve form: PROBE keys, ``Program.entry_keys``) entries (value leaf kind
+    ``val``), then in eval form ``else`` (ALWAYS).  A candidate whose value
+    leaf the program derives keeps its place with value leaf ``AIM_NONE``.
+    An application all of whose candidates are so gets no slot; the later
+    slots are dropped, and with them the key rows of a function no slot is
+    left of, until there are at most 64 slots, 256 candidates and 128 U rows.
+    The ``Bounds`` are :func:`bound_table`'s with slot pieces."""
+    apps = list(apps)
+    leaves = {(l.kind, l.source, l.entry, l.chunk): i for i, l in enumerate(program.leaves)}
+
+    def candidates(t):
+        """[(value leaf, kind, keys)] of t's function; keys: ints (CONST),
+        leaves (LEAF) or probe indices (PROBE)."""
+        name, chunks = t.params[0], (t.params[1] + RESIDUAL_BITS - 1) // RESIDUAL_BITS
+
+        def value(kind, e):
+            li = leaves.get((kind, name, e, 0))
+            return AIM_NONE if li is None or li in program.derived or \
+                program.leaves[li].width != t.width else li
+        out = [(value("cval", i), UF_CONST,
+                [key >> (RESIDUAL_BITS * k) & M256 for k in range(chunks)])
+               for i, key in enumerate(program.table_ckeys.get(name, []))]
+        if name in program.entry_keys:
+            out += [(value("val", e), UF_PROBE, list(key))
+                    for e, key in enumerate(program.entry_keys[name])]
+        else:
+            for e in range(program.table_sizes.get(name, 0)):
+                keys = [leaves.get(("key", name, e, k)) for k in range(chunks)]
+                if None not in keys:
+                    out.append((value("val", e), UF_LEAF, keys))
+            out.append((value("else", 0), UF_ALWAYS, []))
+        return out
+
+    cands_of = {}
+    for t in apps:
+        if t.params[0] not in cands_of:
+            cands_of[t.params[0]] = candidates(t)
+    underived = frozenset(t.id for t in apps
+                          if all(v == AIM_NONE for v, _, _ in cands_of[t.params[0]]))
+    arg_row, row = {}, 0
+    for t in apps:
+        arg_row[t.id] = row
+        row += len(_arg_chunks(t))
+    kept = [t for t in apps if t.id not in underived][:UF_MAX_SLOTS]
+    while kept:
+        names = list(dict.fromkeys(t.params[0] for t in kept))
+        n_arg = arg_row[kept[-1].id] + len(_arg_chunks(kept[-1]))
+        n_key = sum(len(key) for n in names for _, kind, key in cands_of[n] if kind == UF_PROBE)
+        if len(names) <= UF_MAX_FUNCS and n_arg + n_key <= UF_MAX_ROWS and \
+                sum(len(cands_of[n]) for n in names) <= UF_MAX_CANDS:
+            break
+        kept.pop()
+    if not kept:                                         # (the reasons stay: aim_refusal)
+        none = no_ufs()
+        none.slot_of, none.underived = {}, underived
+        return bound_table(constraints, trees, program), none
+    keep, ukeys, funcs, cands, findex = [], [], [], [], {}
+    for n in names:
+        findex[n] = len(funcs)
+        chunks = (next(t for t in kept if t.params[0] == n).params[1] + RESIDUAL_BITS - 1) \
+            // RESIDUAL_BITS
+        funcs.append((len(cands), len(cands_of[n]), chunks))
+        for v, kind, key in cands_of[n]:
+            words = []
+            for k in key:
+                if kind == UF_CONST:
+                    words.append(len(ukeys))
+                    ukeys.append(_u256(k))
+                elif kind == UF_PROBE:
+                    words.append(n_arg + len(keep))
+                    keep.append(int(k))
+                else:
+                    words.append(k)
+            cands.append([v, kind] + words + [0] * (UF_MAX_CHUNKS - len(words)))
+    slot_of = {t.id: u for u, t in enumerate(kept)}
+    ufs = Ufs(np.array([(findex[t.params[0]], arg_row[t.id]) for t in kept],
+                       dtype=np.uint32).reshape(-1, 2),
+              np.array(funcs, dtype=np.uint32).reshape(-1, 3),
+              np.array(cands, dtype=np.uint32).reshape(-1, 6),
+              np.array(ukeys, dtype=np.uint32).reshape(-1, 8), n_arg + len(keep), n_arg,
+              tuple(keep), tuple(kept), tuple(names), slot_of, underived)
+    return bound_table(constraints, trees, program, _slots=slot_of), ufs
+
+
+def has_slot_piece(bounds: Bounds) -> bool:
+    return bool(len(bounds.pieces)) and bool((bounds.pieces[:, 0] & UF_SLOT).any())
+
+
+def uf_resolve_ref(base, urows, ufs: Ufs) -> np.ndarray:
+    """(n_slots,) u32: the destination leaf of every slot under ``base``
+    ((n_leaves, 8) u32, the adopted lane already applied) and the adopted
+    lane's U rows ``urows`` ((n_urows, 8) u32) — the specification of
+    ``mg_walk_uf_resolve``.  The destination is the value leaf of the FIRST
+    candidate of the slot's function whose key equals the argument's rows in
+    every chunk and limb (ALWAYS matches); ``AIM_NONE`` when none matches or
+    that candidate has no value leaf."""
+    base = np.asarray(base, dtype=np.uint32).reshape(-1, 8)
+    urows = np.asarray(urows, dtype=np.uint32).reshape(-1, 8)
+    out = np.full(len(ufs.slots), AIM_NONE, dtype=np.uint32)
+    for u, (f, arg) in enumerate(ufs.slots.tolist()):
+        first, cnt, chunks = (int(x) for x in ufs.funcs[f])
+        for c in range(first, first + cnt):
+            v, kind = int(ufs.cands[c, 0]), int(ufs.cands[c, 1])
+            hit = True
+            for k in range(chunks if kind != UF_ALWAYS else 0):
+                key = int(ufs.cands[c, 2 + k])
+                row = (ufs.ukeys[key] if kind == UF_CONST else base[key] if kind == UF_LEAF
+                       else urows[key])
+                hit = hit and bool((row == urows[arg + k]).all())
+            if hit:
+                out[u] = v
+                break
+    return out
+
+
+def _uf_leaf(leaf: int, dest) -> int:
+    return int(dest[leaf & ~UF_SLOT]) if leaf & UF_SLOT else leaf
+
+
+def uf_live_ref(state, bounds: Bounds) -> list:
+    """L under ``state`` = (residual values, root bits, atom bits, slot
+    destinations (n_slots,)): :func:`bound_live_ref`'s, without the entries
+    that have a slot piece whose destination is ``AIM_NONE``."""
+    if state is None:
+        return []
+    return [e for e in bound_live_ref(state[:3], bounds)
+            if all(_uf_leaf(leaf, state[3]) != AIM_NONE for leaf, *_ in bounds.of(e))]
+
+
+def uf_picks_ref(state, bounds: Bounds, r: int, lanes: int) -> np.ndarray:
+    """:func:`bound_picks_ref` over the live list of :func:`uf_live_ref`."""
+    out = np.full(lanes, AIM_NONE, dtype=np.int64)
+    live = uf_live_ref(state, bounds)
+    n1 = min(len(live), lanes // 8)
+    for j in range(1, 2 * n1 + 1):
+        out[j] = live[((j if j <= n1 else j - n1) - 1 + r * n1) % len(live)]
+    return out
+
+
+def uf_mutate_ref(leafgen, consts, base, state, bounds: Bounds, seed: int, r: int,
+                  lanes: int) -> np.ndarray:
+    """``[n_leaves][8][lanes]`` u32: the neighbours of ``base`` that round
+    ``r`` of ``mg_walk_uf`` evaluates — the specification of
+    ``csrc/mg_walk_uf.h``.  :func:`bound_mutate_ref` with the picks of
+    :func:`uf_picks_ref`, where a slot piece ``UF_SLOT | u`` acts on the leaf
+    ``state[3][u]`` wherever a piece acts on its leaf: the gather of V, the
+    scatter, and the plain move that wins a leaf it shares with a piece."""
+    base = np.ascontiguousarray(base, dtype=np.uint32).reshape(-1, 8)
+    picks = uf_picks_ref(state, bounds, r, lanes)
+    n1 = int((picks != AIM_NONE).sum()) // 2
+    out = np.repeat(base[:, :, None], lanes, axis=2)
+    moves = moves_ref(leafgen, consts, base, seed, r, lanes)
+    bvals = _ints(base)
+    rv = _ints(np.asarray(state[0], dtype=np.uint32).reshape(-1, 8)) if n1 else []
+    for lane in range(lanes):
+        cur = {}
+        if picks[lane] != AIM_NONE:
+            e = int(picks[lane])
+            p, _, _, mode, _ = (int(x) for x in bounds.entries[e])
+            R = rv[p]
+            ps = [(_uf_leaf(leaf, state[3]), lb, vb, n) for leaf, lb, vb, n in bounds.of(e)]
+            if mode == BOUND_XOR:
+                for leaf, leaf_bit, value_bit, n in ps:
+                    cur[leaf] = cur.get(leaf, bvals[leaf]) ^ (
+                        (R >> value_bit & ((1 << n) - 1)) << leaf_bit)
+            else:
+                V = bounds.fixed_of(e)
+                for leaf, leaf_bit, value_bit, n in ps:
+                    V |= (bvals[leaf] >> leaf_bit & ((1 << n) - 1)) << value_bit
+                s = 1 if mode in (BOUND_LOW_STRICT, BOUND_HIGH_STRICT) else 0
+                T = (V - R - s if mode <= BOUND_LOW_STRICT else V + R + s) & M256
+                for leaf, leaf_bit, value_bit, n in ps:
+                    m = (1 << n) - 1
+                    cur[leaf] = (cur.get(leaf, bvals[leaf]) & ~(m << leaf_bit)) | (
+                        (T >> value_bit & m) << leaf_bit)
+        if lane > n1:
+            for leaf, _, v in moves[lane]:
+                cur[leaf] = v
+        for leaf, v in cur.items():
+            out[leaf, :, lane] = np.frombuffer(v.to_bytes(32, "little"), dtype="<u4")
+    return out
+
+
+# ---------------------------------------------------------------------------
 # repair a missed group
 # ---------------------------------------------------------------------------
 
@@ -1253,7 +1611,15 @@ def repair_group(nodes: Sequence, n_cand: int = 1 << 16, form: str = "search", l
     DESIGN.md §3.13): compiled as ``"tree"``, then the table of
     :func:`bound_table` on the compiled program (``bounds`` in the result);
     ``scoring`` is ``"bound"`` when the table has an order entry, else the
-    group runs exactly as ``scored="aim"`` does."""
+    group runs exactly as ``scored="aim"`` does.
+
+    ``scored="uf"``: the same with aims that write the table entry a UF
+    application reads (``mg_walk_uf``): compiled as
+    ``"tree"`` plus the argument probes of :func:`uf_probes`, then the tables
+    of :func:`uf_table` (``bounds`` and ``ufs`` in the result); ``scoring`` is
+    ``"uf"`` when a slot piece is in the table.  When that program does not
+    compile, a probe is folded away or no slot piece results, the group runs
+    exactly as ``scored="bound"`` does."""
     from . import census as CS
     from . import model as M
     from .assign import unpack
@@ -1273,7 +1639,8 @@ def repair_group(nodes: Sequence, n_cand: int = 1 << 16, form: str = "search", l
         return out
     # (built before the mask: a program's schedule follows the node ids, and a
     # wide mask leaves the compiler's spill budget little room)
-    trees = distance_trees(nodes) if scored in ("tree", "aim", "bound") else None
+    trees = distance_trees(nodes) if scored in ("tree", "aim", "bound", "uf") else None
+    apps, uprobes = uf_probes(trees) if scored == "uf" else ([], [])
     resid, table = residuals(nodes) if scored else ([], flat_table(len(nodes)))
     n_amask = 0
     try:
@@ -1285,15 +1652,26 @@ def repair_group(nodes: Sequence, n_cand: int = 1 << 16, form: str = "search", l
         if trees is not None:
             # the atom mask and the trees' residuals; else the table's, below
             extra = CS.mask_probes(trees.atom_nodes) + trees.probes
+            with_trees = None
+            if apps:
+                # the arguments of the UF slots after the residuals
+                try:
+                    with_trees = CS._compile(nodes, CS.mask_probes(nodes) + extra + uprobes, form)
+                except Unsupported:
+                    with_trees = None
+                if with_trees is None or with_trees.n_user_probes != \
+                        masked.n_user_probes + len(extra) + len(uprobes):
+                    with_trees, apps, uprobes = None, [], []
             try:
-                with_trees = CS._compile(nodes, CS.mask_probes(nodes) + extra, form)
+                if with_trees is None:
+                    with_trees = CS._compile(nodes, CS.mask_probes(nodes) + extra, form)
             except Unsupported:
                 with_trees = None
             if with_trees is not None and \
-                    with_trees.n_user_probes == masked.n_user_probes + len(extra):
+                    with_trees.n_user_probes == masked.n_user_probes + len(extra) + len(uprobes):
                 masked, resid, n_amask = with_trees, trees.probes, CS.n_mask_probes(trees.n_atoms)
             else:
-                trees = None
+                trees, apps, uprobes = None, [], []
         if resid and trees is None:
             # residuals the compiler folds or cannot place: the walkers rank by
             # the count alone
@@ -1310,22 +1688,33 @@ def repair_group(nodes: Sequence, n_cand: int = 1 << 16, form: str = "search", l
         out.update(status=CS.UNSUPPORTED, why=str(e))
         return out
     n_mask = CS.n_mask_probes(len(nodes))
-    aims = aim_table(trees, masked) if scored in ("aim", "bound") and trees is not None else None
-    bounds = bound_table(nodes, trees, masked) if scored == "bound" and trees is not None else None
-    if bounds is not None and not bounds.n_order:
+    aims = aim_table(trees, masked) if scored in ("aim", "bound", "uf") and trees is not None \
+        else None
+    bounds = bound_table(nodes, trees, masked) if scored in ("bound", "uf") and trees is not None \
+        else None
+    ufs = no_slots = None
+    if apps:
+        ubounds, ufs = uf_table(nodes, trees, masked, apps)
+        if has_slot_piece(ubounds):
+            bounds = ubounds
+        else:
+            ufs, no_slots = None, ufs
+    if bounds is not None and not bounds.n_order and ufs is None:
         bounds = None
-    if scored == "bound":
+    if scored == "uf":
+        out["ufs"] = ufs if ufs is not None else no_slots if no_slots is not None else no_ufs()
+    if scored in ("bound", "uf"):
         out["bounds"] = bounds if bounds is not None else (
             bounds_of_aims(aims if aims is not None else no_aims(), len(nodes),
                            trees.n_atoms if trees is not None else 0))
     if scored:
-        out["scoring"] = ("bound" if bounds is not None else
+        out["scoring"] = ("uf" if ufs is not None else "bound" if bounds is not None else
                           "aim" if aims is not None and len(aims) else
                           "tree" if trees is not None else "table" if resid else "count")
-    if scored in ("aim", "bound"):
+    if scored in ("aim", "bound", "uf"):
         out["aims"] = aims if aims is not None else no_aims()
         out["program"] = masked                          # what the table's leaves index
-    if masked.n_user_probes != n_mask + n_amask + len(resid):
+    if masked.n_user_probes != n_mask + n_amask + len(resid) + len(uprobes):
         out["status"] = CS.DEAD if masked.n_user_probes == 0 else CS.UNSUPPORTED
         out["why"] = "%d mask probes compiled to %d" % (n_mask, masked.n_user_probes)
         return out
@@ -1353,7 +1742,14 @@ def repair_group(nodes: Sequence, n_cand: int = 1 << 16, form: str = "search", l
         starts = np.stack([leaves if i == c.best_index else eng.witness(full, M.SEARCH_SEED, i)[0]
                            for i in picks])
         wide = eng.load(CS.census_view(masked, n_mask + n_amask + len(resid)), gens, prog_seed=0)
-        if trees is not None and bounds is not None:
+        if trees is not None and ufs is not None:
+            # the U rows after the residuals: the arguments, then the kept keys
+            wide = eng.load(uf_view(masked, n_mask + n_amask + len(resid) + ufs.n_arg_rows,
+                                    ufs.keep), gens, prog_seed=0)
+            res = eng.walk_uf(wide, starts, len(nodes), trees, bounds, ufs, seed, lanes,
+                              max_rounds, sync_every)
+            out["trees"] = trees
+        elif trees is not None and bounds is not None:
             res = eng.walk_bound(wide, starts, len(nodes), trees, bounds, seed, lanes, max_rounds,
                                  sync_every)
             out["trees"] = trees

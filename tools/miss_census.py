@@ -46,6 +46,11 @@ usage: tools/miss_census.py --workload {c1,c3,c3o,c4,c5} --query N
            root the rule that refused each side without an entry, every
            walker's trace, the tree of each root the winner still fails, and
            the device time per round beside mg_walk_aim's from the same starts
+       ... --walk-uf [--walkers N] [--lanes L] [--rounds R]
+           after the census, that walk with aims for UF outputs too (DESIGN.md
+           §3.14): the slots, how many sides of the read residuals resolve with
+           and without them, per reason the refused sides, every walker's
+           trace, and the device time per round beside scored="bound"
        tools/miss_census.py [workload] [n]
            the older census: which of a stream's first n queries the batched
            search misses, grouped by the shape of their newest constraint
@@ -589,6 +594,87 @@ def show_bound(rows, lanes):
                                         g.get("aim_end")))
 
 
+def uf_rows(wl, qi, n_cand, lanes, rounds, walkers):
+    """Per independent group of the query: what ``repair.repair_group(scored=
+    "uf")`` did with ``walkers`` walkers: the slots and their functions, how
+    many sides of the read residual probes (both sides of every xor and
+    difference a HAMMING or MAGNITUDE atom or simple root reads) resolve with
+    the slots and how many did without, per reason the refused sides, every
+    walker's trace, and the device time per round beside mg_walk_bound's from
+    the same starts."""
+    import mythril_amd.model as M
+    from mythril_amd import repair as RP
+    from mythril_amd.smt import node as N
+    rows = []
+    for group in M.dependence_buckets(stream_query(wl, qi)):
+        kw = dict(n_cand=n_cand, form="search", lanes=lanes, max_rounds=rounds)
+        g = RP.repair_group(group, scored="uf", walkers=walkers, **kw)
+        row = {"constraints": len(group), "status": g["status"], "scoring": g.get("scoring")}
+        if "why" in g:
+            row["why"] = g["why"]
+        res, T, B, U = g.get("repair"), g.get("trees"), g.get("bounds"), g.get("ufs")
+        if res is not None and T is not None:
+            prog = g["program"]
+            apps, _ = RP.uf_probes(T)
+            row.update(starts=g["starts"], winner=res.winner, rounds=res.rounds, walkers=walkers,
+                       nfail=[int(v) for v in res.nfail], cost=[int(v) for v in res.cost],
+                       traces=[_runs(res.trace[w, :res.rounds]) for w in range(walkers)],
+                       uf_ms_per_round=round(res.kernel_ms / max(1, res.rounds), 4),
+                       applications=len(apps), slots=len(U), u_rows=int(U.n_urows),
+                       functions=list(U.names), candidates=len(U.cands),
+                       unwritable=int((U.cands[:, 0] == RP.AIM_NONE).sum()) if len(U.cands) else 0,
+                       entries=len(B), slot_entries=sum(
+                           any(leaf & RP.UF_SLOT for leaf, *_ in B.of(e)) for e in range(len(B))))
+            slots = U.slot_of if len(U) else None
+            sides = [t for p in RP._read_probes(T) if len(T.probes[p].args) == 2
+                     for t in T.probes[p].args]
+            row["sides"] = len(sides)
+            row["resolved"] = sum(RP.aim_pieces(t, prog, slots) is not None for t in sides)
+            row["resolved_without_slots"] = sum(RP.aim_pieces(t, prog) is not None for t in sides)
+            row["refused"] = [{"why": RP.aim_refusal(t, prog, U if U.slot_of is not None else None),
+                               "uf": t.op == "apply", "term": N.to_sexpr(t, 3)}
+                              for t in sides if RP.aim_pieces(t, prog, slots) is None]
+            bound = RP.repair_group(group, scored="bound", walkers=walkers, **kw).get("repair")
+            if bound is not None:
+                row["bound_ms_per_round"] = round(bound.kernel_ms / max(1, bound.rounds), 4)
+                row["bound_rounds"] = bound.rounds
+                row["bound_end"] = [int(bound.nfail[bound.winner]), int(bound.cost[bound.winner])]
+        rows.append(row)
+    return rows
+
+
+def show_uf(rows, lanes):
+    for gi, g in enumerate(rows):
+        print(" uf walk group %d: %d constraints -> %s%s; scoring: %s" % (
+            gi, g["constraints"], g["status"], (" (%s)" % g["why"]) if "why" in g else "",
+            g["scoring"]))
+        if "traces" not in g:
+            continue
+        print("  %d applications on the read sides, %d slots of %s, %d U rows; %d candidates, %d "
+              "without a writable value leaf; %d entries, %d with a slot piece" % (
+                  g["applications"], g["slots"], g["functions"], g["u_rows"], g["candidates"],
+                  g["unwritable"], g["entries"], g["slot_entries"]))
+        print("  sides of the read residuals: %d; resolve: %d (%d without slots); refused: %d, "
+              "%d of them UF applications" % (g["sides"], g["resolved"],
+                                              g["resolved_without_slots"], len(g["refused"]),
+                                              sum(e["uf"] for e in g["refused"])))
+        rules = collections.OrderedDict()
+        for e in g["refused"]:
+            rules.setdefault(e["why"], []).append(e)
+        for why, es in rules.items():
+            print("   refused: %d sides: %s, e.g. %.120s" % (len(es), why, es[0]["term"]))
+        print("  %d walkers, %d rounds of %d lanes each; winner: walker %d" % (
+            g["walkers"], g["rounds"], lanes, g["winner"]))
+        for w, tr in enumerate(g["traces"]):
+            print("   walker %2d from candidate %d: ends %d/%d; nfail/cost per round: %s" % (
+                w, g["starts"][w], g["nfail"][w], g["cost"][w], tr))
+        print("  device time per round: mg_walk_%s x%d %.4f ms; scored=\"bound\" x%d %s ms "
+              "(%s rounds, ends %s)" % ("uf" if g["scoring"] == "uf" else g["scoring"],
+                                        g["walkers"], g["uf_ms_per_round"], g["walkers"],
+                                        g.get("bound_ms_per_round"), g.get("bound_rounds"),
+                                        g.get("bound_end")))
+
+
 def show(r):
     print("== %s query %d%s: %d constraints, %d candidates per group (%.0f ms in all)" % (
         r["workload"], r["query"], " (top-level ands split, i.j = conjunct j of constraint i)"
@@ -641,6 +727,8 @@ def main():
                     help="then run the tree-scored walk with aimed moves (DESIGN.md 3.12)")
     ap.add_argument("--walk-bound", action="store_true",
                     help="then run that walk with aims for orders too (DESIGN.md 3.13)")
+    ap.add_argument("--walk-uf", action="store_true",
+                    help="then run that walk with aims for UF outputs too (DESIGN.md 3.14)")
     ap.add_argument("--walkers", type=int, default=16)
     ap.add_argument("--lanes", type=int, default=4096)
     ap.add_argument("--rounds", type=int, default=64)
@@ -674,6 +762,10 @@ def main():
         for r in reports:
             r["walk_bound"] = bound_rows(r["workload"], r["query"], a.candidates, a.lanes,
                                          a.rounds, a.walkers)
+    if a.walk_uf:
+        for r in reports:
+            r["walk_uf"] = uf_rows(r["workload"], r["query"], a.candidates, a.lanes, a.rounds,
+                                   a.walkers)
     if a.json:
         print(json.dumps(reports, indent=1))
     else:
@@ -689,6 +781,8 @@ def main():
                 show_aim(r["walk_aim"], a.lanes)
             if a.walk_bound:
                 show_bound(r["walk_bound"], a.lanes)
+            if a.walk_uf:
+                show_uf(r["walk_uf"], a.lanes)
 
 
 if __name__ == "__main__":

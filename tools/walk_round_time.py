@@ -1,6 +1,8 @@
 """Device time per round of mg_walk_bound beside mg_walk_aim on the same
 program, starts and XOR-only table (aim_cases `bytes`), in one run: aim, bound,
-aim alternating.  Prints median, min and max of kernel_ms / rounds."""
+aim alternating.  Prints median, min and max of kernel_ms / rounds.
+``--uf``: mg_walk_uf beside mg_walk_bound instead, on the same slot-free table:
+bound, uf, bound alternating."""
 import os
 import statistics
 import sys
@@ -22,14 +24,19 @@ for walkers in (1, 16):
     starts = AC.starts(name, walkers)
     aim = lambda: eng.walk_aim(lp, starts, n_roots, T, A, AC.SEED, 4096, 64)
     bound = lambda: eng.walk_bound(lp, starts, n_roots, T, B, AC.SEED, 4096, 64)
+    uf = lambda: eng.walk_uf(lp, starts, n_roots, T, B, RP.no_ufs(), AC.SEED, 4096, 64)
+    plan = (("bound_1", bound), ("uf", uf), ("bound_2", bound)) if "--uf" in sys.argv else \
+        (("aim_1", aim), ("bound", bound), ("aim_2", aim))
+    if "--uf" in sys.argv:
+        aim = uf                                                     # the pair that is compared
     a, b = aim(), bound()                                            # warm up, and the same walk
     assert np.array_equal(a.leaves, b.leaves) and np.array_equal(a.trace, b.trace)
     assert a.rounds == b.rounds
-    runs = {"aim_1": [], "bound": [], "aim_2": []}
+    runs = {key: [] for key, _ in plan}
     for _ in range(40):
-        for key, fn in (("aim_1", aim), ("bound", bound), ("aim_2", aim)):
+        for key, fn in plan:
             res = fn()
             runs[key].append(res.kernel_ms / res.rounds)
     for key, v in runs.items():
-        print("walkers %2d lanes 4096 rounds %d x40  %-6s ms/round: median %.4f min %.4f max %.4f"
+        print("walkers %2d lanes 4096 rounds %d x40  %-7s ms/round: median %.4f min %.4f max %.4f"
               % (walkers, a.rounds, key, statistics.median(v), min(v), max(v)))
