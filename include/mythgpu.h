@@ -471,6 +471,54 @@ int mg_walk_uf_mutate_host(const mg_leafgen* leaves, uint32_t n_leaves, const ui
                            uint64_t seed, uint32_t r, uint32_t lanes, uint32_t lane0,
                            uint32_t n_lanes, uint32_t* out, uint32_t* moves);
 
+/* Tree-scored walk with aims through sums, differences, masks and shifts
+ * (DESIGN.md §3.15): mg_walk_uf whose entries may be linear.  A linear entry
+ * belongs to a side that is a sum of +-terms; its pieces and fixed value are
+ * those of one term of the sum, the target, and its move changes the target
+ * by what the side must change by (csrc/mg_walk_sum.h; mythril_amd/repair.py
+ * sum_table builds the tables, sum_mutate_ref is the specification):
+ *   lin [n_entries]  0: the entry is mg_walk_uf's.  Else bit 0 set; bit 1: the
+ *                    target's sign in the side is -1; bits 8-15: the side row
+ *                    (XOR mode; 0 in the order modes); every other bit 0
+ * The program writes n_srows side rows (at most 64), one 256-bit probe per
+ * linear side with an XOR entry, after the n_resid residual probes and before
+ * the n_urows U rows.  With lin all 0 the walk is mg_walk_uf bit for bit.
+ * Refused without a launch: what mg_walk_uf refuses (a linear XOR entry may
+ * have fixed bits); an unknown lin word; a side row at or above n_srows, or
+ * one in a linear order entry; a slot piece in a linear entry; side rows and
+ * U rows the program does not have; a null table with a non-zero count. */
+int mg_walk_sum(mg_ctx* ctx, const mg_prog* prog,
+                const uint32_t* starts /*[walkers][n_leaves][8]*/, uint32_t walkers,
+                uint32_t n_roots, uint32_t mask_probe0, const uint32_t* roots /*[n_roots]*/,
+                uint32_t n_atoms, const uint32_t* atoms /*[n_atoms] or NULL*/,
+                const uint32_t* code /*[n_code] or NULL*/, uint32_t n_code, uint32_t n_resid,
+                const uint32_t* entries /*[n_entries][5] or NULL*/, uint32_t n_entries,
+                const uint32_t* pieces /*[n_pieces][4] or NULL*/, uint32_t n_pieces,
+                const uint32_t* fixed /*[n_entries][8] or NULL*/,
+                const uint32_t* lin /*[n_entries] or NULL*/, uint32_t n_srows,
+                const uint32_t* slots, uint32_t n_slots, const uint32_t* funcs, uint32_t n_funcs,
+                const uint32_t* cands, uint32_t n_cands, const uint32_t* ukeys, uint32_t n_ukeys,
+                uint32_t n_urows, uint64_t seed, uint32_t lanes, uint32_t max_rounds,
+                uint32_t sync_every, uint32_t* out_leaves /*[walkers][n_leaves][8]*/,
+                uint32_t* out_nfail /*[walkers]*/, uint32_t* out_cost /*[walkers]*/,
+                uint32_t* out_rounds, uint32_t* trace /*[walkers][max_rounds][2] or NULL*/,
+                uint32_t* out_winner);
+/* Host-only (no GPU): mg_walk_uf_mutate_host for mg_walk_sum's lane function;
+ * svals: the side rows of the base. */
+int mg_walk_sum_mutate_host(const mg_leafgen* leaves, uint32_t n_leaves, const uint32_t* consts,
+                            uint32_t n_consts, const uint32_t* base /*[n_leaves][8]*/,
+                            const uint32_t* rvals /*[n_resid][8] or NULL*/, uint32_t n_resid,
+                            const uint32_t* mvals, uint32_t n_roots, uint32_t n_atoms,
+                            const uint32_t* entries, uint32_t n_entries, const uint32_t* pieces,
+                            uint32_t n_pieces, const uint32_t* fixed, const uint32_t* lin,
+                            const uint32_t* svals /*[n_srows][8] or NULL*/, uint32_t n_srows,
+                            const uint32_t* slots, uint32_t n_slots, const uint32_t* funcs,
+                            uint32_t n_funcs, const uint32_t* cands, uint32_t n_cands,
+                            const uint32_t* ukeys, uint32_t n_ukeys, uint32_t n_urows,
+                            const uint32_t* dest /*[n_slots]*/, uint64_t seed, uint32_t r,
+                            uint32_t lanes, uint32_t lane0, uint32_t n_lanes, uint32_t* out,
+                            uint32_t* moves);
+
 /* Corpus batches: many programs, one launch.  Device-pointer API for
  * resident benchmarking; stream is a hipStream_t (NULL = the context's own
  * stream, which the synchronous calls also use).

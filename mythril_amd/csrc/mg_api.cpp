@@ -30,6 +30,7 @@
 #include "mg_walk_aim.h"
 #include "mg_walk_bound.h"
 #include "mg_walk_uf.h"
+#include "mg_walk_sum.h"
 
 // the interpreter of each register layout (mg_interp_asm.hip, one
 // translation unit per layout; mg_find_layout lists them)
@@ -156,6 +157,32 @@ hipError_t mg_launch_walk_uf_pick(const uint32_t* d_masks, const uint32_t* d_ama
                                   uint32_t* d_rstate, uint32_t* d_mstate, uint32_t* d_ustate,
                                   uint32_t* d_dests, uint32_t* d_lives, mg_walk_state* d_state,
                                   uint32_t* d_trace, hipStream_t stream);
+// the round of mg_walk_sum (mg_walk_sum.hip): mg_walk_uf's
+// with the entries' lin words and the walkers' side rows
+hipError_t mg_launch_walk_sum_round(const uint32_t* d_bases, const mg_leafgen* d_gen,
+                                    const uint32_t* d_consts, uint32_t n_leaves, uint64_t seed,
+                                    uint32_t r, uint32_t lanes, uint32_t walkers,
+                                    const uint32_t* d_entries, uint32_t n_entries,
+                                    const uint32_t* d_pieces, const uint32_t* d_fixed,
+                                    const uint32_t* d_lin, const uint32_t* d_rstate,
+                                    uint32_t n_resid, const uint32_t* d_sstate, uint32_t n_srows,
+                                    const uint32_t* d_lives, const uint32_t* d_dests,
+                                    uint32_t n_slots, uint32_t* d_leaves, hipStream_t stream);
+hipError_t mg_launch_walk_sum_pick(const uint32_t* d_masks, const uint32_t* d_amasks,
+                                   const uint32_t* d_resid, const uint32_t* d_srows,
+                                   uint32_t n_srows, const uint32_t* d_urows,
+                                   const uint32_t* d_roots, const uint32_t* d_atoms,
+                                   const uint32_t* d_code, uint32_t lanes, uint32_t walkers,
+                                   uint32_t n_roots, uint32_t n_atoms, uint32_t* d_bases,
+                                   const mg_leafgen* d_gen, const uint32_t* d_consts,
+                                   uint32_t n_leaves, uint64_t seed, uint32_t r,
+                                   uint32_t max_rounds, const uint32_t* d_entries,
+                                   uint32_t n_entries, const uint32_t* d_pieces,
+                                   const uint32_t* d_fixed, const uint32_t* d_lin,
+                                   uint32_t n_resid, const mg_uf_tables& uf, uint32_t* d_rstate,
+                                   uint32_t* d_mstate, uint32_t* d_sstate, uint32_t* d_ustate,
+                                   uint32_t* d_dests, uint32_t* d_lives, mg_walk_state* d_state,
+                                   uint32_t* d_trace, hipStream_t stream);
 
 
 struct mg_ctx {
@@ -1067,7 +1094,9 @@ static bool walk_table_ok(const uint32_t* table, uint32_t n_roots, uint32_t n_re
 // code) or the tree tables of mg_walk_tree (table: its root entries); aim: the
 // round of mg_walk_aim with its aim table (tree scoring); bound: the round of
 // mg_walk_bound, whose entries have 5 words and a fixed value each; uf: the
-// round of mg_walk_uf, mg_walk_bound's with the UF tables uft (host pointers)
+// round of mg_walk_uf, mg_walk_bound's with the UF tables uft (host pointers);
+// sum: the round of mg_walk_sum, mg_walk_uf's with the lin words and n_srows
+// side rows between the residual probes and the U rows
 struct walk_scoring {
     const uint32_t* table;
     const uint32_t* atoms;
@@ -1084,6 +1113,9 @@ struct walk_scoring {
     const uint32_t* fixed;
     bool uf;
     mg_uf_tables uft;
+    bool sum;
+    const uint32_t* lin;
+    uint32_t n_srows;
 };
 
 // The scored walk.  Rounds are queued back to back;
@@ -1131,7 +1163,22 @@ static int walk_run(mg_ctx* ctx, const mg_prog* prog, const uint32_t* starts, ui
         return fail(ctx, MG_E_ARG, "walk: a table entry names an unknown kind or a residual "
                     "probe at or above %u", n_resid);
     }
-    if (sc.uf) {
+    if (sc.sum) {
+        const uint32_t room = prog->n_probes - mask_probe0 - n_mask - n_amask - n_resid;
+        if (sc.n_srows > MG_SUM_MAX_ROWS || sc.n_srows > room || sc.uft.n_urows > room - sc.n_srows)
+            return fail(ctx, MG_E_ARG, "walk_sum: %u side rows (at most %u) and %u U rows after "
+                        "%u residual probes outside the program's %u probes", sc.n_srows,
+                        MG_SUM_MAX_ROWS, sc.uft.n_urows, n_resid, prog->n_probes);
+        if (sc.n_entries && !sc.lin)
+            return fail(ctx, MG_E_ARG, "walk_sum: null lin words with %u entries", sc.n_entries);
+        if (!mg_walk_sum_ok(sc.entries, sc.n_entries, sc.pieces, sc.n_pieces, sc.fixed, sc.lin,
+                            sc.n_srows, prog->leafgen.data(), prog->n_leaves, n_resid, n_roots,
+                            sc.n_atoms, sc.uft))
+            return fail(ctx, MG_E_ARG, "walk_sum: malformed tables (mg_walk_sum_ok: what "
+                        "mg_walk_uf_ok checks; an unknown lin word, the side row of a linear XOR "
+                        "entry at or above %u, a side row in a linear order entry, a slot piece "
+                        "in a linear entry, null tables)", sc.n_srows);
+    } else if (sc.uf) {
         if (sc.uft.n_urows > prog->n_probes - mask_probe0 - n_mask - n_amask - n_resid)
             return fail(ctx, MG_E_ARG, "walk_uf: %u U rows after %u residual probes outside the "
                         "program's %u probes", sc.uft.n_urows, n_resid, prog->n_probes);
@@ -1187,7 +1234,9 @@ static int walk_run(mg_ctx* ctx, const mg_prog* prog, const uint32_t* starts, ui
                  cand_b = sc.uf ? (size_t)sc.uft.n_cands * 24 : 0,
                  ukey_b = sc.uf ? (size_t)sc.uft.n_ukeys * 32 : 0,
                  ustate_b = sc.uf ? (size_t)walkers * sc.uft.n_urows * 32 : 0,
-                 dest_b = sc.uf ? (size_t)walkers * sc.uft.n_slots * 4 : 0;
+                 dest_b = sc.uf ? (size_t)walkers * sc.uft.n_slots * 4 : 0,
+                 lin_b = sc.sum ? (size_t)sc.n_entries * 4 : 0,
+                 sstate_b = sc.sum ? (size_t)walkers * sc.n_srows * 32 : 0;
     const size_t off_base = align(state_b), off_gen = off_base + align(base_b),
                  off_table = off_gen + align(gen_b), off_trace = off_table + align(table_b),
                  off_root = off_trace + align(trace_b), off_leaf = off_root + align(root_b),
@@ -1198,7 +1247,8 @@ static int walk_run(mg_ctx* ctx, const mg_prog* prog, const uint32_t* starts, ui
                  off_mstate = off_fixed + align(fixed_b), off_slot = off_mstate + align(mstate_b),
                  off_func = off_slot + align(slot_b), off_cand = off_func + align(func_b),
                  off_ukey = off_cand + align(cand_b), off_ustate = off_ukey + align(ukey_b),
-                 off_dest = off_ustate + align(ustate_b), bytes = off_dest + align(dest_b);
+                 off_dest = off_ustate + align(ustate_b), off_lin = off_dest + align(dest_b),
+                 off_sstate = off_lin + align(lin_b), bytes = off_sstate + align(sstate_b);
     void* ws;
     int rc = workspace(ctx, bytes + 256, &ws);
     if (rc) return rc;
@@ -1220,6 +1270,8 @@ static int walk_run(mg_ctx* ctx, const mg_prog* prog, const uint32_t* starts, ui
     uint32_t* d_mstate = (uint32_t*)(w + off_mstate);
     uint32_t* d_ustate = (uint32_t*)(w + off_ustate);
     uint32_t* d_dests = (uint32_t*)(w + off_dest);
+    uint32_t* d_lin = (uint32_t*)(w + off_lin);
+    uint32_t* d_sstate = (uint32_t*)(w + off_sstate);
     // the UF tables as the kernels read them: device pointers, host counts
     mg_uf_tables d_uf = sc.uft;
     d_uf.slots = (const uint32_t*)(w + off_slot);
@@ -1264,6 +1316,9 @@ static int walk_run(mg_ctx* ctx, const mg_prog* prog, const uint32_t* starts, ui
                                      ctx->stream));
     if (ustate_b) HIPCHECK(ctx, hipMemsetAsync(d_ustate, 0, ustate_b, ctx->stream));
     if (dest_b) HIPCHECK(ctx, hipMemsetAsync(d_dests, 0xFF, dest_b, ctx->stream));
+    if (lin_b)
+        HIPCHECK(ctx, hipMemcpyAsync(d_lin, sc.lin, lin_b, hipMemcpyHostToDevice, ctx->stream));
+    if (sstate_b) HIPCHECK(ctx, hipMemsetAsync(d_sstate, 0, sstate_b, ctx->stream));
     mg_run run = empty_run();
     run.leaves = d_leaves;
     run.root_bits = (uint64_t*)(w + off_root);
@@ -1274,7 +1329,9 @@ static int walk_run(mg_ctx* ctx, const mg_prog* prog, const uint32_t* starts, ui
     const uint32_t* d_masks = d_probes + (size_t)mask_probe0 * 8 * total;
     const uint32_t* d_amasks = d_masks + (size_t)n_mask * 8 * total;
     const uint32_t* d_resid = d_amasks + (size_t)n_amask * 8 * total;
-    const uint32_t* d_urows = d_resid + (size_t)n_resid * 8 * total;
+    const uint32_t n_srows = sc.sum ? sc.n_srows : 0;
+    const uint32_t* d_srows = d_resid + (size_t)n_resid * 8 * total;
+    const uint32_t* d_urows = d_srows + (size_t)n_srows * 8 * total;
     const uint32_t* d_consts = prog->h_desc.consts;       // the first n_consts entries: as loaded
     std::vector<mg_walk_state> h_state(walkers);
     bool done = false;
@@ -1283,7 +1340,13 @@ static int walk_run(mg_ctx* ctx, const mg_prog* prog, const uint32_t* starts, ui
     while (r < max_rounds && !done) {
         const uint32_t stop = max_rounds - r < sync_every ? max_rounds : r + sync_every;
         for (; r < stop; ++r) {
-            if (sc.uf)
+            if (sc.sum)
+                HIPCHECK(ctx, mg_launch_walk_sum_round(d_bases, d_gen, d_consts, n_leaves, seed,
+                                                       r, lanes, walkers, d_entries, sc.n_entries,
+                                                       d_pieces, d_fixed, d_lin, d_rstate, n_resid,
+                                                       d_sstate, n_srows, d_lives, d_dests,
+                                                       d_uf.n_slots, d_leaves, ctx->stream));
+            else if (sc.uf)
                 HIPCHECK(ctx, mg_launch_walk_uf_round(d_bases, d_gen, d_consts, n_leaves, seed, r,
                                                       lanes, walkers, d_entries, sc.n_entries,
                                                       d_pieces, d_fixed, d_rstate, n_resid,
@@ -1303,7 +1366,16 @@ static int walk_run(mg_ctx* ctx, const mg_prog* prog, const uint32_t* starts, ui
                 HIPCHECK(ctx, mg_launch_walk_round(d_bases, d_gen, d_consts, n_leaves, seed, r,
                                                    lanes, walkers, d_leaves, ctx->stream));
             HIPCHECK(ctx, launch(ctx, 0, prog->d_desc, 1, run, prog->n_lds, ctx->stream));
-            if (sc.uf)
+            if (sc.sum)
+                HIPCHECK(ctx, mg_launch_walk_sum_pick(d_masks, d_amasks, d_resid, d_srows, n_srows,
+                                                      d_urows, d_table, d_atoms, d_code, lanes,
+                                                      walkers, n_roots, sc.n_atoms, d_bases, d_gen,
+                                                      d_consts, n_leaves, seed, r, max_rounds,
+                                                      d_entries, sc.n_entries, d_pieces, d_fixed,
+                                                      d_lin, n_resid, d_uf, d_rstate, d_mstate,
+                                                      d_sstate, d_ustate, d_dests, d_lives,
+                                                      d_state, d_trace, ctx->stream));
+            else if (sc.uf)
                 HIPCHECK(ctx, mg_launch_walk_uf_pick(d_masks, d_amasks, d_resid, d_urows, d_table,
                                                      d_atoms, d_code, lanes, walkers, n_roots,
                                                      sc.n_atoms, d_bases, d_gen, d_consts,
@@ -1438,6 +1510,30 @@ int mg_walk_uf(mg_ctx* ctx, const mg_prog* prog, const uint32_t* starts, uint32_
                              entries, n_entries, pieces, n_pieces, true, fixed, true,
                              {slots, n_slots, funcs, n_funcs, cands, n_cands, ukeys, n_ukeys,
                               n_urows}};
+    return walk_run(ctx, prog, starts, walkers, n_roots, mask_probe0, sc, n_resid, seed, lanes,
+                    max_rounds, sync_every, out_leaves, out_nfail, out_cost, out_rounds, trace,
+                    out_winner);
+}
+
+// The same with aims through sums, differences, masks and shifts (DESIGN.md
+// §3.15): mg_walk_uf with the kernels of mg_walk_sum.hip, the lin words of
+// mg_walk_sum.h and n_srows side rows between the residual probes and the U
+// rows.
+int mg_walk_sum(mg_ctx* ctx, const mg_prog* prog, const uint32_t* starts, uint32_t walkers,
+                uint32_t n_roots, uint32_t mask_probe0, const uint32_t* roots, uint32_t n_atoms,
+                const uint32_t* atoms, const uint32_t* code, uint32_t n_code, uint32_t n_resid,
+                const uint32_t* entries, uint32_t n_entries, const uint32_t* pieces,
+                uint32_t n_pieces, const uint32_t* fixed, const uint32_t* lin, uint32_t n_srows,
+                const uint32_t* slots, uint32_t n_slots, const uint32_t* funcs, uint32_t n_funcs,
+                const uint32_t* cands, uint32_t n_cands, const uint32_t* ukeys, uint32_t n_ukeys,
+                uint32_t n_urows, uint64_t seed, uint32_t lanes, uint32_t max_rounds,
+                uint32_t sync_every, uint32_t* out_leaves, uint32_t* out_nfail,
+                uint32_t* out_cost, uint32_t* out_rounds, uint32_t* trace, uint32_t* out_winner) {
+    if (ctx) HIPCHECK(ctx, hipSetDevice(ctx->device));
+    const walk_scoring sc = {roots, atoms, n_atoms, code, n_code, true, true,
+                             entries, n_entries, pieces, n_pieces, true, fixed, true,
+                             {slots, n_slots, funcs, n_funcs, cands, n_cands, ukeys, n_ukeys,
+                              n_urows}, true, lin, n_srows};
     return walk_run(ctx, prog, starts, walkers, n_roots, mask_probe0, sc, n_resid, seed, lanes,
                     max_rounds, sync_every, out_leaves, out_nfail, out_cost, out_rounds, trace,
                     out_winner);
@@ -1586,6 +1682,61 @@ int mg_walk_uf_mutate_host(const mg_leafgen* leaves, uint32_t n_leaves, const ui
         const uint32_t e = mg_walk_uf_lane(base, leaves, consts, n_leaves, seed, r, lane0 + a,
                                            lanes, entries, pieces, fixed, rvals, live, dest,
                                            out + a, n_lanes, &mv);
+        if (moves) {
+            moves[5 * (size_t)a] = mv.n;
+            moves[5 * (size_t)a + 1] = mv.kind[0] | mv.kind[1] << 8;
+            moves[5 * (size_t)a + 2] = mv.leaf[0];
+            moves[5 * (size_t)a + 3] = mv.leaf[1];
+            moves[5 * (size_t)a + 4] = e;
+        }
+    }
+    return MG_OK;
+}
+
+// Host only: mg_walk_uf_mutate_host of the lane function of mg_walk_sum.h;
+// lin: the entries' lin words, svals: the side rows of the base ([n_srows][8];
+// may be null when rvals or mvals is: round 0).
+int mg_walk_sum_mutate_host(const mg_leafgen* leaves, uint32_t n_leaves, const uint32_t* consts,
+                            uint32_t n_consts, const uint32_t* base, const uint32_t* rvals,
+                            uint32_t n_resid, const uint32_t* mvals, uint32_t n_roots,
+                            uint32_t n_atoms, const uint32_t* entries, uint32_t n_entries,
+                            const uint32_t* pieces, uint32_t n_pieces, const uint32_t* fixed,
+                            const uint32_t* lin, const uint32_t* svals, uint32_t n_srows,
+                            const uint32_t* slots, uint32_t n_slots, const uint32_t* funcs,
+                            uint32_t n_funcs, const uint32_t* cands, uint32_t n_cands,
+                            const uint32_t* ukeys, uint32_t n_ukeys, uint32_t n_urows,
+                            const uint32_t* dest, uint64_t seed, uint32_t r, uint32_t lanes,
+                            uint32_t lane0, uint32_t n_lanes, uint32_t* out, uint32_t* moves) {
+    if (!leaves || !base || !out || (n_consts && !consts) || n_leaves == 0) return MG_E_ARG;
+    if (lanes < 1 || lanes > MG_REPAIR_MAX_LANES || r >= MG_REPAIR_MAX_ROUNDS) return MG_E_ARG;
+    if (lane0 > lanes || n_lanes > lanes - lane0) return MG_E_ARG;
+    if (n_roots > MG_WT_MAX_ROOTS || n_atoms > MG_WT_MAX_ATOMS) return MG_E_ARG;
+    if (n_slots && !dest) return MG_E_ARG;
+    if (n_srows && rvals && mvals && !svals) return MG_E_ARG;
+    for (uint32_t i = 0; i < n_leaves; ++i) {
+        if (leaves[i].width < 1 || leaves[i].width > MG_MAX_WIDTH) return MG_E_ARG;
+        if ((uint64_t)leaves[i].pool_off + leaves[i].pool_n > n_consts) return MG_E_ARG;
+        uint32_t v[8];
+        memcpy(v, base + (size_t)i * 8, 32);
+        mg_repair_mask(v, leaves[i].width);
+        if (memcmp(v, base + (size_t)i * 8, 32)) return MG_E_ARG;     // a base beyond its width
+    }
+    const mg_uf_tables t = {slots, n_slots, funcs, n_funcs, cands, n_cands, ukeys, n_ukeys,
+                            n_urows};
+    if (!mg_walk_sum_ok(entries, n_entries, pieces, n_pieces, fixed, lin, n_srows, leaves,
+                        n_leaves, n_resid, n_roots, n_atoms, t))
+        return MG_E_ARG;
+    for (uint32_t u = 0; u < n_slots; ++u)               // a destination is a leaf or none
+        if (dest[u] != MG_AIM_NONE && dest[u] >= n_leaves) return MG_E_ARG;
+    uint32_t live[MG_AIM_LIVE_WORDS];
+    mg_walk_uf_live(entries, n_entries, pieces, rvals, mvals, MG_BOUND_MASK_WORDS(n_roots), dest,
+                    live);
+    for (uint32_t a = 0; a < n_lanes; ++a) {
+        for (size_t i = 0; i < (size_t)n_leaves * 8; ++i) out[i * n_lanes + a] = base[i];
+        mg_repair_moves mv;
+        const uint32_t e = mg_walk_sum_lane(base, leaves, consts, n_leaves, seed, r, lane0 + a,
+                                            lanes, entries, pieces, fixed, lin, rvals, svals,
+                                            live, dest, out + a, n_lanes, &mv);
         if (moves) {
             moves[5 * (size_t)a] = mv.n;
             moves[5 * (size_t)a + 1] = mv.kind[0] | mv.kind[1] << 8;

@@ -37,7 +37,7 @@ EXPORTS = ("mg_init", "mg_init_layout", "mg_layouts", "mg_free", "mg_last_error"
            "mg_walk", "mg_walk_score_host", "mg_walk_tree", "mg_walk_tree_score_host",
            "mg_walk_aim", "mg_walk_aim_mutate_host", "mg_walk_bound",
            "mg_walk_bound_mutate_host", "mg_walk_uf", "mg_walk_uf_resolve_host",
-           "mg_walk_uf_mutate_host")
+           "mg_walk_uf_mutate_host", "mg_walk_sum", "mg_walk_sum_mutate_host")
 
 
 def layouts() -> Dict[int, Tuple[int, int]]:
@@ -147,6 +147,12 @@ def load_library(path: str = _LIB_PATH, check_digest: bool = True):
         lib.mg_walk_uf_mutate_host.argtypes = [p, u32, p, u32, p, p, u32, p, u32, u32, p, u32, p,
                                                u32, p, p, u32, p, u32, p, u32, p, u32, u32, p,
                                                u64, u32, u32, u32, u32, p, p]
+        lib.mg_walk_sum.argtypes = [p, p, p, u32, u32, u32, p, u32, p, p, u32, u32, p, u32, p, u32,
+                                    p, p, u32, p, u32, p, u32, p, u32, p, u32, u32, u64, u32, u32,
+                                    u32, p, p, p, C.POINTER(u32), p, C.POINTER(u32)]
+        lib.mg_walk_sum_mutate_host.argtypes = [p, u32, p, u32, p, p, u32, p, u32, u32, p, u32, p,
+                                                u32, p, p, p, u32, p, u32, p, u32, p, u32, p, u32,
+                                                u32, p, u64, u32, u32, u32, u32, p, p]
         lib.mg_batch_create.argtypes = [p, C.POINTER(p), u32, C.POINTER(p)]
         lib.mg_batch_free.argtypes = [p]
         lib.mg_batch_free.restype = None
@@ -585,6 +591,59 @@ class Engine:
         return WalkResult(out[:, :n_leaves], nfail.astype(np.int64), cost.astype(np.int64),
                           int(rounds.value), trace, int(winner.value), self.last_kernel_ms())
 
+    def walk_sum(self, lp: LoadedProgram, starts: np.ndarray, n_roots: int, trees, bounds, ufs,
+                 sums, seed: int, lanes: int = 4096, max_rounds: int = 64, sync_every: int = 8,
+                 mask_probe0: int = 0, n_resid: Optional[int] = None):
+        """Tree-scored walk with aims through sums, differences, masks and
+        shifts (mg_walk_sum): :meth:`walk_uf` whose entries
+        may be linear (``sums``: ``repair.Sums``, its ``lin`` words parallel to
+        ``bounds.entries``); the program writes ``sums.n_srows`` side rows
+        after the residual probes and before the U rows.  With no linear entry
+        it is :meth:`walk_uf` bit for bit."""
+        from .repair import WalkResult
+        n_leaves = len(lp.program.leaves)
+        starts = np.ascontiguousarray(starts, dtype=np.uint32)
+        if starts.ndim != 3 or starts.shape[1:] != (n_leaves, 8):
+            raise ValueError("starts must be (walkers, n_leaves, 8)")
+        walkers = starts.shape[0]
+        roots = np.ascontiguousarray(trees.roots, dtype=np.uint32)
+        atoms = np.ascontiguousarray(trees.atoms, dtype=np.uint32)
+        code = np.ascontiguousarray(trees.code, dtype=np.uint32)
+        if roots.shape != (max(0, int(n_roots)),) and 1 <= int(n_roots) <= 1024:
+            raise ValueError("trees.roots must have n_roots entries")
+        entries = np.ascontiguousarray(bounds.entries, dtype=np.uint32)
+        pieces = np.ascontiguousarray(bounds.pieces, dtype=np.uint32)
+        fixed = np.ascontiguousarray(bounds.fixed, dtype=np.uint32)
+        lin = np.ascontiguousarray(sums.lin, dtype=np.uint32)
+        if entries.shape[1:] != (5,) or pieces.shape[1:] != (4,) or \
+                fixed.shape != (entries.shape[0], 8) or lin.shape != (entries.shape[0],):
+            raise ValueError("bounds.entries must be (n, 5), bounds.pieces (m, 4), "
+                             "bounds.fixed (n, 8), sums.lin (n,)")
+        tabs = _uf_arrays(ufs)
+        n_resid = len(trees.probes) if n_resid is None else n_resid
+        w1, r1 = max(1, min(walkers, 64)), max(1, min(int(max_rounds), 1 << 16))
+        out = np.zeros((w1, max(1, n_leaves), 8), dtype=np.uint32)
+        nfail, cost = np.zeros(w1, dtype=np.uint32), np.zeros(w1, dtype=np.uint32)
+        trace = np.zeros((w1, r1, 2), dtype=np.uint32)
+        rounds, winner = C.c_uint32(0), C.c_uint32(0)
+        rc = self.lib.mg_walk_sum(self._ctx, lp.handle,
+                                  _ptr(starts) if starts.size else _ptr(out), walkers,
+                                  max(0, int(n_roots)), mask_probe0,
+                                  _ptr(roots) if roots.size else _ptr(nfail), atoms.size,
+                                  _ptr(atoms) if atoms.size else None,
+                                  _ptr(code) if code.size else None, code.size,
+                                  max(0, int(n_resid)),
+                                  _ptr(entries) if entries.size else None, entries.shape[0],
+                                  _ptr(pieces) if pieces.size else None, pieces.shape[0],
+                                  _ptr(fixed) if fixed.size else None,
+                                  _ptr(lin) if lin.size else None, max(0, int(sums.n_srows)),
+                                  *_uf_args(tabs), max(0, int(ufs.n_urows)), seed & (2**64 - 1),
+                                  lanes, max_rounds, sync_every, _ptr(out), _ptr(nfail),
+                                  _ptr(cost), C.byref(rounds), _ptr(trace), C.byref(winner))
+        self._check(rc, "mg_walk_sum")
+        return WalkResult(out[:, :n_leaves], nfail.astype(np.int64), cost.astype(np.int64),
+                          int(rounds.value), trace, int(winner.value), self.last_kernel_ms())
+
     def witness(self, lp: LoadedProgram, seed: int, index: int):
         """Leaves and probe values of candidate ``index`` (one lane): what a
         solve-mode program's model needs besides the generated leaves."""
@@ -917,6 +976,59 @@ def walk_uf_mutate_host(leafgen: Sequence[LeafGen], consts: np.ndarray, base: np
         seed & (2**64 - 1), r, lanes, lane0, n_lanes, _ptr(out), _ptr(moves))
     if rc != 0:
         raise EngineError("mg_walk_uf_mutate_host failed (%d)" % rc)
+    return out[:len(gens), :, :n_lanes], moves[:n_lanes]
+
+
+def walk_sum_mutate_host(leafgen: Sequence[LeafGen], consts: np.ndarray, base: np.ndarray,
+                         state, bounds, ufs, sums, seed: int, r: int, lanes: int, lane0: int = 0,
+                         n_lanes: Optional[int] = None, n_resid: Optional[int] = None):
+    """Host-only (no GPU): :func:`walk_uf_mutate_host` for the lane function
+    of mg_walk_sum (mg_walk_sum_mutate_host; ``repair.sum_mutate_ref`` is its
+    specification).  ``state``: ``(rvals, root bits, atom bits, dest (n_slots,)
+    u32, srows (n_srows, 8) u32)``, None in round 0."""
+    from .repair import bound_mask_words
+    lib = load_library()
+    gens = list(leafgen)
+    garr = (LeafGen * max(1, len(gens)))(*gens)
+    consts = np.ascontiguousarray(consts, dtype=np.uint32).reshape(-1, 8)
+    base = np.ascontiguousarray(base, dtype=np.uint32)
+    entries = np.ascontiguousarray(bounds.entries, dtype=np.uint32).reshape(-1, 5)
+    pieces = np.ascontiguousarray(bounds.pieces, dtype=np.uint32).reshape(-1, 4)
+    fixed = np.ascontiguousarray(bounds.fixed, dtype=np.uint32).reshape(-1, 8)
+    lin = np.ascontiguousarray(sums.lin, dtype=np.uint32).reshape(-1)
+    tabs = _uf_arrays(ufs)
+    rvals = mvals = svals = None
+    n_roots, n_atoms = bounds.n_roots, bounds.n_atoms
+    dest = np.full(max(1, tabs[0].shape[0]), 0xFFFFFFFF, dtype=np.uint32)
+    if state is not None:
+        rvals = np.ascontiguousarray(state[0], dtype=np.uint32).reshape(-1, 8)
+        n_roots, n_atoms = len(state[1]), len(state[2])
+        mvals = np.concatenate([bound_mask_words(state[1]), bound_mask_words(state[2]),
+                                np.zeros(1, dtype=np.uint32)])
+        dest[:tabs[0].shape[0]] = np.asarray(state[3], dtype=np.uint32)
+        svals = np.ascontiguousarray(state[4], dtype=np.uint32).reshape(-1, 8)
+        if svals.shape[0] < sums.n_srows:
+            raise EngineError("mg_walk_sum_mutate_host: srows shorter than n_srows")
+    if n_resid is None:
+        n_resid = rvals.shape[0] if rvals is not None else \
+            (int(entries[:, 0].max()) + 1 if entries.size else 0)
+    if rvals is not None and rvals.shape[0] < n_resid:
+        raise EngineError("mg_walk_sum_mutate_host: rvals shorter than n_resid")
+    n_lanes = lanes - lane0 if n_lanes is None else n_lanes
+    out = np.zeros((max(1, len(gens)), 8, max(1, n_lanes)), dtype=np.uint32)
+    moves = np.zeros((max(1, n_lanes), 5), dtype=np.uint32)
+    rc = lib.mg_walk_sum_mutate_host(
+        C.cast(garr, C.c_void_p), len(gens), _ptr(consts), consts.shape[0], _ptr(base),
+        _ptr(rvals) if rvals is not None and rvals.size else None, n_resid,
+        _ptr(mvals) if mvals is not None else None, n_roots, n_atoms,
+        _ptr(entries) if entries.size else None, entries.shape[0],
+        _ptr(pieces) if pieces.size else None, pieces.shape[0],
+        _ptr(fixed) if fixed.size else None, _ptr(lin) if lin.size else None,
+        _ptr(svals) if svals is not None and svals.size else None, int(sums.n_srows),
+        *_uf_args(tabs), int(ufs.n_urows), _ptr(dest),
+        seed & (2**64 - 1), r, lanes, lane0, n_lanes, _ptr(out), _ptr(moves))
+    if rc != 0:
+        raise EngineError("mg_walk_sum_mutate_host failed (%d)" % rc)
     return out[:len(gens), :, :n_lanes], moves[:n_lanes]
 
 

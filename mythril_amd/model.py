@@ -195,9 +195,12 @@ REFUTE = True              # host refutation before compiling (refute.py)
 # MYTHRIL_GPU_REPAIR=4: to the tree-scored walk with aimed moves (§3.12);
 # MYTHRIL_GPU_REPAIR=5: to that walk with aims for orders too (§3.13);
 # MYTHRIL_GPU_REPAIR=6: and with aims that write the table entry a UF
-# application reads (§3.14)
+# application reads (§3.14);
+# MYTHRIL_GPU_REPAIR=7: and with aims through sums, differences, masks and
+# shifts (§3.15)
 REPAIR = False
-REPAIR_SCORED = False      # repair_group's `scored`: False, True, "tree", "aim", "bound" or "uf"
+# repair_group's `scored`: False, True, "tree", "aim", "bound", "uf" or "sum"
+REPAIR_SCORED = False
 REPAIR_WALKERS = 16
 SHAPE_MIN, SHAPE_FLOOR, SHAPE_PROBE = 4, 1.0 / 16, 8
 
@@ -217,7 +220,8 @@ def configure_from_env(env=None) -> None:
     aimed by a failing equality's residual, ``MYTHRIL_GPU_REPAIR=5`` that walk
     with moves aimed by a failing order's difference as well,
     ``MYTHRIL_GPU_REPAIR=6`` that walk with aims for the outputs of
-    uninterpreted functions too."""
+    uninterpreted functions too, ``MYTHRIL_GPU_REPAIR=7`` that walk with aims
+    through sums, differences, masks and shifts too."""
     global GPU_ENABLED, DEVICES, SEARCH_CANDIDATES, SEARCH_BUDGET_MS, SHAPE_GATE, REFUTE, REPAIR
     global REPAIR_SCORED
     import os
@@ -234,7 +238,8 @@ def configure_from_env(env=None) -> None:
     SHAPE_GATE = env.get("MYTHRIL_GPU_ADAPTIVE", "1").strip().lower() not in ("0", "off", "false",
                                                                              "no")
     REFUTE = env.get("MYTHRIL_GPU_REFUTE", "1").strip().lower() not in ("0", "off", "false", "no")
-    REPAIR_SCORED = {"2": True, "3": "tree", "4": "aim", "5": "bound", "6": "uf"}.get(
+    REPAIR_SCORED = {"2": True, "3": "tree", "4": "aim", "5": "bound", "6": "uf",
+                     "7": "sum"}.get(
         env.get("MYTHRIL_GPU_REPAIR", "0").strip(), False)
     REPAIR = bool(REPAIR_SCORED) or env.get("MYTHRIL_GPU_REPAIR", "0").strip().lower() in (
         "1", "on", "true", "yes")
@@ -840,7 +845,7 @@ def gpu_search(nodes: Sequence[N.Node], budget_ms: float):
 def _repair_misses(buckets, hits, budget_ms: float, t_start: float):
     """``hits`` with every missed group the local search repairs
     (``repair.repair_group``, MYTHRIL_GPU_REPAIR=1, 2: scored, 3: trees, 4: aimed, 5: orders
-    too, 6: UF outputs too) replaced by (0, its
+    too, 6: UF outputs too, 7: sums too) replaced by (0, its
     assignment), as long as search budget remains; stops at the first group
     it cannot repair (the query is a miss then).  The witness goes through
     ``_accept`` like any other."""
@@ -1199,7 +1204,8 @@ def repair_miss(constraints, **kw) -> dict:
     ``scored``, ``walkers`` for the scored walk of DESIGN.md §3.10, ``scored="tree"``
     for its tree distances of §3.11, ``scored="aim"`` for the aimed moves of
     §3.12, ``scored="bound"`` for the aims for orders of §3.13, ``scored="uf"`` for the
-    aims for UF outputs of §3.14): ``groups``
+    aims for UF outputs of §3.14, ``scored="sum"`` for the aims through sums
+    of §3.15): ``groups``
     and, when every group was repaired, the joined ``model``.  Touches no
     memo, gate or counter; the model is not verified by z3 here."""
     from .repair import repair

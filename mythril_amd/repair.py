@@ -286,7 +286,7 @@ class WalkResult:
 
 def walk_ref(values_fn: Callable, leafgen, consts, starts, table, seed: int, lanes: int = 4096,
              max_rounds: int = 64, sync_every: int = 8, score: Optional[Callable] = None,
-             aims=None, bounds=None, ufs=None) -> WalkResult:
+             aims=None, bounds=None, ufs=None, sums=None) -> WalkResult:
     """The whole loop as ``mg_walk`` runs it.  ``values_fn`` maps an SoA leaf
     array ``(n_leaves, 8, n)`` to ``(bits (n, n_roots) bool, resid (n_resid,
     8, n) u32)``: the verdicts and the residual values.  Walker w moves under
@@ -311,7 +311,12 @@ def walk_ref(values_fn: Callable, leafgen, consts, starts, table, seed: int, lan
     ``values_fn`` returns ``(bits, abits, resid, urows)``, the walker keeps the
     adopted lane's U rows ``urows[:, :, lane]`` and resolves its slots after
     each adoption (:func:`uf_resolve_ref` on the new base), and the neighbours
-    are those of :func:`uf_mutate_ref`."""
+    are those of :func:`uf_mutate_ref`.
+
+    ``sums``: with ``bounds`` and ``ufs``, the lin words of ``mg_walk_sum``
+    (:func:`sum_table`): ``values_fn`` returns ``(bits, abits, resid, urows,
+    srows)``, the walker also keeps the adopted lane's side rows ``srows[:, :,
+    lane]``, and the neighbours are those of :func:`sum_mutate_ref`."""
     bases = np.ascontiguousarray(starts, dtype=np.uint32).copy()
     walkers = bases.shape[0]
     if not 1 <= walkers <= MAX_WALKERS or bases.shape[2:] != (8,):
@@ -324,7 +329,11 @@ def walk_ref(values_fn: Callable, leafgen, consts, starts, table, seed: int, lan
     while r < max_rounds and not any(k is not None and k[0] == 0 for k in keys):
         stop = max_rounds if max_rounds - r < sync_every else r + sync_every
         while r < stop:
-            if ufs is not None:
+            if sums is not None:
+                nb = np.concatenate([sum_mutate_ref(leafgen, consts, bases[w], rvals[w], bounds,
+                                                    sums, seed ^ (w * CW & M64), r, lanes)
+                                     for w in range(walkers)], axis=2)
+            elif ufs is not None:
                 nb = np.concatenate([uf_mutate_ref(leafgen, consts, bases[w], rvals[w], bounds,
                                                    seed ^ (w * CW & M64), r, lanes)
                                      for w in range(walkers)], axis=2)
@@ -340,8 +349,10 @@ def walk_ref(values_fn: Callable, leafgen, consts, starts, table, seed: int, lan
                                                     seed ^ (w * CW & M64), r, lanes)
                                      for w in range(walkers)], axis=2)
             values = values_fn(nb)
-            urows = None
-            if ufs is not None:
+            urows = srows = None
+            if sums is not None:
+                values, urows, srows = values[:3], values[3], values[4]
+            elif ufs is not None:
                 values, urows = values[:3], values[3]
             if score is None:
                 nfail, cost = _score_bits(values[0], values[1], table)
@@ -361,6 +372,8 @@ def walk_ref(values_fn: Callable, leafgen, consts, starts, table, seed: int, lan
                                              dtype=bool))
                         if ufs is not None:
                             rvals[w] += (uf_resolve_ref(bases[w], urows[:, :, at], ufs),)
+                        if sums is not None:
+                            rvals[w] += (np.ascontiguousarray(srows[:, :, at]),)
                     elif aims is not None:
                         rvals[w] = np.ascontiguousarray(values[-1][:, :, w * lanes + lane])
                 trace[w, r] = key
@@ -809,23 +822,90 @@ def _fold_key(i, subst) -> Optional[int]:
     return None
 
 
-def aim_pieces(t, program, _slots=None) -> Optional[list]:
+def aim_pieces(t, program, _slots=None, _rules: bool = False) -> Optional[list]:
     """The pieces ``[(leaf, leaf_bit, value_bit, len)]`` of the bit-vector
     term ``t`` as a destination, ``value_bit`` relative to
     ``t``'s bit 0; None when ``t`` does not resolve.  A numeral resolves to no
-    piece."""
-    side = _resolve_side(t, program, _slots)
+    piece.  ``_rules``: with the mask and shift rules of §3.15
+    (:func:`sum_table` alone passes it)."""
+    side = _resolve_side(t, program, _slots, _rules)
     return None if side is None else side[0]
 
 
-def _resolve_side(t, program, slots=None) -> Optional[tuple]:
+def _pow2(v: int) -> Optional[int]:
+    """c when v == 2^c, else None."""
+    return v.bit_length() - 1 if v > 0 and v & (v - 1) == 0 else None
+
+
+def _shift_of(t) -> Optional[tuple]:
+    """``(operand, c, left)`` when ``t`` is a shift of one operand by the
+    numeral c: ``bvlshr(x, c)``, ``bvudiv(x, 2^c)``,
+    ``bvshl(x, c)`` or a ``bvmul`` of one non-numeral operand and numerals
+    whose product is 2^c; else None."""
+    if t.op in ("bvlshr", "bvshl") and t.args[1].op == "bvnum" and t.args[0].op != "bvnum":
+        return t.args[0], t.args[1].params[0], t.op == "bvshl"
+    if t.op == "bvudiv" and t.args[1].op == "bvnum" and t.args[0].op != "bvnum":
+        c = _pow2(t.args[1].params[0])
+        return None if c is None else (t.args[0], c, False)
+    if t.op == "bvmul":
+        rest = [a for a in t.args if a.op != "bvnum"]
+        prod = 1
+        for a in t.args:
+            if a.op == "bvnum":
+                prod *= a.params[0]
+        c = _pow2(prod)
+        return None if len(rest) != 1 or c is None else (rest[0], c, True)
+    return None
+
+
+def _mask_of(t) -> Optional[tuple]:
+    """``(operand, keep, ones)`` when ``t`` is ``bvand`` / ``bvor`` of exactly
+    one non-numeral operand and numerals: the bits of the operand that pass
+    (``keep``) and the bits that are fixed ones; else None."""
+    if t.op not in ("bvand", "bvor"):
+        return None
+    rest = [a for a in t.args if a.op != "bvnum"]
+    if len(rest) != 1 or len(rest) == len(t.args):
+        return None
+    full = (1 << t.width) - 1
+    m = full if t.op == "bvand" else 0
+    for a in t.args:
+        if a.op == "bvnum":
+            m = m & a.params[0] if t.op == "bvand" else m | a.params[0]
+    m &= full
+    return (rest[0], m, 0) if t.op == "bvand" else (rest[0], full & ~m, m)
+
+
+def _cut_pieces(pieces, keep: int) -> list:
+    """``pieces`` cut to the runs of set bits of ``keep`` (value bits)."""
+    out = []
+    for l, lb, vb, n in pieces:
+        b = vb
+        while b < vb + n:
+            if not keep >> b & 1:
+                b += 1
+                continue
+            e = b
+            while e < vb + n and keep >> e & 1:
+                e += 1
+            out.append((l, lb + b - vb, b, e - b))
+            b = e
+    return out
+
+
+def _resolve_side(t, program, slots=None, rules: bool = False) -> Optional[tuple]:
     """``(pieces, fixed)`` of ``t`` by the rules of :func:`aim_pieces`;
     ``fixed``: the bits of ``t`` that numerals give (a numeral, or a numeral
     operand of a concat, at its offset; the numeral arm of an ``ite`` gives
     none), as an int.  ``slots`` ({apply node id: slot}, :func:`uf_table`
     alone passes it): an application with a slot u is the one piece ``(UF_SLOT
     | u, 0, 0, width)``, and one at a numeral argument that is a constant key
-    of its function is that entry's ``cval`` leaf."""
+    of its function is that entry's ``cval`` leaf.  ``rules`` (DESIGN.md
+    §3.15): ``bvand`` / ``bvor`` with numerals cut the pieces of their one
+    other operand to the runs of passing bits (the rest is fixed 0, or 1), a
+    right shift by a numeral (``bvlshr``, ``bvudiv`` by 2^c) is ``extract(w -
+    1, c, .)`` zero-extended and a left shift (``bvshl``, ``bvmul`` by 2^c)
+    ``concat(extract(w - 1 - c, 0, .), 0_c)``."""
     leaves = {(l.kind, l.source, l.entry, l.chunk): i for i, l in enumerate(program.leaves)}
     subst = getattr(program.presets, "subst", None) or {}
 
@@ -892,25 +972,68 @@ def _resolve_side(t, program, slots=None) -> Optional[tuple]:
             if key is None or key not in ckeys:
                 return None
             return leafy(cells("cval", name, ckeys.index(key), t.width))
+        if rules and _mask_of(t) is not None:
+            x, keep, ones = _mask_of(t)
+            side = go(x)
+            if side is None:
+                return None
+            return _cut_pieces(side[0], keep), side[1] & keep | ones
+        if rules and _shift_of(t) is not None:
+            x, c, left = _shift_of(t)
+            side = go(x)
+            if side is None:
+                return None
+            w = t.width
+            if c >= w:
+                return [], 0
+            if left:                                     # bits 0 .. w - 1 - c move up by c
+                return ([(l, lb, vb + c, n) for l, lb, vb, n in
+                         _cut_pieces(side[0], (1 << (w - c)) - 1)],
+                        side[1] << c & ((1 << w) - 1))
+            return ([(l, lb, vb - c, n) for l, lb, vb, n in
+                     _cut_pieces(side[0], ((1 << w) - 1) & ~((1 << c) - 1))], side[1] >> c)
         return None
     return go(t)
 
 
-def aim_refusal(t, program, ufs=None) -> Optional[str]:
+def aim_refusal(t, program, ufs=None, rules: bool = False) -> Optional[str]:
     """Why :func:`aim_pieces` does not resolve ``t`` (the first subterm no
     rule takes, with the rule that refused it), None when it resolves.
     ``ufs``: the tables of :func:`uf_table`; an ``apply`` then resolves where
-    it has a slot, and else the reason says why it got none."""
+    it has a slot, and else the reason says why it got none.  ``rules``: with
+    the mask and shift rules of §3.15; a mask or shift those rules do not take
+    says which operand stands in the way."""
     slots = None if ufs is None else ufs.slot_of
-    if aim_pieces(t, program, slots) is not None:
+    if aim_pieces(t, program, slots, rules) is not None:
         return None
     if t.op in ("concat", "extract", "zero_extend"):
-        return next(r for r in (aim_refusal(a, program, ufs) for a in t.args) if r)
+        return next((r for r in (aim_refusal(a, program, ufs, rules) for a in t.args) if r),
+                    "%s over a sum: only the top of a side is flattened" % t.op)
     if t.op == "ite" and t.is_bv():
         _, x, y = t.args
         if x.op == "bvnum" or y.op == "bvnum":
-            return aim_refusal(y if x.op == "bvnum" else x, program, ufs)
+            return aim_refusal(y if x.op == "bvnum" else x, program, ufs, rules)
         return "ite: neither arm is a numeral"
+    if rules and t.op in ("bvand", "bvor"):
+        got = _mask_of(t)
+        if got is None:
+            return "%s: not one operand and numerals" % t.op
+        return aim_refusal(got[0], program, ufs, rules)
+    if rules and t.op in ("bvlshr", "bvshl", "bvudiv", "bvmul"):
+        got = _shift_of(t)
+        if got is None:
+            return "%s: not one operand and %s" % (
+                t.op, "a numeral shift" if t.op in ("bvlshr", "bvshl") else "a numeral 2^c")
+        return aim_refusal(got[0], program, ufs, rules)
+    if rules and t.op in ("bvadd", "bvsub", "bvneg"):
+        terms = linear_terms(t)
+        if terms is None:
+            return "%s: more than %d terms, or wider than %d bits" % (t.op, SUM_MAX_TERMS,
+                                                                     RESIDUAL_BITS)
+        why = [sum_target(t, i, program) for i in range(len(terms))]
+        if all(isinstance(w, str) for w in why):
+            return "%s: no eligible target (%s)" % (t.op, "; ".join(dict.fromkeys(why)))
+        return None
     if t.op == "apply" and ufs is not None:
         name = t.params[0]
         if t.width > RESIDUAL_BITS:
@@ -1559,6 +1682,269 @@ def uf_mutate_ref(leafgen, consts, base, state, bounds: Bounds, seed: int, r: in
 
 
 # ---------------------------------------------------------------------------
+# aims through sums: a side that is a sum of +-terms moves
+# by moving one of its terms
+# ---------------------------------------------------------------------------
+
+# the constants of csrc/mg_walk_sum.h
+SUM_LINEAR, SUM_NEG, SUM_ROW_SHIFT = 1, 2, 8
+SUM_MAX_ROWS, SUM_MAX_TERMS = 64, 4
+
+
+@dataclass
+class Sums:
+    """What ``mg_walk_sum`` adds to the tables of ``mg_walk_uf``
+    (``csrc/mg_walk_sum.h``)."""
+    lin: np.ndarray            # (n_entries,) u32: 0, or LINEAR | NEG? | side row << 8
+    n_srows: int = 0           # side rows the program writes after the residuals
+    probes: tuple = ()         # per side row its node (sum_probes)
+
+    @property
+    def n_linear(self) -> int:
+        return int((self.lin != 0).sum())
+
+
+def no_sums(n_entries: int = 0) -> Sums:
+    return Sums(np.zeros(n_entries, dtype=np.uint32))
+
+
+def make_sums(words, n_srows: int = 0) -> Sums:
+    """``Sums`` of one ``None`` (not linear) or ``(sign, side row)`` per entry."""
+    lin = [0 if w is None else SUM_LINEAR | (SUM_NEG if w[0] < 0 else 0) | w[1] << SUM_ROW_SHIFT
+           for w in words]
+    return Sums(np.array(lin, dtype=np.uint32).reshape(-1), n_srows)
+
+
+def linear_terms(t) -> Optional[list]:
+    """``[(sign, term)]``, the non-numeral terms of the side ``t`` in order,
+    when ``t`` is linear by its nodes: at most 256 bits
+    wide, a ``bvadd``, ``bvsub`` or ``bvneg`` at the top, and 1 .. 4 terms
+    after flattening ``bvadd`` (n-ary, nested), ``bvsub(x, y)`` as ``x + (-y)``
+    and ``bvneg``; numerals are dropped (the move is a difference).  Else
+    None.  Nothing under another operator is flattened."""
+    if not t.is_bv() or t.width > RESIDUAL_BITS or t.op not in ("bvadd", "bvsub", "bvneg"):
+        return None
+    out = []
+
+    def go(t, sign):
+        if t.op == "bvadd":
+            for a in t.args:
+                go(a, sign)
+        elif t.op == "bvsub":
+            go(t.args[0], sign)
+            go(t.args[1], -sign)
+        elif t.op == "bvneg":
+            go(t.args[0], -sign)
+        elif t.op != "bvnum":
+            out.append((sign, t))
+    go(t, 1)
+    return out if 1 <= len(out) <= SUM_MAX_TERMS else None
+
+
+def _names(t) -> set:
+    """The names of the variables, arrays and functions under ``t``."""
+    out, seen, todo = set(), set(), [t]
+    while todo:
+        n = todo.pop()
+        if n.id in seen:
+            continue
+        seen.add(n.id)
+        if n.op in ("var", "array", "apply"):
+            out.add(n.params[0])
+        todo.extend(n.args)
+    return out
+
+
+def sum_target(t, i: int, program, slots=None):
+    """Term ``i`` of the linear side ``t`` as a target: ``(sign, pieces,
+    fixed)`` when it is eligible, else the reason as a string.  Eligible: it
+    resolves with the rules of §3.15 to 1 .. 64 pieces, none a UF slot, none
+    on a leaf the program derives, and no variable, array or function its
+    leaves come from occurs under another term of the side."""
+    terms = linear_terms(t)
+    sign, x = terms[i]
+    res = _resolve_side(x, program, slots, True)
+    if res is None:
+        return aim_refusal(x, program, None, True) or "%s is not a destination" % x.op
+    ps, fixed = res
+    if not ps:
+        return "a term without a piece"
+    if len(ps) > AIM_MAX_PIECES:
+        return "a term of more than %d pieces" % AIM_MAX_PIECES
+    if any(l & UF_SLOT for l, *_ in ps):
+        return "a UF slot piece in a sum"
+    if any(l in program.derived for l, *_ in ps):
+        return "a term on a derived leaf"
+    mine = {program.leaves[l].source for l, *_ in ps}
+    for k, (_, other) in enumerate(terms):
+        if k != i and mine & _names(other):
+            return "a leaf shared with another term"
+    return sign, ps, fixed
+
+
+def sum_probes(trees: Trees) -> list:
+    """The linear sides that need a side row, from the nodes alone (DESIGN.md
+    §3.15): the sides of every residual probe ``bvxor(a, b)`` that a HAMMING
+    atom or simple root of ``trees`` reads, in probe order, ``a`` then ``b``,
+    that :func:`linear_terms` takes; distinct by id in first-seen order; at
+    most 64, the first ones.  Compiled as user probes after the residuals."""
+    out, seen = [], set()
+    for p in _read_probes(trees):
+        node = trees.probes[p]
+        if node.op != "bvxor" or len(node.args) != 2:
+            continue
+        e = [int(x) for x in list(trees.atoms) + [r for r in trees.roots if not int(r) & WT_TREE]
+             if int(x) & 0xFFFF == p]
+        if not any(x >> 16 == HAMMING for x in e):
+            continue
+        for t in node.args:
+            if t.id not in seen and linear_terms(t) is not None:
+                seen.add(t.id)
+                out.append(t)
+    return out[:SUM_MAX_ROWS]
+
+
+def sum_table(constraints: Sequence, trees: Trees, program, apps: Sequence) -> tuple:
+    """``(Bounds, Ufs, Sums)`` of ``mg_walk_sum`` on
+    ``program``, compiled with the side rows of :func:`sum_probes` after the
+    residuals and the argument probes of ``apps`` after them.  The ``Ufs`` are
+    :func:`uf_table`'s.  The entries follow its procedure and order — the XOR
+    entries of :func:`aim_table`, then the order entries of
+    :func:`bound_table` — with the mask and shift rules of §3.15 on: where a
+    side resolves it gives the entry it gives there (``lin`` 0); else, where
+    :func:`linear_terms` takes it, one entry per eligible target
+    (:func:`sum_target`) in term order, with the side's row, mode and truth
+    and the target's pieces and fixed bits, ``lin`` = LINEAR, NEG for a
+    negative term and, in XOR mode, the side's row among :func:`sum_probes`
+    (a side past the 64 rows gets no XOR entry).  At most 256 entries, the
+    first ones."""
+    constraints = list(constraints)
+    _, ufs = uf_table(constraints, trees, program, apps)
+    slots = ufs.slot_of if len(ufs) else None
+    sides_with_row = sum_probes(trees)
+    row_of = {t.id: i for i, t in enumerate(sides_with_row)}
+    rows, sides, words = [], [], []
+
+    def side_entries(p, t, side, mode, truth):
+        res = _resolve_side(t, program, slots, True)
+        if res is not None:
+            if res[0] and len(res[0]) <= AIM_MAX_PIECES and \
+                    not any(l in program.derived for l, *_ in res[0]):
+                rows.append((p, res[0], mode, truth, 0 if mode == BOUND_XOR else res[1]))
+                sides.append(side)
+                words.append(None)
+            return
+        terms = linear_terms(t)
+        if terms is None or (mode == BOUND_XOR and t.id not in row_of):
+            return
+        for i in range(len(terms)):
+            got = sum_target(t, i, program, slots)
+            if isinstance(got, str):
+                continue
+            sign, ps, fixed = got
+            rows.append((p, ps, mode, truth, fixed))
+            sides.append(side)
+            words.append((sign, row_of[t.id] if mode == BOUND_XOR else 0))
+
+    used = set()
+    for e in list(trees.atoms) + [r for r in trees.roots if not int(r) & WT_TREE]:
+        if int(e) >> 16 == HAMMING:
+            used.add(int(e) & 0xFFFF)
+    for p in sorted(used):
+        node = trees.probes[p]
+        if node.op != "bvxor" or len(node.args) != 2:
+            continue
+        for side, t in enumerate(node.args):
+            side_entries(p, t, side, BOUND_XOR, 0)
+
+    def order(node, truth, negated=False):
+        got = order_sides(node, negated)
+        if got is None:
+            return
+        lo, hi, strict = got
+        p = _order_probe(trees, lo, hi)
+        if p is None:
+            return
+        for side, t in enumerate((lo, hi)):
+            side_entries(p, t, side, (BOUND_LOW, BOUND_HIGH)[side] + int(strict), truth)
+
+    for i, e in enumerate(trees.atoms):
+        if int(e) >> 16 == MAGNITUDE:
+            order(trees.atom_nodes[i], BOUND_ATOM | i)
+    for k, c in enumerate(constraints):
+        if trees.is_tree(k) or trees.kind(k) != MAGNITUDE:
+            continue
+        d, neg = peel(c)
+        if d.op not in _NEGATED_ORDER:
+            continue
+        order(d, k, neg)
+    bounds = make_bounds(rows[:AIM_MAX_ENTRIES], len(constraints), trees.n_atoms)
+    bounds.sides = sides[:AIM_MAX_ENTRIES]
+    sums = make_sums(words[:AIM_MAX_ENTRIES], len(sides_with_row))
+    sums.probes = tuple(sides_with_row)
+    return bounds, ufs, sums
+
+
+def sum_mutate_ref(leafgen, consts, base, state, bounds: Bounds, sums: Sums, seed: int, r: int,
+                   lanes: int) -> np.ndarray:
+    """``[n_leaves][8][lanes]`` u32: the neighbours of ``base`` that round
+    ``r`` of ``mg_walk_sum`` evaluates — the specification of
+    ``csrc/mg_walk_sum.h``.  :func:`uf_mutate_ref` (its picks and live list
+    too) under ``state`` = (residual values, root bits, atom bits, slot
+    destinations, side rows (n_srows, 8) u32), where a linear entry (``sums.lin``)
+    gathers its target's value ``V = fixed | OR ((base[leaf] >> leaf_bit) &
+    mask(len)) << value_bit``, takes with R its residual value, s = 1 for the
+    strict modes and S its side row's value
+    ``X = V - sign (R + s)`` (LOW), ``V + sign (R + s)`` (HIGH) or ``V + sign
+    ((S ^ R) - S)`` (XOR) mod 2^256, and replaces, in piece order, bits
+    ``leaf_bit ..`` of the lane's current value of the leaf by ``(X >>
+    value_bit) & mask(len)``."""
+    base = np.ascontiguousarray(base, dtype=np.uint32).reshape(-1, 8)
+    picks = uf_picks_ref(state, bounds, r, lanes)
+    n1 = int((picks != AIM_NONE).sum()) // 2
+    out = np.repeat(base[:, :, None], lanes, axis=2)
+    moves = moves_ref(leafgen, consts, base, seed, r, lanes)
+    bvals = _ints(base)
+    rv = _ints(np.asarray(state[0], dtype=np.uint32).reshape(-1, 8)) if n1 else []
+    sv = _ints(np.asarray(state[4], dtype=np.uint32).reshape(-1, 8)) if n1 else []
+    for lane in range(lanes):
+        cur = {}
+        if picks[lane] != AIM_NONE:
+            e = int(picks[lane])
+            p, _, _, mode, _ = (int(x) for x in bounds.entries[e])
+            R, lw = rv[p], int(sums.lin[e])
+            ps = [(_uf_leaf(leaf, state[3]), lb, vb, n) for leaf, lb, vb, n in bounds.of(e)]
+            if mode == BOUND_XOR and not lw:
+                for leaf, leaf_bit, value_bit, n in ps:
+                    cur[leaf] = cur.get(leaf, bvals[leaf]) ^ (
+                        (R >> value_bit & ((1 << n) - 1)) << leaf_bit)
+            else:
+                V = bounds.fixed_of(e)
+                for leaf, leaf_bit, value_bit, n in ps:
+                    V |= (bvals[leaf] >> leaf_bit & ((1 << n) - 1)) << value_bit
+                s = 1 if mode in (BOUND_LOW_STRICT, BOUND_HIGH_STRICT) else 0
+                up = mode >= BOUND_HIGH
+                d = R + s
+                if lw:
+                    if mode == BOUND_XOR:
+                        S = sv[lw >> SUM_ROW_SHIFT & 0xFF]
+                        d, up = (S ^ R) - S, True
+                    if lw & SUM_NEG:
+                        up = not up
+                T = (V + d if up else V - d) & M256
+                for leaf, leaf_bit, value_bit, n in ps:
+                    m = (1 << n) - 1
+                    cur[leaf] = (cur.get(leaf, bvals[leaf]) & ~(m << leaf_bit)) | (
+                        (T >> value_bit & m) << leaf_bit)
+        if lane > n1:
+            for leaf, _, v in moves[lane]:
+                cur[leaf] = v
+        for leaf, v in cur.items():
+            out[leaf, :, lane] = np.frombuffer(v.to_bytes(32, "little"), dtype="<u4")
+    return out
+
+
+# ---------------------------------------------------------------------------
 # repair a missed group
 # ---------------------------------------------------------------------------
 
@@ -1619,7 +2005,17 @@ def repair_group(nodes: Sequence, n_cand: int = 1 << 16, form: str = "search", l
     of :func:`uf_table` (``bounds`` and ``ufs`` in the result); ``scoring`` is
     ``"uf"`` when a slot piece is in the table.  When that program does not
     compile, a probe is folded away or no slot piece results, the group runs
-    exactly as ``scored="bound"`` does."""
+    exactly as ``scored="bound"`` does.
+
+    ``scored="sum"``: the same with aims through sums, differences, masks and
+    shifts (``mg_walk_sum``): compiled as ``"uf"`` plus the
+    side rows of :func:`sum_probes` between the residuals and the argument
+    probes, then the tables of :func:`sum_table` (``bounds``, ``ufs`` and
+    ``sums`` in the result); ``scoring`` is ``"sum"`` when a linear entry is in
+    the table.  When that program does not compile or a probe is folded away,
+    the group falls back to ``"uf"`` and onward; with no linear entry it runs
+    exactly as ``scored="uf"`` does on the table of :func:`sum_table` (the
+    mask and shift rules may have added plain entries to it)."""
     from . import census as CS
     from . import model as M
     from .assign import unpack
@@ -1639,8 +2035,10 @@ def repair_group(nodes: Sequence, n_cand: int = 1 << 16, form: str = "search", l
         return out
     # (built before the mask: a program's schedule follows the node ids, and a
     # wide mask leaves the compiler's spill budget little room)
-    trees = distance_trees(nodes) if scored in ("tree", "aim", "bound", "uf") else None
-    apps, uprobes = uf_probes(trees) if scored == "uf" else ([], [])
+    trees = distance_trees(nodes) if scored in ("tree", "aim", "bound", "uf", "sum") else None
+    apps, uprobes = uf_probes(trees) if scored in ("uf", "sum") else ([], [])
+    sprobes = sum_probes(trees) if scored == "sum" else []
+    summed = False                                       # compiled with the side rows
     resid, table = residuals(nodes) if scored else ([], flat_table(len(nodes)))
     n_amask = 0
     try:
@@ -1653,7 +2051,19 @@ def repair_group(nodes: Sequence, n_cand: int = 1 << 16, form: str = "search", l
             # the atom mask and the trees' residuals; else the table's, below
             extra = CS.mask_probes(trees.atom_nodes) + trees.probes
             with_trees = None
-            if apps:
+            if scored == "sum":
+                # the side rows after the residuals, then the arguments
+                try:
+                    with_trees = CS._compile(
+                        nodes, CS.mask_probes(nodes) + extra + sprobes + uprobes, form)
+                except Unsupported:
+                    with_trees = None
+                if with_trees is None or with_trees.n_user_probes != \
+                        masked.n_user_probes + len(extra) + len(sprobes) + len(uprobes):
+                    with_trees, sprobes = None, []
+                else:
+                    summed = True
+            if apps and with_trees is None:
                 # the arguments of the UF slots after the residuals
                 try:
                     with_trees = CS._compile(nodes, CS.mask_probes(nodes) + extra + uprobes, form)
@@ -1667,11 +2077,11 @@ def repair_group(nodes: Sequence, n_cand: int = 1 << 16, form: str = "search", l
                     with_trees = CS._compile(nodes, CS.mask_probes(nodes) + extra, form)
             except Unsupported:
                 with_trees = None
-            if with_trees is not None and \
-                    with_trees.n_user_probes == masked.n_user_probes + len(extra) + len(uprobes):
+            if with_trees is not None and with_trees.n_user_probes == \
+                    masked.n_user_probes + len(extra) + len(sprobes) + len(uprobes):
                 masked, resid, n_amask = with_trees, trees.probes, CS.n_mask_probes(trees.n_atoms)
             else:
-                trees, apps, uprobes = None, [], []
+                trees, apps, uprobes, sprobes, summed = None, [], [], [], False
         if resid and trees is None:
             # residuals the compiler folds or cannot place: the walkers rank by
             # the count alone
@@ -1688,12 +2098,18 @@ def repair_group(nodes: Sequence, n_cand: int = 1 << 16, form: str = "search", l
         out.update(status=CS.UNSUPPORTED, why=str(e))
         return out
     n_mask = CS.n_mask_probes(len(nodes))
-    aims = aim_table(trees, masked) if scored in ("aim", "bound", "uf") and trees is not None \
-        else None
-    bounds = bound_table(nodes, trees, masked) if scored in ("bound", "uf") and trees is not None \
-        else None
-    ufs = no_slots = None
-    if apps:
+    aims = aim_table(trees, masked) if scored in ("aim", "bound", "uf", "sum") and \
+        trees is not None else None
+    bounds = bound_table(nodes, trees, masked) if scored in ("bound", "uf", "sum") and \
+        trees is not None else None
+    ufs = no_slots = sums = None
+    if summed:
+        sbounds, sufs, sums = sum_table(nodes, trees, masked, apps)
+        if len(sbounds):
+            bounds, ufs = sbounds, sufs
+        else:
+            sums = None
+    if apps and sums is None:
         ubounds, ufs = uf_table(nodes, trees, masked, apps)
         if has_slot_piece(ubounds):
             bounds = ubounds
@@ -1701,20 +2117,26 @@ def repair_group(nodes: Sequence, n_cand: int = 1 << 16, form: str = "search", l
             ufs, no_slots = None, ufs
     if bounds is not None and not bounds.n_order and ufs is None:
         bounds = None
-    if scored == "uf":
+    if scored == "sum":
+        out["sums"] = sums if sums is not None else no_sums(len(bounds) if bounds is not None else 0)
+    if scored in ("uf", "sum"):
         out["ufs"] = ufs if ufs is not None else no_slots if no_slots is not None else no_ufs()
-    if scored in ("bound", "uf"):
+    if scored in ("bound", "uf", "sum"):
         out["bounds"] = bounds if bounds is not None else (
             bounds_of_aims(aims if aims is not None else no_aims(), len(nodes),
                            trees.n_atoms if trees is not None else 0))
     if scored:
-        out["scoring"] = ("uf" if ufs is not None else "bound" if bounds is not None else
+        out["scoring"] = ("sum" if sums is not None and sums.n_linear else
+                          "uf" if ufs is not None and (sums is None or has_slot_piece(bounds))
+                          else "bound" if sums is not None and bounds.n_order else
+                          "aim" if sums is not None else
+                          "uf" if ufs is not None else "bound" if bounds is not None else
                           "aim" if aims is not None and len(aims) else
                           "tree" if trees is not None else "table" if resid else "count")
-    if scored in ("aim", "bound", "uf"):
+    if scored in ("aim", "bound", "uf", "sum"):
         out["aims"] = aims if aims is not None else no_aims()
         out["program"] = masked                          # what the table's leaves index
-    if masked.n_user_probes != n_mask + n_amask + len(resid) + len(uprobes):
+    if masked.n_user_probes != n_mask + n_amask + len(resid) + len(sprobes) + len(uprobes):
         out["status"] = CS.DEAD if masked.n_user_probes == 0 else CS.UNSUPPORTED
         out["why"] = "%d mask probes compiled to %d" % (n_mask, masked.n_user_probes)
         return out
@@ -1742,7 +2164,15 @@ def repair_group(nodes: Sequence, n_cand: int = 1 << 16, form: str = "search", l
         starts = np.stack([leaves if i == c.best_index else eng.witness(full, M.SEARCH_SEED, i)[0]
                            for i in picks])
         wide = eng.load(CS.census_view(masked, n_mask + n_amask + len(resid)), gens, prog_seed=0)
-        if trees is not None and ufs is not None:
+        if trees is not None and sums is not None:
+            # the side rows after the residuals, then the U rows: the
+            # arguments, then the kept keys
+            wide = eng.load(uf_view(masked, n_mask + n_amask + len(resid) + len(sprobes) +
+                                    ufs.n_arg_rows, ufs.keep), gens, prog_seed=0)
+            res = eng.walk_sum(wide, starts, len(nodes), trees, bounds, ufs, sums, seed, lanes,
+                               max_rounds, sync_every)
+            out["trees"] = trees
+        elif trees is not None and ufs is not None:
             # the U rows after the residuals: the arguments, then the kept keys
             wide = eng.load(uf_view(masked, n_mask + n_amask + len(resid) + ufs.n_arg_rows,
                                     ufs.keep), gens, prog_seed=0)

@@ -51,6 +51,13 @@ usage: tools/miss_census.py --workload {c1,c3,c3o,c4,c5} --query N
            §3.14): the slots, how many sides of the read residuals resolve with
            and without them, per reason the refused sides, every walker's
            trace, and the device time per round beside scored="bound"
+       ... --walk-sum [--walkers N] [--lanes L] [--rounds R]
+           after the census, that walk with aims through sums, differences,
+           masks and shifts too: the entries, the linear
+           ones and their side rows, how many of the sides §3.14 refused now
+           resolve or are linear and what refused them before, per reason the
+           sides still refused, every walker's trace, and the device time per
+           round beside scored="uf"
        tools/miss_census.py [workload] [n]
            the older census: which of a stream's first n queries the batched
            search misses, grouped by the shape of their newest constraint
@@ -675,6 +682,99 @@ def show_uf(rows, lanes):
                                         g.get("bound_end")))
 
 
+def sum_rows(wl, qi, n_cand, lanes, rounds, walkers):
+    """Per independent group of the query: what ``repair.repair_group(scored=
+    "sum")`` did with ``walkers`` walkers: the entries, how many are linear and
+    how many side rows they read, how many sides of the read residual probes
+    resolve or are linear with an eligible target under the rules of DESIGN.md
+    3.15 beside how many resolved under 3.14's, per reason the sides still
+    refused, every walker's trace, and the device time per round beside
+    scored="uf"'s from the same starts."""
+    import mythril_amd.model as M
+    from mythril_amd import repair as RP
+    from mythril_amd.smt import node as N
+    rows = []
+    for group in M.dependence_buckets(stream_query(wl, qi)):
+        kw = dict(n_cand=n_cand, form="search", lanes=lanes, max_rounds=rounds)
+        g = RP.repair_group(group, scored="sum", walkers=walkers, **kw)
+        row = {"constraints": len(group), "status": g["status"], "scoring": g.get("scoring")}
+        if "why" in g:
+            row["why"] = g["why"]
+        res, T, B, U, S = (g.get(k) for k in ("repair", "trees", "bounds", "ufs", "sums"))
+        if res is not None and T is not None:
+            prog = g["program"]
+            row.update(starts=g["starts"], winner=res.winner, rounds=res.rounds, walkers=walkers,
+                       nfail=[int(v) for v in res.nfail], cost=[int(v) for v in res.cost],
+                       traces=[_runs(res.trace[w, :res.rounds]) for w in range(walkers)],
+                       sum_ms_per_round=round(res.kernel_ms / max(1, res.rounds), 4),
+                       entries=len(B), linear=S.n_linear, side_rows=int(S.n_srows), slots=len(U))
+            # (as sum_table resolves: an application at a numeral key only
+            # where the table has slots)
+            slots = U.slot_of if len(U) else None
+            ufs = U if U.slot_of is not None else None
+            sides = [t for p in RP._read_probes(T) if len(T.probes[p].args) == 2
+                     for t in T.probes[p].args]
+            row["sides"] = len(sides)
+
+            def moves(t):
+                terms = RP.linear_terms(t)
+                return RP.aim_pieces(t, prog, slots, True) is not None or (
+                    terms is not None and any(not isinstance(RP.sum_target(t, i, prog, slots), str)
+                                              for i in range(len(terms))))
+            old = [t for t in sides if RP.aim_pieces(t, prog, slots) is None]
+            new = [t for t in sides if not moves(t)]
+            row["refused_before"] = len(old)
+            gained = [t for t in old if moves(t)]
+            row["gained"] = [{"was": RP.aim_refusal(t, prog, ufs),
+                              "linear": RP.linear_terms(t) is not None,
+                              "term": N.to_sexpr(t, 3)} for t in gained]
+            row["refused"] = [{"why": RP.aim_refusal(t, prog, ufs, True) or
+                               "resolves only in a table that has slots", "uf": t.op == "apply",
+                               "term": N.to_sexpr(t, 3)} for t in new]
+            uf = RP.repair_group(group, scored="uf", walkers=walkers, **kw).get("repair")
+            if uf is not None:
+                row["uf_ms_per_round"] = round(uf.kernel_ms / max(1, uf.rounds), 4)
+                row["uf_rounds"] = uf.rounds
+                row["uf_end"] = [int(uf.nfail[uf.winner]), int(uf.cost[uf.winner])]
+        rows.append(row)
+    return rows
+
+
+def show_sum(rows, lanes):
+    for gi, g in enumerate(rows):
+        print(" sum walk group %d: %d constraints -> %s%s; scoring: %s" % (
+            gi, g["constraints"], g["status"], (" (%s)" % g["why"]) if "why" in g else "",
+            g["scoring"]))
+        if "traces" not in g:
+            continue
+        print("  %d entries, %d linear, %d side rows, %d slots" % (
+            g["entries"], g["linear"], g["side_rows"], g["slots"]))
+        print("  sides of the read residuals: %d; refused before: %d; of them now resolved or "
+              "linear: %d; still refused: %d, %d of them UF applications" % (
+                  g["sides"], g["refused_before"], len(g["gained"]), len(g["refused"]),
+                  sum(e["uf"] for e in g["refused"])))
+        was = collections.OrderedDict()
+        for e in g["gained"]:
+            was.setdefault((e["was"], e["linear"]), []).append(e)
+        for (why, linear), es in was.items():
+            print("   gained: %d sides (%s) that were: %s, e.g. %.120s" % (
+                len(es), "linear" if linear else "pieces", why, es[0]["term"]))
+        rules = collections.OrderedDict()
+        for e in g["refused"]:
+            rules.setdefault(e["why"], []).append(e)
+        for why, es in rules.items():
+            print("   refused: %d sides: %s, e.g. %.120s" % (len(es), why, es[0]["term"]))
+        print("  %d walkers, %d rounds of %d lanes each; winner: walker %d" % (
+            g["walkers"], g["rounds"], lanes, g["winner"]))
+        for w, tr in enumerate(g["traces"]):
+            print("   walker %2d from candidate %d: ends %d/%d; nfail/cost per round: %s" % (
+                w, g["starts"][w], g["nfail"][w], g["cost"][w], tr))
+        print("  device time per round: scored=\"sum\" (%s) x%d %.4f ms; scored=\"uf\" x%d %s ms "
+              "(%s rounds, ends %s)" % (g["scoring"], g["walkers"], g["sum_ms_per_round"],
+                                        g["walkers"], g.get("uf_ms_per_round"),
+                                        g.get("uf_rounds"), g.get("uf_end")))
+
+
 def show(r):
     print("== %s query %d%s: %d constraints, %d candidates per group (%.0f ms in all)" % (
         r["workload"], r["query"], " (top-level ands split, i.j = conjunct j of constraint i)"
@@ -729,6 +829,8 @@ def main():
                     help="then run that walk with aims for orders too (DESIGN.md 3.13)")
     ap.add_argument("--walk-uf", action="store_true",
                     help="then run that walk with aims for UF outputs too (DESIGN.md 3.14)")
+    ap.add_argument("--walk-sum", action="store_true",
+                    help="then run that walk with aims through sums too (DESIGN.md 3.15)")
     ap.add_argument("--walkers", type=int, default=16)
     ap.add_argument("--lanes", type=int, default=4096)
     ap.add_argument("--rounds", type=int, default=64)
@@ -766,6 +868,10 @@ def main():
         for r in reports:
             r["walk_uf"] = uf_rows(r["workload"], r["query"], a.candidates, a.lanes, a.rounds,
                                    a.walkers)
+    if a.walk_sum:
+        for r in reports:
+            r["walk_sum"] = sum_rows(r["workload"], r["query"], a.candidates, a.lanes, a.rounds,
+                                     a.walkers)
     if a.json:
         print(json.dumps(reports, indent=1))
     else:
@@ -783,6 +889,8 @@ def main():
                 show_bound(r["walk_bound"], a.lanes)
             if a.walk_uf:
                 show_uf(r["walk_uf"], a.lanes)
+            if a.walk_sum:
+                show_sum(r["walk_sum"], a.lanes)
 
 
 if __name__ == "__main__":

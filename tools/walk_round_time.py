@@ -2,7 +2,9 @@
 program, starts and XOR-only table (aim_cases `bytes`), in one run: aim, bound,
 aim alternating.  Prints median, min and max of kernel_ms / rounds.
 ``--uf``: mg_walk_uf beside mg_walk_bound instead, on the same slot-free table:
-bound, uf, bound alternating."""
+bound, uf, bound alternating.
+``--sum``: mg_walk_sum beside mg_walk_uf on the same linear-free table, 8
+rounds per call: uf, sum, uf alternating."""
 import os
 import statistics
 import sys
@@ -25,10 +27,16 @@ for walkers in (1, 16):
     aim = lambda: eng.walk_aim(lp, starts, n_roots, T, A, AC.SEED, 4096, 64)
     bound = lambda: eng.walk_bound(lp, starts, n_roots, T, B, AC.SEED, 4096, 64)
     uf = lambda: eng.walk_uf(lp, starts, n_roots, T, B, RP.no_ufs(), AC.SEED, 4096, 64)
-    plan = (("bound_1", bound), ("uf", uf), ("bound_2", bound)) if "--uf" in sys.argv else \
+    uf8 = lambda: eng.walk_uf(lp, starts, n_roots, T, B, RP.no_ufs(), AC.SEED, 4096, 8)
+    sum8 = lambda: eng.walk_sum(lp, starts, n_roots, T, B, RP.no_ufs(), RP.no_sums(len(B)),
+                                AC.SEED, 4096, 8)
+    plan = (("uf_1", uf8), ("sum", sum8), ("uf_2", uf8)) if "--sum" in sys.argv else \
+        (("bound_1", bound), ("uf", uf), ("bound_2", bound)) if "--uf" in sys.argv else \
         (("aim_1", aim), ("bound", bound), ("aim_2", aim))
     if "--uf" in sys.argv:
         aim = uf                                                     # the pair that is compared
+    if "--sum" in sys.argv:
+        aim, bound = sum8, uf8
     a, b = aim(), bound()                                            # warm up, and the same walk
     assert np.array_equal(a.leaves, b.leaves) and np.array_equal(a.trace, b.trace)
     assert a.rounds == b.rounds
