@@ -519,6 +519,80 @@ int mg_walk_sum_mutate_host(const mg_leafgen* leaves, uint32_t n_leaves, const u
                             uint32_t lanes, uint32_t lane0, uint32_t n_lanes, uint32_t* out,
                             uint32_t* moves);
 
+/* The walks of several groups in one launch sequence.  A
+ * job is what mg_walk_sum takes for one program; walkers, lanes, max_rounds
+ * and sync_every are shared by the batch, and the same mg_prog may appear in
+ * several jobs.  Every output of job g (leaves, nfail, cost, rounds, winner,
+ * trace) is byte for byte what mg_walk_sum returns for job g alone with the
+ * same shared arguments — and with empty tables what mg_walk_uf, _bound, _aim
+ * and _tree return, as mg_walk_sum documents.  A round of the batch is four
+ * launches, each n_jobs times as wide as the single walk's; after every
+ * sync_every rounds the host reads all states, and a job one of whose walkers
+ * has no failing root is frozen there, as its single walk would have stopped:
+ * its rounds are fixed, no kernel works on it again and its trace rows past
+ * the stop stay zero.  The batch ends when every job is frozen or after
+ * max_rounds rounds. */
+typedef struct mg_walk_job {
+    const mg_prog* prog;
+    const uint32_t* starts;           /* [walkers][n_leaves][8] */
+    const uint32_t* roots;            /* [n_roots] */
+    const uint32_t* atoms;            /* [n_atoms] or NULL */
+    const uint32_t* code;             /* [n_code] or NULL */
+    const uint32_t* entries;          /* [n_entries][5] or NULL */
+    const uint32_t* pieces;           /* [n_pieces][4] or NULL */
+    const uint32_t* fixed;            /* [n_entries][8] or NULL */
+    const uint32_t* lin;              /* [n_entries] or NULL */
+    const uint32_t *slots, *funcs, *cands, *ukeys;
+    uint32_t* out_leaves;             /* [walkers][n_leaves][8] */
+    uint32_t* out_nfail;              /* [walkers] */
+    uint32_t* out_cost;               /* [walkers] */
+    uint32_t* out_rounds;
+    uint32_t* trace;                  /* [walkers][max_rounds][2] or NULL */
+    uint32_t* out_winner;
+    uint64_t seed;
+    uint32_t n_roots, mask_probe0, n_atoms, n_code, n_resid, n_entries, n_pieces, n_srows,
+             n_slots, n_funcs, n_cands, n_ukeys, n_urows;
+} mg_walk_job;
+/* The counts of one job that size its share of the batch's device buffer. */
+typedef struct mg_walk_shape {
+    uint32_t n_leaves, n_probes;      /* of the job's program */
+    uint32_t n_roots, mask_probe0, n_atoms, n_code, n_resid, n_entries, n_pieces, n_srows,
+             n_slots, n_funcs, n_cands, n_ukeys, n_urows;
+} mg_walk_shape;
+/* Jobs of one batch.  A job of one walker at 4096 lanes is 16 blocks, so 16
+ * jobs fill the device's 256 CUs once and 256 jobs sixteen times over: past
+ * that a wider grid gains nothing, while the states the host reads at every
+ * sync point (16 bytes per walker and job) and the buffer grow with it.  Far
+ * below the 65535 a grid's z dimension allows; callers with more jobs run
+ * several batches (mythril_amd/engine.py walk_batch does). */
+#define MG_WALK_BATCH_MAX_JOBS 256u
+/* max_bytes 0: the batch's device buffer may take this much (1 GiB) */
+#define MG_WALK_BATCH_DEFAULT_BYTES ((uint64_t)1 << 30)
+/* Refused with MG_E_ARG before any upload or launch, the message beginning
+ * "walk_batch:": n_jobs outside 1..MG_WALK_BATCH_MAX_JOBS; walkers, lanes or
+ * max_rounds outside mg_walk_sum's ranges; a null job array, program or
+ * output pointer; a program of another context; a buffer above max_bytes
+ * (the message gives the bytes needed); and, as "walk_batch: job k: ...",
+ * whatever mg_walk_sum refuses for job k. */
+int mg_walk_batch(mg_ctx* ctx, const mg_walk_job* jobs, uint32_t n_jobs, uint32_t walkers,
+                  uint32_t lanes, uint32_t max_rounds, uint32_t sync_every, uint64_t max_bytes);
+/* Host-only (no GPU): the plan of the device buffer mg_walk_batch uses
+ * (csrc/mg_walk_batch.h says what lies where).  out_offsets:
+ * [MG_WALK_BATCH_SHARED + n_jobs * MG_WALK_BATCH_JOB_REGIONS] byte offsets,
+ * the shared regions (descriptors, jobs, frozen words, states, root bits) and
+ * then job by job its 22 regions, the last two its leaf and its probe region;
+ * every region is 256-byte aligned and ends where the next one in address
+ * order begins, the last at *out_bytes.  MG_E_ARG: shared arguments out of
+ * range, a null pointer, or a size beyond 64 bits. */
+#define MG_WALK_BATCH_SHARED 5
+#define MG_WALK_BATCH_JOB_REGIONS 22
+int mg_walk_batch_plan_host(const mg_walk_shape* shapes, uint32_t n_jobs, uint32_t walkers,
+                            uint32_t lanes, uint32_t max_rounds, uint64_t* out_offsets,
+                            uint64_t* out_bytes);
+/* Host-only (no GPU): 1 when the counts of a job are in the ranges
+ * mg_walk_sum accepts (what it checks before it reads a table), else 0. */
+int mg_walk_batch_shape_ok_host(const mg_walk_shape* shape);
+
 /* Corpus batches: many programs, one launch.  Device-pointer API for
  * resident benchmarking; stream is a hipStream_t (NULL = the context's own
  * stream, which the synchronous calls also use).

@@ -31,6 +31,7 @@
 #include "mg_walk_bound.h"
 #include "mg_walk_uf.h"
 #include "mg_walk_sum.h"
+#include "mg_walk_batch.h"
 
 // the interpreter of each register layout (mg_interp_asm.hip, one
 // translation unit per layout; mg_find_layout lists them)
@@ -184,6 +185,13 @@ hipError_t mg_launch_walk_sum_pick(const uint32_t* d_masks, const uint32_t* d_am
                                    uint32_t* d_dests, uint32_t* d_lives, mg_walk_state* d_state,
                                    uint32_t* d_trace, hipStream_t stream);
 
+
+hipError_t mg_launch_walk_batch_round(const mg_walk_batch_job* d_jobs, const uint32_t* d_frozen,
+                                     uint32_t n_jobs, uint32_t r, uint32_t lanes,
+                                     uint32_t walkers, uint32_t max_rounds, hipStream_t stream);
+hipError_t mg_launch_walk_batch_pick(const mg_walk_batch_job* d_jobs, const uint32_t* d_frozen,
+                                    uint32_t n_jobs, uint32_t r, uint32_t lanes, uint32_t walkers,
+                                    uint32_t max_rounds, hipStream_t stream);
 
 struct mg_ctx {
     int device = 0;
@@ -1118,15 +1126,14 @@ struct walk_scoring {
     uint32_t n_srows;
 };
 
-// The scored walk (DESIGN.md §3.10, §3.11).  Rounds are queued back to back;
-// after every sync_every rounds the host reads the walkers' states (16 bytes
-// each) and stops once one of them has no failing root.
-static int walk_run(mg_ctx* ctx, const mg_prog* prog, const uint32_t* starts, uint32_t walkers,
-                    uint32_t n_roots, uint32_t mask_probe0, const walk_scoring& sc,
-                    uint32_t n_resid, uint64_t seed, uint32_t lanes, uint32_t max_rounds,
-                    uint32_t sync_every, uint32_t* out_leaves, uint32_t* out_nfail,
-                    uint32_t* out_cost, uint32_t* out_rounds, uint32_t* trace,
-                    uint32_t* out_winner) {
+// What every walk refuses before it uploads or launches anything (the
+// message in ctx); mg_walk_batch asks the same of each of its jobs.
+static int walk_check(mg_ctx* ctx, const mg_prog* prog, const uint32_t* starts, uint32_t walkers,
+                      uint32_t n_roots, uint32_t mask_probe0, const walk_scoring& sc,
+                      uint32_t n_resid, uint32_t lanes, uint32_t max_rounds,
+                      const uint32_t* out_leaves, const uint32_t* out_nfail,
+                      const uint32_t* out_cost, const uint32_t* out_rounds,
+                      const uint32_t* out_winner) {
     const uint32_t* table = sc.table;
     if (!ctx || !prog || !starts || !table || !out_leaves || !out_nfail || !out_cost ||
         !out_rounds || !out_winner || (sc.n_atoms && !sc.atoms) || (sc.n_code && !sc.code) ||
@@ -1211,6 +1218,24 @@ static int walk_run(mg_ctx* ctx, const mg_prog* prog, const uint32_t* starts, ui
                     "probe buffer; load the census view of the program (census.census_view: "
                     "only the mask and residual probes are written) or pass fewer lanes",
                     prog->n_probes, walkers, lanes, MG_CENSUS_MAX_PROBE_BYTES >> 20);
+    return MG_OK;
+}
+
+// The scored walk (DESIGN.md §3.10, §3.11).  Rounds are queued back to back;
+// after every sync_every rounds the host reads the walkers' states (16 bytes
+// each) and stops once one of them has no failing root.
+static int walk_run(mg_ctx* ctx, const mg_prog* prog, const uint32_t* starts, uint32_t walkers,
+                    uint32_t n_roots, uint32_t mask_probe0, const walk_scoring& sc,
+                    uint32_t n_resid, uint64_t seed, uint32_t lanes, uint32_t max_rounds,
+                    uint32_t sync_every, uint32_t* out_leaves, uint32_t* out_nfail,
+                    uint32_t* out_cost, uint32_t* out_rounds, uint32_t* trace,
+                    uint32_t* out_winner) {
+    int ok = walk_check(ctx, prog, starts, walkers, n_roots, mask_probe0, sc, n_resid, lanes,
+                        max_rounds, out_leaves, out_nfail, out_cost, out_rounds, out_winner);
+    if (ok != MG_OK) return ok;
+    const uint32_t* table = sc.table;
+    const uint32_t n_mask = (n_roots + 255) / 256, n_amask = (sc.n_atoms + 255) / 256;
+    const uint64_t total = (uint64_t)walkers * lanes;
     if (sync_every == 0) sync_every = 8;
     HIPCHECK(ctx, hipSetDevice(ctx->device));
     auto align = [](size_t x) { return (x + 255) & ~(size_t)255; };
@@ -1537,6 +1562,249 @@ int mg_walk_sum(mg_ctx* ctx, const mg_prog* prog, const uint32_t* starts, uint32
     return walk_run(ctx, prog, starts, walkers, n_roots, mask_probe0, sc, n_resid, seed, lanes,
                     max_rounds, sync_every, out_leaves, out_nfail, out_cost, out_rounds, trace,
                     out_winner);
+}
+
+// The walks of several groups in one launch sequence (DESIGN.md §3.16,
+// csrc/mg_walk_batch.h, mg_walk_batch.hip): the round of mg_walk_sum with a
+// job axis, every job stopped at the sync point where its own walk stops.
+static mg_walk_shape walk_job_shape(const mg_walk_job& j) {
+    mg_walk_shape s;
+    s.n_leaves = j.prog->n_leaves;
+    s.n_probes = j.prog->n_probes;
+    s.n_roots = j.n_roots;
+    s.mask_probe0 = j.mask_probe0;
+    s.n_atoms = j.n_atoms;
+    s.n_code = j.n_code;
+    s.n_resid = j.n_resid;
+    s.n_entries = j.n_entries;
+    s.n_pieces = j.n_pieces;
+    s.n_srows = j.n_srows;
+    s.n_slots = j.n_slots;
+    s.n_funcs = j.n_funcs;
+    s.n_cands = j.n_cands;
+    s.n_ukeys = j.n_ukeys;
+    s.n_urows = j.n_urows;
+    return s;
+}
+
+int mg_walk_batch(mg_ctx* ctx, const mg_walk_job* jobs, uint32_t n_jobs, uint32_t walkers,
+                  uint32_t lanes, uint32_t max_rounds, uint32_t sync_every, uint64_t max_bytes) {
+    if (!ctx) return MG_E_ARG;
+    if (n_jobs < 1 || n_jobs > MG_WALK_BATCH_MAX_JOBS)
+        return fail(ctx, MG_E_ARG, "walk_batch: %u jobs outside 1..%u", n_jobs,
+                    MG_WALK_BATCH_MAX_JOBS);
+    if (walkers < 1 || walkers > MG_WALK_MAX_WALKERS)
+        return fail(ctx, MG_E_ARG, "walk_batch: %u walkers outside 1..%u", walkers,
+                    MG_WALK_MAX_WALKERS);
+    if (lanes < 1 || lanes > MG_REPAIR_MAX_LANES)
+        return fail(ctx, MG_E_ARG, "walk_batch: %u lanes outside 1..%u", lanes,
+                    MG_REPAIR_MAX_LANES);
+    if (max_rounds < 1 || max_rounds > MG_REPAIR_MAX_ROUNDS)
+        return fail(ctx, MG_E_ARG, "walk_batch: %u rounds outside 1..%u", max_rounds,
+                    MG_REPAIR_MAX_ROUNDS);
+    if (!jobs) return fail(ctx, MG_E_ARG, "walk_batch: null jobs");
+    std::vector<mg_walk_shape> shapes(n_jobs);
+    for (uint32_t g = 0; g < n_jobs; ++g) {
+        const mg_walk_job& j = jobs[g];
+        if (!j.prog || !j.starts || !j.roots || !j.out_leaves || !j.out_nfail || !j.out_cost ||
+            !j.out_rounds || !j.out_winner)
+            return fail(ctx, MG_E_ARG, "walk_batch: job %u: null program, starts, roots or "
+                        "output pointer", g);
+        if (j.prog->ctx != ctx)
+            return fail(ctx, MG_E_ARG, "walk_batch: job %u: a program of another context", g);
+        const walk_scoring sc = {j.roots, j.atoms, j.n_atoms, j.code, j.n_code, true, true,
+                                 j.entries, j.n_entries, j.pieces, j.n_pieces, true, j.fixed, true,
+                                 {j.slots, j.n_slots, j.funcs, j.n_funcs, j.cands, j.n_cands,
+                                  j.ukeys, j.n_ukeys, j.n_urows}, true, j.lin, j.n_srows};
+        if (walk_check(ctx, j.prog, j.starts, walkers, j.n_roots, j.mask_probe0, sc, j.n_resid,
+                       lanes, max_rounds, j.out_leaves, j.out_nfail, j.out_cost, j.out_rounds,
+                       j.out_winner) != MG_OK) {
+            const std::string why = ctx->err;
+            return fail(ctx, MG_E_ARG, "walk_batch: job %u: %s", g, why.c_str());
+        }
+        shapes[g] = walk_job_shape(j);
+        if (!mg_walk_batch_shape_ok(shapes[g]))        // implied by the checks above
+            return fail(ctx, MG_E_ARG, "walk_batch: job %u: counts out of range", g);
+    }
+    std::vector<uint64_t> off(MG_WB_SHARED + (size_t)n_jobs * MG_WB_JOB_REGIONS);
+    uint64_t bytes = 0, leaf_w = 0, probe_w = 0;
+    if (!mg_walk_batch_plan(shapes.data(), n_jobs, walkers, lanes, max_rounds, off.data(), &bytes,
+                            &leaf_w, &probe_w))
+        return fail(ctx, MG_E_ARG, "walk_batch: the batch's buffer exceeds 64 bits");
+    if (max_bytes == 0) max_bytes = MG_WALK_BATCH_DEFAULT_BYTES;
+    if (bytes > max_bytes)
+        return fail(ctx, MG_E_ARG, "walk_batch: %llu bytes needed for %u jobs, max_bytes is %llu",
+                    (unsigned long long)bytes, n_jobs, (unsigned long long)max_bytes);
+    if (sync_every == 0) sync_every = 8;
+    HIPCHECK(ctx, hipSetDevice(ctx->device));
+    void* ws;
+    int rc = workspace(ctx, (size_t)bytes + 256, &ws);
+    if (rc) return rc;
+    uint8_t* w = (uint8_t*)ws;
+    const uint64_t total = (uint64_t)walkers * lanes, words = (total + 63) / 64;
+    // the host image of everything uploaded: descriptors, jobs, frozen words
+    // (zero) and every job's tables, at the offsets of the plan
+    const size_t up_b = (size_t)off[MG_WB_OFF(0, MG_WB_FIRST_ZEROED)];
+    const size_t zero_b = (size_t)(off[MG_WB_STATES] - up_b);
+    const size_t ones_b = (size_t)(off[MG_WB_ROOTBITS] - off[MG_WB_STATES]);
+    std::vector<uint8_t> img(up_b, 0);
+    mg_pdesc* h_descs = (mg_pdesc*)(img.data() + off[MG_WB_DESCS]);
+    mg_walk_batch_job* h_jobs = (mg_walk_batch_job*)(img.data() + off[MG_WB_JOBS]);
+    mg_walk_state* d_states = (mg_walk_state*)(w + off[MG_WB_STATES]);
+    uint32_t max_lds = 0;
+    for (uint32_t g = 0; g < n_jobs; ++g) {
+        const mg_walk_job& j = jobs[g];
+        const mg_walk_shape& s = shapes[g];
+        auto at = [&](uint32_t k) { return off[MG_WB_OFF(g, k)]; };
+        auto put = [&](uint32_t k, const void* src, size_t n) {
+            if (n) memcpy(img.data() + at(k), src, n);
+        };
+        put(MG_WB_BASES, j.starts, (size_t)walkers * s.n_leaves * 32);
+        put(MG_WB_GEN, j.prog->leafgen.data(), (size_t)s.n_leaves * sizeof(mg_leafgen));
+        put(MG_WB_ROOTS, j.roots, (size_t)s.n_roots * 4);
+        put(MG_WB_ATOMS, j.atoms, (size_t)s.n_atoms * 4);
+        put(MG_WB_CODE, j.code, (size_t)s.n_code * 4);
+        put(MG_WB_ENTRIES, j.entries, (size_t)s.n_entries * 20);
+        put(MG_WB_PIECES, j.pieces, (size_t)s.n_pieces * 16);
+        put(MG_WB_FIXED, j.fixed, (size_t)s.n_entries * 32);
+        put(MG_WB_LIN, j.lin, (size_t)s.n_entries * 4);
+        put(MG_WB_SLOTS, j.slots, (size_t)s.n_slots * 8);
+        put(MG_WB_FUNCS, j.funcs, (size_t)s.n_funcs * 12);
+        put(MG_WB_CANDS, j.cands, (size_t)s.n_cands * 24);
+        put(MG_WB_UKEYS, j.ukeys, (size_t)s.n_ukeys * 32);
+        h_descs[g] = j.prog->h_desc;
+        if (j.prog->n_lds > max_lds) max_lds = j.prog->n_lds;
+        const uint32_t n_mask = (s.n_roots + 255) / 256, n_amask = (s.n_atoms + 255) / 256;
+        mg_walk_batch_job& d = h_jobs[g];
+        d.bases = (uint32_t*)(w + at(MG_WB_BASES));
+        d.gen = (const mg_leafgen*)(w + at(MG_WB_GEN));
+        d.consts = j.prog->h_desc.consts;             // the first n_consts entries: as loaded
+        d.roots = (const uint32_t*)(w + at(MG_WB_ROOTS));
+        d.atoms = (const uint32_t*)(w + at(MG_WB_ATOMS));
+        d.code = (const uint32_t*)(w + at(MG_WB_CODE));
+        d.entries = (const uint32_t*)(w + at(MG_WB_ENTRIES));
+        d.pieces = (const uint32_t*)(w + at(MG_WB_PIECES));
+        d.fixed = (const uint32_t*)(w + at(MG_WB_FIXED));
+        d.lin = (const uint32_t*)(w + at(MG_WB_LIN));
+        d.slots = (const uint32_t*)(w + at(MG_WB_SLOTS));
+        d.funcs = (const uint32_t*)(w + at(MG_WB_FUNCS));
+        d.cands = (const uint32_t*)(w + at(MG_WB_CANDS));
+        d.ukeys = (const uint32_t*)(w + at(MG_WB_UKEYS));
+        d.rstate = (uint32_t*)(w + at(MG_WB_RSTATE));
+        d.mstate = (uint32_t*)(w + at(MG_WB_MSTATE));
+        d.sstate = (uint32_t*)(w + at(MG_WB_SSTATE));
+        d.ustate = (uint32_t*)(w + at(MG_WB_USTATE));
+        d.dests = (uint32_t*)(w + at(MG_WB_DESTS));
+        d.lives = (uint32_t*)(w + at(MG_WB_LIVES));
+        d.state = d_states + (size_t)g * walkers;
+        d.trace = (uint32_t*)(w + at(MG_WB_TRACE));
+        d.leaves = (uint32_t*)(w + at(MG_WB_LEAVES));
+        // in the job's probe region: as mg_walk_sum lays its probes out
+        d.masks = (const uint32_t*)(w + at(MG_WB_PROBES)) + (size_t)s.mask_probe0 * 8 * total;
+        d.amasks = d.masks + (size_t)n_mask * 8 * total;
+        d.resid = d.amasks + (size_t)n_amask * 8 * total;
+        d.srows = d.resid + (size_t)s.n_resid * 8 * total;
+        d.urows = d.srows + (size_t)s.n_srows * 8 * total;
+        d.seed = j.seed;
+        d.n_leaves = s.n_leaves;
+        d.n_roots = s.n_roots;
+        d.n_atoms = s.n_atoms;
+        d.n_resid = s.n_resid;
+        d.n_entries = s.n_entries;
+        d.n_srows = s.n_srows;
+        d.n_urows = s.n_urows;
+        d.n_slots = s.n_slots;
+    }
+    const mg_pdesc* d_descs = (const mg_pdesc*)(w + off[MG_WB_DESCS]);
+    const mg_walk_batch_job* d_jobs = (const mg_walk_batch_job*)(w + off[MG_WB_JOBS]);
+    uint32_t* d_frozen = (uint32_t*)(w + off[MG_WB_FROZEN]);
+    HIPCHECK(ctx, hipMemcpyAsync(w, img.data(), up_b, hipMemcpyHostToDevice, ctx->stream));
+    if (zero_b) HIPCHECK(ctx, hipMemsetAsync(w + up_b, 0, zero_b, ctx->stream));
+    HIPCHECK(ctx, hipMemsetAsync(d_states, 0xFF, ones_b, ctx->stream));
+    mg_run run = empty_run();
+    run.leaves = (const uint32_t*)(w + off[MG_WB_OFF(0, MG_WB_LEAVES)]);
+    run.leaves_prog_words = leaf_w;
+    run.probes = (uint32_t*)(w + off[MG_WB_OFF(0, MG_WB_PROBES)]);
+    run.probe_prog_words = probe_w;
+    run.probes_per_prog = 1;
+    run.skip_prog = d_frozen;
+    run.root_bits = (uint64_t*)(w + off[MG_WB_ROOTBITS]);
+    run.stride = total;
+    run.n_assign = total;
+    run.words_per_prog = words;
+    const size_t state_b = (size_t)n_jobs * walkers * sizeof(mg_walk_state);
+    std::vector<mg_walk_state> h_state((size_t)n_jobs * walkers);
+    std::vector<uint32_t> h_frozen(n_jobs, 0), rounds(n_jobs, max_rounds);
+    uint32_t live = n_jobs;
+    timing_begin(ctx);
+    uint32_t r = 0;
+    while (r < max_rounds && live) {
+        const uint32_t stop = max_rounds - r < sync_every ? max_rounds : r + sync_every;
+        for (; r < stop; ++r) {
+            HIPCHECK(ctx, mg_launch_walk_batch_round(d_jobs, d_frozen, n_jobs, r, lanes, walkers,
+                                                     max_rounds, ctx->stream));
+            HIPCHECK(ctx, launch(ctx, 0, d_descs, n_jobs, run, max_lds, ctx->stream));
+            HIPCHECK(ctx, mg_launch_walk_batch_pick(d_jobs, d_frozen, n_jobs, r, lanes, walkers,
+                                                    max_rounds, ctx->stream));
+        }
+        timing_end(ctx);
+        HIPCHECK(ctx, hipMemcpyAsync(h_state.data(), d_states, state_b, hipMemcpyDeviceToHost,
+                                     ctx->stream));
+        HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
+        bool froze = false;
+        for (uint32_t g = 0; g < n_jobs; ++g) {
+            if (h_frozen[g]) continue;
+            bool done = false;
+            for (uint32_t k = 0; k < walkers; ++k)
+                done = done || h_state[(size_t)g * walkers + k].nfail == 0;
+            if (!done) continue;
+            h_frozen[g] = 1;                   // where the single walk of g stops
+            rounds[g] = r;
+            --live;
+            froze = true;
+        }
+        if (froze && live && r < max_rounds)
+            HIPCHECK(ctx, hipMemcpyAsync(d_frozen, h_frozen.data(), (size_t)n_jobs * 4,
+                                         hipMemcpyHostToDevice, ctx->stream));
+    }
+    timing_read(ctx);
+    for (uint32_t g = 0; g < n_jobs; ++g) {
+        const mg_walk_job& j = jobs[g];
+        HIPCHECK(ctx, hipMemcpyAsync(j.out_leaves, w + off[MG_WB_OFF(g, MG_WB_BASES)],
+                                     (size_t)walkers * shapes[g].n_leaves * 32,
+                                     hipMemcpyDeviceToHost, ctx->stream));
+        if (j.trace)
+            HIPCHECK(ctx, hipMemcpyAsync(j.trace, w + off[MG_WB_OFF(g, MG_WB_TRACE)],
+                                         (size_t)walkers * max_rounds * 8, hipMemcpyDeviceToHost,
+                                         ctx->stream));
+    }
+    HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
+    for (uint32_t g = 0; g < n_jobs; ++g) {
+        const mg_walk_job& j = jobs[g];
+        const mg_walk_state* st = h_state.data() + (size_t)g * walkers;
+        uint32_t win = 0;
+        for (uint32_t k = 0; k < walkers; ++k) {
+            j.out_nfail[k] = st[k].nfail;
+            j.out_cost[k] = st[k].cost;
+            if (st[k].nfail < st[win].nfail ||
+                (st[k].nfail == st[win].nfail && st[k].cost < st[win].cost))
+                win = k;
+        }
+        *j.out_rounds = rounds[g] < r ? rounds[g] : r;
+        *j.out_winner = win;
+    }
+    return MG_OK;
+}
+
+int mg_walk_batch_plan_host(const mg_walk_shape* shapes, uint32_t n_jobs, uint32_t walkers,
+                            uint32_t lanes, uint32_t max_rounds, uint64_t* out_offsets,
+                            uint64_t* out_bytes) {
+    return mg_walk_batch_plan(shapes, n_jobs, walkers, lanes, max_rounds, out_offsets, out_bytes,
+                              nullptr, nullptr) ? MG_OK : MG_E_ARG;
+}
+
+int mg_walk_batch_shape_ok_host(const mg_walk_shape* shape) {
+    return shape && mg_walk_batch_shape_ok(*shape) ? 1 : 0;
 }
 
 // Host only: lanes lane0 .. lane0 + n_lanes - 1 of round r of the lane

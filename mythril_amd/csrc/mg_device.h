@@ -85,6 +85,14 @@ struct mg_run {
     uint64_t lout_prog_words;  /* leaves_out stride between programs       */
     uint64_t probe_prog_words; /* witness regeneration: probes stride
                                   between programs (0: one program)        */
+    /* per-program buffers in one launch (mg_walk_batch): all zero, every
+       program computes the addresses above                                */
+    uint64_t leaves_prog_words; /* program p reads its host-supplied leaves
+                                  at leaves + p * leaves_prog_words        */
+    uint32_t probes_per_prog;  /* apply probe_prog_words outside witness
+                                  regeneration as well                     */
+    const uint32_t* skip_prog; /* [prog]: a program whose word is non-zero
+                                  returns before the body                  */
 };
 
 #endif

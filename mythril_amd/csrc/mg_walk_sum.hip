@@ -12,6 +12,7 @@
 //   mg_walk_tree_score  (mg_walk_tree.hip, unchanged)
 //   mg_walk_sum_adopt   mg_walk_sum_adopt; on adoption the block also gathers
 //                       the adopted lane's side rows into the walker's state
+// (the adopt body lives in mg_walk_batch.h: mg_walk_batch_adopt runs it too).
 // Thread 0 applies the adopted lane under the OLD side rows, before the
 // barrier; the block replaces them after it, as it replaces the residual
 // values.  Before round 0's adoption no entry is live and nothing is read.
@@ -19,15 +20,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "mg_walk_batch.h"      // the adopt body, shared with mg_walk_batch_adopt
 #include "mg_walk_sum.h"
 #include "mg_walk_tree.h"
 
-#define BLOCK 256
+#define BLOCK MG_WALK_BLOCK
 // blocks per walker and launch: tiles beyond are grid-strided (as mg_walk.hip)
 #define MAX_BLOCKS 2048u
-
-static_assert(MG_AIM_MAX_ENTRIES <= BLOCK, "one thread per entry builds the live list");
-static_assert(MG_UF_MAX_SLOTS <= BLOCK, "one thread per slot resolves it");
 
 // the score kernel of mg_walk_tree.hip
 __global__ __launch_bounds__(BLOCK) void mg_walk_tree_score(
@@ -82,66 +81,11 @@ __global__ __launch_bounds__(BLOCK) void mg_walk_sum_adopt(
     const uint32_t* __restrict__ cands, const uint32_t* __restrict__ ukeys, uint32_t* rstate,
     uint32_t* mstate, uint32_t* ustate, uint32_t* dests, uint32_t* lives,
     mg_walk_state* __restrict__ st, uint32_t* __restrict__ trace) {
-    __shared__ uint32_t s_lane;                  // the adopted lane, or MG_AIM_NONE
-    __shared__ uint32_t s_flag[BLOCK];
-    __shared__ uint32_t s_dest[MG_UF_MAX_SLOTS];
-    const uint32_t w = blockIdx.y;
-    const size_t total = (size_t)gridDim.y * lanes;
-    uint32_t* base = bases + (size_t)w * n_leaves * 8;
-    uint32_t* rvals = rstate + (size_t)w * n_resid * 8;
-    uint32_t* mvals = mstate + (size_t)w * n_mwords;
-    uint32_t* svals = sstate + (size_t)w * n_srows * 8;
-    uint32_t* uvals = ustate + (size_t)w * n_urows * 8;
-    uint32_t* dest = dests + (size_t)w * n_slots;
-    uint32_t* live = lives + (size_t)w * MG_AIM_LIVE_WORDS;
-    if (threadIdx.x == 0) {
-        const unsigned long long key = st[w].key;
-        const uint32_t nfail = (uint32_t)(key >> MG_WALK_NFAIL_SHIFT);
-        const uint32_t cost = (uint32_t)(key >> MG_WALK_COST_SHIFT) & MG_WALK_FIELD;
-        const uint32_t j = (uint32_t)key & MG_WALK_FIELD;
-        const bool better = nfail < st[w].nfail || (nfail == st[w].nfail && cost < st[w].cost);
-        const bool adopt = key != ~0ull && better && j < lanes;
-        if (adopt) {
-            // the moves and the gathered side are computed from the base
-            // before anything is stored; the old residual values, side rows,
-            // live list and destinations are read here, before the barrier,
-            // and replaced after it
-            mg_walk_sum_lane(base, gen, consts, n_leaves, mg_walk_seed(seed, w), r, j, lanes,
-                             entries, pieces, fixed, lin, rvals, svals, live, dest, base, 1,
-                             nullptr);
-            st[w].nfail = nfail;
-            st[w].cost = cost;
-        }
-        trace[((size_t)w * max_rounds + r) * 2] = nfail;
-        trace[((size_t)w * max_rounds + r) * 2 + 1] = cost;
-        st[w].key = ~0ull;
-        s_lane = adopt ? j : MG_AIM_NONE;
-    }
-    __syncthreads();                             // the new base is visible to the block
-    const uint32_t j = s_lane;                                             // block-uniform
-    if (j == MG_AIM_NONE) return;
-    const uint32_t* column = resid + (size_t)w * lanes + j;
-    const uint32_t* mcolumn = masks + (size_t)w * lanes + j;
-    const uint32_t* scolumn = srows + (size_t)w * lanes + j;
-    const uint32_t* ucolumn = urows + (size_t)w * lanes + j;
-    for (uint32_t i = threadIdx.x; i < n_resid * 8; i += BLOCK) rvals[i] = column[(size_t)i * total];
-    for (uint32_t i = threadIdx.x; i < n_mwords; i += BLOCK) mvals[i] = mcolumn[(size_t)i * total];
-    for (uint32_t i = threadIdx.x; i < n_srows * 8; i += BLOCK) svals[i] = scolumn[(size_t)i * total];
-    for (uint32_t i = threadIdx.x; i < n_urows * 8; i += BLOCK) uvals[i] = ucolumn[(size_t)i * total];
-    const uint32_t e = threadIdx.x;
-    if (e < n_slots) {
-        const uint32_t d = mg_walk_uf_resolve(slots, funcs, cands, ukeys, e, base, ucolumn, total);
-        s_dest[e] = d;
-        dest[e] = d;
-    }
-    __syncthreads();
-    s_flag[e] = e < n_entries && mg_walk_uf_is_live(entries, pieces, e, column, mcolumn, n_rwords,
-                                                    total, s_dest) ? 1u : 0u;
-    __syncthreads();
-    uint32_t before = 0;
-    for (uint32_t i = 0; i < BLOCK; ++i) before += i < e ? s_flag[i] : 0u;
-    if (s_flag[e]) live[1 + before] = e;
-    if (e == BLOCK - 1) live[0] = before + s_flag[e];
+    mg_walk_sum_adopt_body(blockIdx.y, (size_t)gridDim.y * lanes, bases, gen, consts, n_leaves,
+                           seed, r, lanes, max_rounds, entries, n_entries, pieces, fixed, lin,
+                           resid, n_resid, masks, n_mwords, n_rwords, srows, n_srows, sstate,
+                           urows, n_urows, slots, n_slots, funcs, cands, ukeys, rstate, mstate,
+                           ustate, dests, lives, st, trace);
 }
 
 static bool sum_shape_ok(uint32_t walkers, uint32_t lanes, uint32_t n_leaves, uint32_t r,

@@ -37,7 +37,8 @@ EXPORTS = ("mg_init", "mg_init_layout", "mg_layouts", "mg_free", "mg_last_error"
            "mg_walk", "mg_walk_score_host", "mg_walk_tree", "mg_walk_tree_score_host",
            "mg_walk_aim", "mg_walk_aim_mutate_host", "mg_walk_bound",
            "mg_walk_bound_mutate_host", "mg_walk_uf", "mg_walk_uf_resolve_host",
-           "mg_walk_uf_mutate_host", "mg_walk_sum", "mg_walk_sum_mutate_host")
+           "mg_walk_uf_mutate_host", "mg_walk_sum", "mg_walk_sum_mutate_host", "mg_walk_batch",
+           "mg_walk_batch_plan_host", "mg_walk_batch_shape_ok_host")
 
 
 def layouts() -> Dict[int, Tuple[int, int]]:
@@ -82,6 +83,31 @@ class LeafGen(C.Structure):
 
 class Gen(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("first_index", C.c_uint64)]
+
+
+_WALK_COUNTS = ("n_roots", "mask_probe0", "n_atoms", "n_code", "n_resid", "n_entries", "n_pieces",
+                "n_srows", "n_slots", "n_funcs", "n_cands", "n_ukeys", "n_urows")
+
+
+class WalkJob(C.Structure):
+    """mg_walk_job (include/mythgpu.h): one job of mg_walk_batch."""
+    _fields_ = [(n, C.c_void_p) for n in (
+        "prog", "starts", "roots", "atoms", "code", "entries", "pieces", "fixed", "lin", "slots",
+        "funcs", "cands", "ukeys", "out_leaves", "out_nfail", "out_cost", "out_rounds", "trace",
+        "out_winner")] + [("seed", C.c_uint64)] + [(n, C.c_uint32) for n in _WALK_COUNTS]
+
+
+class WalkShape(C.Structure):
+    """mg_walk_shape: the counts that size a job's share of the batch's
+    device buffer."""
+    _fields_ = [(n, C.c_uint32) for n in ("n_leaves", "n_probes") + _WALK_COUNTS]
+
+
+# include/mythgpu.h
+WALK_BATCH_MAX_JOBS = 256
+WALK_BATCH_DEFAULT_BYTES = 1 << 30
+WALK_BATCH_SHARED = 5
+WALK_BATCH_JOB_REGIONS = 22
 
 
 _libs: Dict[str, object] = {}
@@ -153,6 +179,10 @@ def load_library(path: str = _LIB_PATH, check_digest: bool = True):
         lib.mg_walk_sum_mutate_host.argtypes = [p, u32, p, u32, p, p, u32, p, u32, u32, p, u32, p,
                                                 u32, p, p, p, u32, p, u32, p, u32, p, u32, p, u32,
                                                 u32, p, u64, u32, u32, u32, u32, p, p]
+        lib.mg_walk_batch.argtypes = [p, C.POINTER(WalkJob), u32, u32, u32, u32, u32, u64]
+        lib.mg_walk_batch_plan_host.argtypes = [C.POINTER(WalkShape), u32, u32, u32, u32, p,
+                                                C.POINTER(u64)]
+        lib.mg_walk_batch_shape_ok_host.argtypes = [C.POINTER(WalkShape)]
         lib.mg_batch_create.argtypes = [p, C.POINTER(p), u32, C.POINTER(p)]
         lib.mg_batch_free.argtypes = [p]
         lib.mg_batch_free.restype = None
@@ -644,6 +674,73 @@ class Engine:
         return WalkResult(out[:, :n_leaves], nfail.astype(np.int64), cost.astype(np.int64),
                           int(rounds.value), trace, int(winner.value), self.last_kernel_ms())
 
+    def walk_batch(self, jobs, lanes: int = 4096, max_rounds: int = 64, sync_every: int = 8,
+                   max_bytes: Optional[int] = None):
+        """The walks of several groups in one launch sequence (mg_walk_batch,
+        DESIGN.md §3.16).  ``jobs``: a list of ``(lp, starts, n_roots, trees,
+        bounds, ufs, sums, seed[, mask_probe0, n_resid])``, the arguments of
+        :meth:`walk_sum` for one program each; every job has the same number
+        of walkers.  Returns one :class:`mythril_amd.repair.WalkResult` per
+        job, equal to ``walk_sum`` on it alone (``kernel_ms``: the device time
+        of the whole launch sequence the job ran in).  When the batch's device
+        buffer would exceed ``max_bytes`` (default: the library's, 1 GiB) or
+        there are more jobs than one batch takes, consecutive sub-batches that
+        fit are run; jobs are independent, so the results do not depend on the
+        split.  A single job that does not fit raises :class:`EngineError`."""
+        from .repair import WalkResult
+        jobs = [tuple(j) for j in jobs]
+        if not jobs:
+            return []
+        packed = [_pack_walk_job(j) for j in jobs]
+        walkers = packed[0]["starts"].shape[0]
+        if any(q["starts"].shape[0] != walkers for q in packed):
+            raise ValueError("every job of a batch has the same number of walkers")
+        cap = WALK_BATCH_DEFAULT_BYTES if not max_bytes else int(max_bytes)
+        shapes = [q["shape"] for q in packed]
+        plannable = 1 <= walkers <= 64 and 1 <= lanes <= 1 << 20 and 1 <= max_rounds <= 1 << 16
+        if plannable:
+            parts = split_walk_jobs(shapes, walkers, lanes, max_rounds, cap)
+        else:                                   # the library says what is wrong
+            parts = [(0, min(len(jobs), WALK_BATCH_MAX_JOBS))]
+        w1, r1 = max(1, min(walkers, 64)), max(1, min(int(max_rounds), 1 << 16))
+        results = []
+        for lo, hi in parts:
+            arr = (WalkJob * (hi - lo))()
+            outs = []
+            for i, q in enumerate(packed[lo:hi]):
+                n_leaves = q["shape"].n_leaves
+                out = np.zeros((w1, max(1, n_leaves), 8), dtype=np.uint32)
+                nfail, cost = np.zeros(w1, dtype=np.uint32), np.zeros(w1, dtype=np.uint32)
+                trace = np.zeros((w1, r1, 2), dtype=np.uint32)
+                rw = np.zeros(2, dtype=np.uint32)            # rounds, winner
+                outs.append((out, nfail, cost, trace, rw, n_leaves))
+                j = arr[i]
+                j.prog = q["lp"].handle
+                for name in ("starts", "roots", "atoms", "code", "entries", "pieces", "fixed",
+                             "lin", "slots", "funcs", "cands", "ukeys"):
+                    a = q[name]
+                    setattr(j, name, a.ctypes.data if a.size else None)
+                if not q["starts"].size:
+                    j.starts = out.ctypes.data
+                if not q["roots"].size:
+                    j.roots = nfail.ctypes.data
+                j.out_leaves, j.out_nfail, j.out_cost = (out.ctypes.data, nfail.ctypes.data,
+                                                         cost.ctypes.data)
+                j.out_rounds, j.out_winner = rw.ctypes.data, rw.ctypes.data + 4
+                j.trace = trace.ctypes.data
+                j.seed = q["seed"] & (2**64 - 1)
+                for name in _WALK_COUNTS:
+                    setattr(j, name, getattr(q["shape"], name))
+            rc = self.lib.mg_walk_batch(self._ctx, arr, hi - lo, walkers, lanes, max_rounds,
+                                        sync_every, cap)
+            self._check(rc, "mg_walk_batch")
+            ms = self.last_kernel_ms()
+            for out, nfail, cost, trace, rw, n_leaves in outs:
+                results.append(WalkResult(out[:, :n_leaves], nfail.astype(np.int64),
+                                          cost.astype(np.int64), int(rw[0]), trace, int(rw[1]),
+                                          ms))
+        return results
+
     def witness(self, lp: LoadedProgram, seed: int, index: int):
         """Leaves and probe values of candidate ``index`` (one lane): what a
         solve-mode program's model needs besides the generated leaves."""
@@ -889,6 +986,84 @@ def walk_bound_mutate_host(leafgen: Sequence[LeafGen], consts: np.ndarray, base:
     if rc != 0:
         raise EngineError("mg_walk_bound_mutate_host failed (%d)" % rc)
     return out[:len(gens), :, :n_lanes], moves[:n_lanes]
+
+
+def _pack_walk_job(job):
+    """One job of :meth:`Engine.walk_batch` as contiguous arrays and its
+    :class:`WalkShape`; the shapes :meth:`Engine.walk_sum` checks."""
+    lp, starts, n_roots, trees, bounds, ufs, sums, seed = job[:8]
+    mask_probe0 = job[8] if len(job) > 8 else 0
+    n_resid = job[9] if len(job) > 9 and job[9] is not None else len(trees.probes)
+    n_leaves = len(lp.program.leaves)
+    starts = np.ascontiguousarray(starts, dtype=np.uint32)
+    if starts.ndim != 3 or starts.shape[1:] != (n_leaves, 8):
+        raise ValueError("starts must be (walkers, n_leaves, 8)")
+    q = dict(lp=lp, starts=starts, seed=int(seed),
+             roots=np.ascontiguousarray(trees.roots, dtype=np.uint32),
+             atoms=np.ascontiguousarray(trees.atoms, dtype=np.uint32),
+             code=np.ascontiguousarray(trees.code, dtype=np.uint32),
+             entries=np.ascontiguousarray(bounds.entries, dtype=np.uint32),
+             pieces=np.ascontiguousarray(bounds.pieces, dtype=np.uint32),
+             fixed=np.ascontiguousarray(bounds.fixed, dtype=np.uint32),
+             lin=np.ascontiguousarray(sums.lin, dtype=np.uint32))
+    if q["roots"].shape != (max(0, int(n_roots)),) and 1 <= int(n_roots) <= 1024:
+        raise ValueError("trees.roots must have n_roots entries")
+    n = q["entries"].shape[0]
+    if q["entries"].shape[1:] != (5,) or q["pieces"].shape[1:] != (4,) or \
+            q["fixed"].shape != (n, 8) or q["lin"].shape != (n,):
+        raise ValueError("bounds.entries must be (n, 5), bounds.pieces (m, 4), "
+                         "bounds.fixed (n, 8), sums.lin (n,)")
+    q["slots"], q["funcs"], q["cands"], q["ukeys"] = _uf_arrays(ufs)
+    q["shape"] = WalkShape(
+        n_leaves=n_leaves, n_probes=lp.program.n_probes, n_roots=max(0, int(n_roots)),
+        mask_probe0=mask_probe0, n_atoms=q["atoms"].size, n_code=q["code"].size,
+        n_resid=max(0, int(n_resid)), n_entries=n, n_pieces=q["pieces"].shape[0],
+        n_srows=max(0, int(sums.n_srows)), n_slots=q["slots"].shape[0],
+        n_funcs=q["funcs"].shape[0], n_cands=q["cands"].shape[0], n_ukeys=q["ukeys"].shape[0],
+        n_urows=max(0, int(ufs.n_urows)))
+    return q
+
+
+def walk_batch_plan_host(shapes: Sequence[WalkShape], walkers: int, lanes: int, max_rounds: int):
+    """Host-only (no GPU): ``(offsets, bytes)`` of the device buffer
+    mg_walk_batch uses for jobs of these shapes (mg_walk_batch_plan_host:
+    ``offsets`` u64, WALK_BATCH_SHARED shared regions and then
+    WALK_BATCH_JOB_REGIONS per job), or ``None`` when the library refuses the
+    arguments or the size exceeds 64 bits."""
+    lib = load_library(check_digest=False)
+    n = len(shapes)
+    arr = (WalkShape * max(1, n))(*shapes)
+    offs = np.zeros(WALK_BATCH_SHARED + max(1, n) * WALK_BATCH_JOB_REGIONS, dtype=np.uint64)
+    total = C.c_uint64(0)
+    rc = lib.mg_walk_batch_plan_host(arr, n, walkers, lanes, max_rounds, _ptr(offs),
+                                     C.byref(total))
+    if rc != 0:
+        return None
+    return offs[:WALK_BATCH_SHARED + n * WALK_BATCH_JOB_REGIONS], int(total.value)
+
+
+def split_walk_jobs(shapes: Sequence[WalkShape], walkers: int, lanes: int, max_rounds: int,
+                    max_bytes: int, max_jobs: int = WALK_BATCH_MAX_JOBS):
+    """Consecutive ``(lo, hi)`` ranges that cover ``shapes`` once, in order,
+    each the longest run from its start whose plan (:func:`walk_batch_plan_host`)
+    stays within ``max_bytes`` and ``max_jobs``.  A plan only grows with
+    another job (the strides are maxima), so the greedy run is found by
+    extending it.  :class:`EngineError` for a job that does not fit alone."""
+    parts, lo, n = [], 0, len(shapes)
+    while lo < n:
+        hi = lo
+        while hi < n and hi - lo < max_jobs:
+            plan = walk_batch_plan_host(shapes[lo:hi + 1], walkers, lanes, max_rounds)
+            if plan is None or plan[1] > max_bytes:
+                break
+            hi += 1
+        if hi == lo:
+            plan = walk_batch_plan_host(shapes[lo:lo + 1], walkers, lanes, max_rounds)
+            raise EngineError("walk_batch: job %d alone needs %s bytes, max_bytes is %d"
+                              % (lo, "more than 2^64" if plan is None else plan[1], max_bytes))
+        parts.append((lo, hi))
+        lo = hi
+    return parts
 
 
 def _uf_arrays(ufs):

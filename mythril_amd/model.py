@@ -119,11 +119,14 @@ class SolverStatistics:
         self.refuted = 0                # queries refuted on the host (refute.py): not compiled
         self.repair_attempts = 0        # missed groups handed to the local search (repair.py)
         self.repair_hits = 0            # ... that it turned into a witness
+        self.repair_batches = 0         # repair.repair_groups calls of batch_is_possible
         self.phase = {k: 0.0 for k in PHASES}
 
     def gpu_report(self) -> str:
         return self._gpu_report() + (
-            "\nGPU repair: attempts: {} hits: {}".format(self.repair_attempts, self.repair_hits)
+            "\nGPU repair: attempts: {} hits: {}{}".format(
+                self.repair_attempts, self.repair_hits,
+                " batches: {}".format(self.repair_batches) if self.repair_batches else "")
             if self.repair_attempts or self.repair_hits else "")
 
     def _gpu_report(self) -> str:
@@ -202,6 +205,10 @@ REPAIR = False
 # repair_group's `scored`: False, True, "tree", "aim", "bound", "uf" or "sum"
 REPAIR_SCORED = False
 REPAIR_WALKERS = 16
+# opt-in (MYTHRIL_GPU_REPAIR_BATCH=1, with MYTHRIL_GPU_REPAIR 3..7): the groups
+# a batch_is_possible search missed go to ONE repair.repair_groups call, their
+# walks in one launch sequence; unset, nothing changes
+REPAIR_BATCH = False
 SHAPE_MIN, SHAPE_FLOOR, SHAPE_PROBE = 4, 1.0 / 16, 8
 
 
@@ -221,9 +228,12 @@ def configure_from_env(env=None) -> None:
     with moves aimed by a failing order's difference as well,
     ``MYTHRIL_GPU_REPAIR=6`` that walk with aims for the outputs of
     uninterpreted functions too, ``MYTHRIL_GPU_REPAIR=7`` that walk with aims
-    through sums, differences, masks and shifts too."""
+    through sums, differences, masks and shifts too;
+    ``MYTHRIL_GPU_REPAIR_BATCH=1`` (off by default; with
+    ``MYTHRIL_GPU_REPAIR`` 3..7) hands the groups a ``batch_is_possible``
+    search missed to one batched walk (``repair.repair_groups``)."""
     global GPU_ENABLED, DEVICES, SEARCH_CANDIDATES, SEARCH_BUDGET_MS, SHAPE_GATE, REFUTE, REPAIR
-    global REPAIR_SCORED
+    global REPAIR_SCORED, REPAIR_BATCH
     import os
     env = os.environ if env is None else env
     GPU_ENABLED = env.get("MYTHRIL_GPU", "1").strip().lower() not in ("0", "off", "false", "no")
@@ -242,6 +252,8 @@ def configure_from_env(env=None) -> None:
                      "7": "sum"}.get(
         env.get("MYTHRIL_GPU_REPAIR", "0").strip(), False)
     REPAIR = bool(REPAIR_SCORED) or env.get("MYTHRIL_GPU_REPAIR", "0").strip().lower() in (
+        "1", "on", "true", "yes")
+    REPAIR_BATCH = env.get("MYTHRIL_GPU_REPAIR_BATCH", "0").strip().lower() in (
         "1", "on", "true", "yes")
 
 
@@ -1123,22 +1135,30 @@ def batch_is_possible(constraint_sets, enforce_execution_time=True) -> List[bool
                 stats.errors += 1
                 log.debug("GPU pre-filter failed on a set: %s", e)
                 continue
-            pending.append((cs, progs))
+            pending.append((cs, progs, buckets))
     if pending:
         try:
             t0 = time.perf_counter()
-            flat = [p for _, progs in pending for p in progs]
+            flat = [p for _, progs, _ in pending for p in progs]
             n_cand = _n_cand(flat, min(timeout, SEARCH_BUDGET_MS))
             kinds: List[str] = []
-            hits = iter(_search_sets([progs for _, progs in pending], n_cand, kinds))
+            hits = iter(_search_sets([progs for _, progs, _ in pending], n_cand, kinds))
             kinds_it = iter(kinds)
+            answers = [([next(hits) for _ in progs], [next(kinds_it) for _ in progs])
+                       for _, progs, _ in pending]
+            repaired = {}
+            if REPAIR_BATCH and REPAIR_SCORED in _BATCHED_WALKS:
+                repaired = _repair_batch(pending, answers, min(timeout, SEARCH_BUDGET_MS), t0)
             stats.gpu_time += time.perf_counter() - t0
-            for cs, progs in pending:
-                found = [next(hits) for _ in progs]
-                how = [next(kinds_it) for _ in progs]
+            for (cs, progs, _), (found, how) in zip(pending, answers):
                 stats.gpu_queries += 1
                 stats.gpu_candidates += sum(n_cand if k < 0 else k + 1
                                             for (k, _), h in zip(found, how) if h == SEARCHED)
+                # (the candidates above count the search; a group the batched
+                # walk repaired is a hit from here on)
+                found = [(0, repaired[p.group_key]) if k < 0 and h == SEARCHED and
+                         p.group_key in repaired else (k, w)
+                         for p, (k, w), h in zip(progs, found, how)]
                 for p, (k, _), h in zip(progs, found, how):
                     # only a group that was launched (or folded to false)
                     # missed; a group skipped for a false sibling was not
@@ -1173,6 +1193,35 @@ def batch_is_possible(constraint_sets, enforce_execution_time=True) -> List[bool
         except UnsatError:
             results.append(False)
     return results
+
+
+# the kinds of repair_group's `scored` whose walks mg_walk_batch runs
+_BATCHED_WALKS = ("tree", "aim", "bound", "uf", "sum")
+
+
+def _repair_batch(pending, answers, budget_ms: float, t_start: float) -> dict:
+    """group key -> assignment for the SEARCHED groups the batched search of
+    ``batch_is_possible`` missed and ONE ``repair.repair_groups`` call repairs
+    (MYTHRIL_GPU_REPAIR_BATCH=1): the groups are deduplicated by key over all
+    pending sets and walk in one launch sequence on the first device, while
+    search budget remains.  ``stats.repair_attempts`` and ``repair_hits`` count
+    groups, ``repair_batches`` the calls."""
+    from .repair import REPAIRED, repair_groups
+    missed = {}
+    for (_, progs, buckets), (found, how) in zip(pending, answers):
+        for p, b, (k, _), h in zip(progs, buckets, found, how):
+            if k < 0 and h == SEARCHED and p.group_key is not None:
+                missed.setdefault(p.group_key, b)
+    if not missed or (time.perf_counter() - t_start) * 1e3 >= budget_ms:
+        return {}
+    stats.repair_batches += 1
+    stats.repair_attempts += len(missed)
+    with _Phase("search"):
+        gs = repair_groups(list(missed.values()), device=(list(DEVICES) or [0])[0],
+                           scored=REPAIR_SCORED, walkers=REPAIR_WALKERS)
+    out = {k: g["assignment"] for k, g in zip(missed, gs) if g["status"] == REPAIRED}
+    stats.repair_hits += len(out)
+    return out
 
 
 def filter_possible(states, constraints_of=lambda s: s.world_state.constraints):

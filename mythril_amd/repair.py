@@ -2016,6 +2016,36 @@ def repair_group(nodes: Sequence, n_cand: int = 1 << 16, form: str = "search", l
     the group falls back to ``"uf"`` and onward; with no linear entry it runs
     exactly as ``scored="uf"`` does on the table of :func:`sum_table` (the
     mask and shift rules may have added plain entries to it)."""
+    steps = _repair_steps(nodes, n_cand, form, lanes, max_rounds, device, seed, sync_every, scored,
+                          walkers)
+    try:
+        walk = next(steps)
+        while True:
+            walk = steps.send(walk.single())
+    except StopIteration as done:
+        return done.value
+
+
+class _TreeWalk:
+    """Where :func:`_repair_steps` hands a tree-scored walk to its driver:
+    ``single()`` runs it as :func:`repair_group` always has; ``job`` is the same
+    walk as a job of ``Engine.walk_batch`` on ``eng`` (mg_walk_sum's arguments:
+    a kind without a table gets the empty one, which by §3.12 - §3.15 is that
+    kind bit for bit)."""
+
+    def __init__(self, eng, job, single):
+        self.eng, self.job, self.single = eng, job, single
+
+
+def _repair_steps(nodes, n_cand, form, lanes, max_rounds, device, seed, sync_every, scored,
+                  walkers):
+    """:func:`repair_group` in three steps, as a generator.  Prepare: compile,
+    build the tables, run the census, pick the starts.  Walk: a tree-scored
+    walk is yielded as a :class:`_TreeWalk` and its ``WalkResult`` sent back
+    (:func:`repair_group` runs it alone, :func:`repair_groups` in one batch
+    with the other groups'); the table-scored walk and the count walk run
+    here.  Finish: the fresh evaluation, ``failing``, ``atom_state``, the
+    assignment.  Returns the group's dict."""
     from . import census as CS
     from . import model as M
     from .assign import unpack
@@ -2164,32 +2194,38 @@ def repair_group(nodes: Sequence, n_cand: int = 1 << 16, form: str = "search", l
         starts = np.stack([leaves if i == c.best_index else eng.witness(full, M.SEARCH_SEED, i)[0]
                            for i in picks])
         wide = eng.load(CS.census_view(masked, n_mask + n_amask + len(resid)), gens, prog_seed=0)
+        n = len(nodes)
         if trees is not None and sums is not None:
             # the side rows after the residuals, then the U rows: the
             # arguments, then the kept keys
             wide = eng.load(uf_view(masked, n_mask + n_amask + len(resid) + len(sprobes) +
                                     ufs.n_arg_rows, ufs.keep), gens, prog_seed=0)
-            res = eng.walk_sum(wide, starts, len(nodes), trees, bounds, ufs, sums, seed, lanes,
-                               max_rounds, sync_every)
-            out["trees"] = trees
+            job = (wide, starts, n, trees, bounds, ufs, sums, seed)
+            single = lambda: eng.walk_sum(wide, starts, n, trees, bounds, ufs, sums, seed, lanes,
+                                          max_rounds, sync_every)
         elif trees is not None and ufs is not None:
             # the U rows after the residuals: the arguments, then the kept keys
             wide = eng.load(uf_view(masked, n_mask + n_amask + len(resid) + ufs.n_arg_rows,
                                     ufs.keep), gens, prog_seed=0)
-            res = eng.walk_uf(wide, starts, len(nodes), trees, bounds, ufs, seed, lanes,
-                              max_rounds, sync_every)
-            out["trees"] = trees
+            job = (wide, starts, n, trees, bounds, ufs, no_sums(len(bounds)), seed)
+            single = lambda: eng.walk_uf(wide, starts, n, trees, bounds, ufs, seed, lanes,
+                                         max_rounds, sync_every)
         elif trees is not None and bounds is not None:
-            res = eng.walk_bound(wide, starts, len(nodes), trees, bounds, seed, lanes, max_rounds,
-                                 sync_every)
-            out["trees"] = trees
+            job = (wide, starts, n, trees, bounds, no_ufs(), no_sums(len(bounds)), seed)
+            single = lambda: eng.walk_bound(wide, starts, n, trees, bounds, seed, lanes,
+                                            max_rounds, sync_every)
         elif trees is not None and aims is not None and len(aims):
-            res = eng.walk_aim(wide, starts, len(nodes), trees, aims, seed, lanes, max_rounds,
-                               sync_every)
-            out["trees"] = trees
+            xor = bounds_of_aims(aims, n, trees.n_atoms)
+            job = (wide, starts, n, trees, xor, no_ufs(), no_sums(len(xor)), seed)
+            single = lambda: eng.walk_aim(wide, starts, n, trees, aims, seed, lanes, max_rounds,
+                                          sync_every)
         elif trees is not None:
-            res = eng.walk_tree(wide, starts, len(nodes), trees, seed, lanes, max_rounds,
-                                sync_every)
+            job = (wide, starts, n, trees, bounds_of_aims(no_aims(), n, trees.n_atoms), no_ufs(),
+                   no_sums(0), seed)
+            single = lambda: eng.walk_tree(wide, starts, n, trees, seed, lanes, max_rounds,
+                                           sync_every)
+        if trees is not None:
+            res = yield _TreeWalk(eng, job, single)
             out["trees"] = trees
         else:
             res = eng.walk(wide, starts, len(nodes), table, len(resid), seed, lanes, max_rounds,
@@ -2226,6 +2262,46 @@ def repair_group(nodes: Sequence, n_cand: int = 1 << 16, form: str = "search", l
         return out
     out["status"] = REPAIRED
     out["assignment"] = unpack(masked, leaves, probes[:, :, 0] if masked.solved else None)
+    return out
+
+
+def repair_groups(groups: Sequence[Sequence], n_cand: int = 1 << 16, form: str = "search",
+                  lanes: int = 4096, max_rounds: int = 64, device: int = 0,
+                  seed: Optional[int] = None, sync_every: int = 8, scored=False,
+                  walkers: int = 1, max_bytes: Optional[int] = None) -> List[dict]:
+    """``[repair_group(g, ...) for g in groups]`` with the tree-scored walks
+    of all groups in one ``Engine.walk_batch`` (``mg_walk_batch``, DESIGN.md
+    §3.16) — one per register layout, should the groups' programs differ in
+    it: every key of every dict is what :func:`repair_group` returns but
+    ``repair.kernel_ms``, the device time of the batch the group's walk ran
+    in.  Every group is prepared first (compile, tables, census and witness
+    launches, per group as before), then the walks run together, then every
+    group is finished.  Groups that end without a walk (refuted, ground,
+    unsupported, dead, satisfied by the census) and groups that fall back to
+    the table or the count run as :func:`repair_group` runs them."""
+    runs = [_repair_steps(g, n_cand, form, lanes, max_rounds, device, seed, sync_every, scored,
+                          walkers) for g in groups]
+    out: List[Optional[dict]] = [None] * len(runs)
+    waiting, engines = {}, []
+    for i, steps in enumerate(runs):
+        try:
+            waiting[i] = next(steps)
+        except StopIteration as done:
+            out[i] = done.value
+            continue
+        if not any(e is waiting[i].eng for e in engines):
+            engines.append(waiting[i].eng)
+    for eng in engines:
+        idx = [i for i in waiting if waiting[i].eng is eng]
+        results = eng.walk_batch([waiting[i].job for i in idx], lanes, max_rounds, sync_every,
+                                 max_bytes)
+        for i, res in zip(idx, results):
+            try:
+                runs[i].send(res)
+            except StopIteration as done:
+                out[i] = done.value
+            else:
+                raise RuntimeError("a group asked for a second walk")
     return out
 
 

@@ -1,0 +1,51 @@
+"""Host sanitizer coverage of the host side of mg_walk_batch (DESIGN.md
+§3.16): mythril_amd/csrc/mg_walk_batch.h — the check of a job's counts
+(mg_walk_batch_shape_ok) and the plan of the batch's device buffer
+(mg_walk_batch_plan), the code the C ABI runs before it uploads anything —
+built with g++ -fsanitize=address,undefined into the stand-alone
+tests/fuzz_walk_batch.cpp and driven with valid, mutated and random shapes.
+CPU only; nothing is loaded into Python."""
+
+import json
+import os
+import shutil
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.fixture(scope="module")
+def fuzz_binary(tmp_path_factory):
+    if not shutil.which("g++"):
+        pytest.skip("g++ not available")
+    out = str(tmp_path_factory.mktemp("fuzz") / "fuzz_walk_batch")
+    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer",
+           "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan",
+           "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "mythril_amd", "csrc"),
+           os.path.join(ROOT, "tests", "fuzz_walk_batch.cpp"), "-o", out]
+    subprocess.run(cmd, check=True)
+    return out
+
+
+def test_shape_check_and_plan_under_asan_ubsan(fuzz_binary):
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1",
+               UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
+    r = subprocess.run([fuzz_binary, "3000"], capture_output=True, text=True, env=env, timeout=600)
+    assert r.returncode == 0, r.stderr[-4000:]
+    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-4000:]
+    stats = json.loads(r.stdout.strip().splitlines()[-1])
+    n = stats["iterations"]
+    # valid shapes pass the check, and every batch of them is planned
+    assert stats["valid_accepted"] == n == stats["valid_planned"]
+    # a mutated count is caught often; the plan holds for any counts short of
+    # 2^64 bytes, and random words sometimes exceed that
+    assert 0 < stats["mutated_accepted"] < stats["mutated"]
+    assert stats["mutated_planned"] > stats["mutated"] // 2
+    assert stats["random_accepted"] == 0
+    assert 0 < stats["random_planned"] <= n
+    # shared arguments out of range: five cases in six
+    assert n // 2 < stats["shared_refused"] < n
+    # and most accepted plans were laid out in a buffer of exactly their size
+    assert stats["laid_out"] > n and stats["bytes_laid"] > 0
