@@ -28,8 +28,6 @@
 #include "mg_walk.h"
 #include "mg_walk_tree.h"
 #include "mg_walk_aim.h"
-#include "mg_walk_bound.h"
-#include "mg_walk_uf.h"
 #include "mg_walk_sum.h"
 #include "mg_walk_batch.h"
 
@@ -114,52 +112,11 @@ hipError_t mg_launch_walk_aim_pick(const uint32_t* d_masks, const uint32_t* d_am
                                    uint32_t n_entries, const uint32_t* d_pieces, uint32_t n_resid,
                                    uint32_t* d_rstate, uint32_t* d_lives, mg_walk_state* d_state,
                                    uint32_t* d_trace, hipStream_t stream);
-// the round of mg_walk_bound (mg_walk_bound.hip): mg_walk_aim's
-// with the wider table, the side's fixed bits and the walkers' mask state
-hipError_t mg_launch_walk_bound_round(const uint32_t* d_bases, const mg_leafgen* d_gen,
-                                      const uint32_t* d_consts, uint32_t n_leaves, uint64_t seed,
-                                      uint32_t r, uint32_t lanes, uint32_t walkers,
-                                      const uint32_t* d_entries, uint32_t n_entries,
-                                      const uint32_t* d_pieces, const uint32_t* d_fixed,
-                                      const uint32_t* d_rstate, uint32_t n_resid,
-                                      const uint32_t* d_lives, uint32_t* d_leaves,
-                                      hipStream_t stream);
-hipError_t mg_launch_walk_bound_pick(const uint32_t* d_masks, const uint32_t* d_amasks,
-                                     const uint32_t* d_resid, const uint32_t* d_roots,
-                                     const uint32_t* d_atoms, const uint32_t* d_code,
-                                     uint32_t lanes, uint32_t walkers, uint32_t n_roots,
-                                     uint32_t n_atoms, uint32_t* d_bases, const mg_leafgen* d_gen,
-                                     const uint32_t* d_consts, uint32_t n_leaves, uint64_t seed,
-                                     uint32_t r, uint32_t max_rounds, const uint32_t* d_entries,
-                                     uint32_t n_entries, const uint32_t* d_pieces,
-                                     const uint32_t* d_fixed, uint32_t n_resid, uint32_t* d_rstate,
-                                     uint32_t* d_mstate, uint32_t* d_lives, mg_walk_state* d_state,
-                                     uint32_t* d_trace, hipStream_t stream);
-// the round of mg_walk_uf (mg_walk_uf.hip): mg_walk_bound's
-// with the walkers' slot destinations, U rows and the UF tables
-hipError_t mg_launch_walk_uf_round(const uint32_t* d_bases, const mg_leafgen* d_gen,
-                                   const uint32_t* d_consts, uint32_t n_leaves, uint64_t seed,
-                                   uint32_t r, uint32_t lanes, uint32_t walkers,
-                                   const uint32_t* d_entries, uint32_t n_entries,
-                                   const uint32_t* d_pieces, const uint32_t* d_fixed,
-                                   const uint32_t* d_rstate, uint32_t n_resid,
-                                   const uint32_t* d_lives, const uint32_t* d_dests,
-                                   uint32_t n_slots, uint32_t* d_leaves, hipStream_t stream);
-hipError_t mg_launch_walk_uf_pick(const uint32_t* d_masks, const uint32_t* d_amasks,
-                                  const uint32_t* d_resid, const uint32_t* d_urows,
-                                  const uint32_t* d_roots, const uint32_t* d_atoms,
-                                  const uint32_t* d_code, uint32_t lanes, uint32_t walkers,
-                                  uint32_t n_roots, uint32_t n_atoms, uint32_t* d_bases,
-                                  const mg_leafgen* d_gen, const uint32_t* d_consts,
-                                  uint32_t n_leaves, uint64_t seed, uint32_t r,
-                                  uint32_t max_rounds, const uint32_t* d_entries,
-                                  uint32_t n_entries, const uint32_t* d_pieces,
-                                  const uint32_t* d_fixed, uint32_t n_resid, const mg_uf_tables& uf,
-                                  uint32_t* d_rstate, uint32_t* d_mstate, uint32_t* d_ustate,
-                                  uint32_t* d_dests, uint32_t* d_lives, mg_walk_state* d_state,
-                                  uint32_t* d_trace, hipStream_t stream);
-// the round of mg_walk_sum (mg_walk_sum.hip): mg_walk_uf's
-// with the entries' lin words and the walkers' side rows
+// the round of mg_walk_bound, mg_walk_uf and mg_walk_sum (mg_walk_sum.hip,
+// DESIGN.md §3.13 - §3.15): mg_walk_aim's with the wider table, the side's
+// fixed bits and the walkers' mask state; the walkers' slot destinations, U
+// rows and the UF tables; the entries' lin words and the walkers' side rows.
+// A lower rung passes lin words all 0 and empty tables.
 hipError_t mg_launch_walk_sum_round(const uint32_t* d_bases, const mg_leafgen* d_gen,
                                     const uint32_t* d_consts, uint32_t n_leaves, uint64_t seed,
                                     uint32_t r, uint32_t lanes, uint32_t walkers,
@@ -1101,10 +1058,11 @@ static bool walk_table_ok(const uint32_t* table, uint32_t n_roots, uint32_t n_re
 // what scores a walk's neighbours: the residual table of mg_walk (no atoms, no
 // code) or the tree tables of mg_walk_tree (table: its root entries); aim: the
 // round of mg_walk_aim with its aim table (tree scoring); bound: the round of
-// mg_walk_bound, whose entries have 5 words and a fixed value each; uf: the
-// round of mg_walk_uf, mg_walk_bound's with the UF tables uft (host pointers);
-// sum: the round of mg_walk_sum, mg_walk_uf's with the lin words and n_srows
-// side rows between the residual probes and the U rows
+// mg_walk_sum.hip, whose entries have 5 words and a fixed value each; uf: with
+// the UF tables uft (host pointers; else empty); sum: with the lin words (else
+// null: all 0) and n_srows side rows between the residual probes and the U
+// rows (else 0).  bound, uf and sum also say which rung's checks and messages
+// walk_check applies.
 struct walk_scoring {
     const uint32_t* table;
     const uint32_t* atoms;
@@ -1254,14 +1212,12 @@ static int walk_run(mg_ctx* ctx, const mg_prog* prog, const uint32_t* starts, ui
                  fixed_b = sc.bound ? (size_t)sc.n_entries * 32 : 0,
                  mstate_b = sc.bound ? (size_t)walkers * 4 * (MG_BOUND_MASK_WORDS(n_roots) +
                                                               MG_BOUND_MASK_WORDS(sc.n_atoms)) : 0,
-                 slot_b = sc.uf ? (size_t)sc.uft.n_slots * 8 : 0,
-                 func_b = sc.uf ? (size_t)sc.uft.n_funcs * 12 : 0,
-                 cand_b = sc.uf ? (size_t)sc.uft.n_cands * 24 : 0,
-                 ukey_b = sc.uf ? (size_t)sc.uft.n_ukeys * 32 : 0,
-                 ustate_b = sc.uf ? (size_t)walkers * sc.uft.n_urows * 32 : 0,
-                 dest_b = sc.uf ? (size_t)walkers * sc.uft.n_slots * 4 : 0,
-                 lin_b = sc.sum ? (size_t)sc.n_entries * 4 : 0,
-                 sstate_b = sc.sum ? (size_t)walkers * sc.n_srows * 32 : 0;
+                 slot_b = (size_t)sc.uft.n_slots * 8, func_b = (size_t)sc.uft.n_funcs * 12,
+                 cand_b = (size_t)sc.uft.n_cands * 24, ukey_b = (size_t)sc.uft.n_ukeys * 32,
+                 ustate_b = (size_t)walkers * sc.uft.n_urows * 32,
+                 dest_b = (size_t)walkers * sc.uft.n_slots * 4,
+                 lin_b = sc.bound ? (size_t)sc.n_entries * 4 : 0,
+                 sstate_b = (size_t)walkers * sc.n_srows * 32;
     const size_t off_base = align(state_b), off_gen = off_base + align(base_b),
                  off_table = off_gen + align(gen_b), off_trace = off_table + align(table_b),
                  off_root = off_trace + align(trace_b), off_leaf = off_root + align(root_b),
@@ -1341,8 +1297,10 @@ static int walk_run(mg_ctx* ctx, const mg_prog* prog, const uint32_t* starts, ui
                                      ctx->stream));
     if (ustate_b) HIPCHECK(ctx, hipMemsetAsync(d_ustate, 0, ustate_b, ctx->stream));
     if (dest_b) HIPCHECK(ctx, hipMemsetAsync(d_dests, 0xFF, dest_b, ctx->stream));
-    if (lin_b)
+    if (lin_b && sc.lin)
         HIPCHECK(ctx, hipMemcpyAsync(d_lin, sc.lin, lin_b, hipMemcpyHostToDevice, ctx->stream));
+    else if (lin_b)                                       // a lower rung: no entry is linear
+        HIPCHECK(ctx, hipMemsetAsync(d_lin, 0, lin_b, ctx->stream));
     if (sstate_b) HIPCHECK(ctx, hipMemsetAsync(d_sstate, 0, sstate_b, ctx->stream));
     mg_run run = empty_run();
     run.leaves = d_leaves;
@@ -1354,7 +1312,7 @@ static int walk_run(mg_ctx* ctx, const mg_prog* prog, const uint32_t* starts, ui
     const uint32_t* d_masks = d_probes + (size_t)mask_probe0 * 8 * total;
     const uint32_t* d_amasks = d_masks + (size_t)n_mask * 8 * total;
     const uint32_t* d_resid = d_amasks + (size_t)n_amask * 8 * total;
-    const uint32_t n_srows = sc.sum ? sc.n_srows : 0;
+    const uint32_t n_srows = sc.n_srows;
     const uint32_t* d_srows = d_resid + (size_t)n_resid * 8 * total;
     const uint32_t* d_urows = d_srows + (size_t)n_srows * 8 * total;
     const uint32_t* d_consts = prog->h_desc.consts;       // the first n_consts entries: as loaded
@@ -1365,23 +1323,12 @@ static int walk_run(mg_ctx* ctx, const mg_prog* prog, const uint32_t* starts, ui
     while (r < max_rounds && !done) {
         const uint32_t stop = max_rounds - r < sync_every ? max_rounds : r + sync_every;
         for (; r < stop; ++r) {
-            if (sc.sum)
+            if (sc.bound)                      // mg_walk_bound, mg_walk_uf, mg_walk_sum
                 HIPCHECK(ctx, mg_launch_walk_sum_round(d_bases, d_gen, d_consts, n_leaves, seed,
                                                        r, lanes, walkers, d_entries, sc.n_entries,
                                                        d_pieces, d_fixed, d_lin, d_rstate, n_resid,
                                                        d_sstate, n_srows, d_lives, d_dests,
                                                        d_uf.n_slots, d_leaves, ctx->stream));
-            else if (sc.uf)
-                HIPCHECK(ctx, mg_launch_walk_uf_round(d_bases, d_gen, d_consts, n_leaves, seed, r,
-                                                      lanes, walkers, d_entries, sc.n_entries,
-                                                      d_pieces, d_fixed, d_rstate, n_resid,
-                                                      d_lives, d_dests, d_uf.n_slots, d_leaves,
-                                                      ctx->stream));
-            else if (sc.bound)
-                HIPCHECK(ctx, mg_launch_walk_bound_round(d_bases, d_gen, d_consts, n_leaves, seed,
-                                                         r, lanes, walkers, d_entries,
-                                                         sc.n_entries, d_pieces, d_fixed, d_rstate,
-                                                         n_resid, d_lives, d_leaves, ctx->stream));
             else if (sc.aim)
                 HIPCHECK(ctx, mg_launch_walk_aim_round(d_bases, d_gen, d_consts, n_leaves, seed, r,
                                                        lanes, walkers, d_entries, sc.n_entries,
@@ -1391,7 +1338,7 @@ static int walk_run(mg_ctx* ctx, const mg_prog* prog, const uint32_t* starts, ui
                 HIPCHECK(ctx, mg_launch_walk_round(d_bases, d_gen, d_consts, n_leaves, seed, r,
                                                    lanes, walkers, d_leaves, ctx->stream));
             HIPCHECK(ctx, launch(ctx, 0, prog->d_desc, 1, run, prog->n_lds, ctx->stream));
-            if (sc.sum)
+            if (sc.bound)
                 HIPCHECK(ctx, mg_launch_walk_sum_pick(d_masks, d_amasks, d_resid, d_srows, n_srows,
                                                       d_urows, d_table, d_atoms, d_code, lanes,
                                                       walkers, n_roots, sc.n_atoms, d_bases, d_gen,
@@ -1400,22 +1347,6 @@ static int walk_run(mg_ctx* ctx, const mg_prog* prog, const uint32_t* starts, ui
                                                       d_lin, n_resid, d_uf, d_rstate, d_mstate,
                                                       d_sstate, d_ustate, d_dests, d_lives,
                                                       d_state, d_trace, ctx->stream));
-            else if (sc.uf)
-                HIPCHECK(ctx, mg_launch_walk_uf_pick(d_masks, d_amasks, d_resid, d_urows, d_table,
-                                                     d_atoms, d_code, lanes, walkers, n_roots,
-                                                     sc.n_atoms, d_bases, d_gen, d_consts,
-                                                     n_leaves, seed, r, max_rounds, d_entries,
-                                                     sc.n_entries, d_pieces, d_fixed, n_resid,
-                                                     d_uf, d_rstate, d_mstate, d_ustate, d_dests,
-                                                     d_lives, d_state, d_trace, ctx->stream));
-            else if (sc.bound)
-                HIPCHECK(ctx, mg_launch_walk_bound_pick(d_masks, d_amasks, d_resid, d_table,
-                                                        d_atoms, d_code, lanes, walkers, n_roots,
-                                                        sc.n_atoms, d_bases, d_gen, d_consts,
-                                                        n_leaves, seed, r, max_rounds, d_entries,
-                                                        sc.n_entries, d_pieces, d_fixed, n_resid,
-                                                        d_rstate, d_mstate, d_lives, d_state,
-                                                        d_trace, ctx->stream));
             else if (sc.aim)
                 HIPCHECK(ctx, mg_launch_walk_aim_pick(d_masks, d_amasks, d_resid, d_table, d_atoms,
                                                       d_code, lanes, walkers, n_roots, d_bases,
@@ -1501,7 +1432,8 @@ int mg_walk_aim(mg_ctx* ctx, const mg_prog* prog, const uint32_t* starts, uint32
 }
 
 // The tree-scored walk with moves aimed by equalities and orders (DESIGN.md
-// §3.13): mg_walk_aim with the kernels of mg_walk_bound.hip and their table.
+// §3.13): mg_walk_aim with the kernels of mg_walk_sum.hip and the 5-word table
+// of mg_walk_bound.h (no UF table, no lin word).
 int mg_walk_bound(mg_ctx* ctx, const mg_prog* prog, const uint32_t* starts, uint32_t walkers,
                   uint32_t n_roots, uint32_t mask_probe0, const uint32_t* roots, uint32_t n_atoms,
                   const uint32_t* atoms, const uint32_t* code, uint32_t n_code, uint32_t n_resid,
@@ -1518,8 +1450,8 @@ int mg_walk_bound(mg_ctx* ctx, const mg_prog* prog, const uint32_t* starts, uint
 }
 
 // The same with aims that write the table entry a UF application reads
-// (DESIGN.md §3.14): mg_walk_bound with the kernels of mg_walk_uf.hip, the UF
-// tables of mg_walk_uf.h and n_urows U rows after the residual probes.
+// (DESIGN.md §3.14): mg_walk_bound with the UF tables of mg_walk_uf.h and
+// n_urows U rows after the residual probes.
 int mg_walk_uf(mg_ctx* ctx, const mg_prog* prog, const uint32_t* starts, uint32_t walkers,
                uint32_t n_roots, uint32_t mask_probe0, const uint32_t* roots, uint32_t n_atoms,
                const uint32_t* atoms, const uint32_t* code, uint32_t n_code, uint32_t n_resid,
@@ -1541,9 +1473,8 @@ int mg_walk_uf(mg_ctx* ctx, const mg_prog* prog, const uint32_t* starts, uint32_
 }
 
 // The same with aims through sums, differences, masks and shifts (DESIGN.md
-// §3.15): mg_walk_uf with the kernels of mg_walk_sum.hip, the lin words of
-// mg_walk_sum.h and n_srows side rows between the residual probes and the U
-// rows.
+// §3.15): mg_walk_uf with the lin words of mg_walk_sum.h and n_srows side rows
+// between the residual probes and the U rows.
 int mg_walk_sum(mg_ctx* ctx, const mg_prog* prog, const uint32_t* starts, uint32_t walkers,
                 uint32_t n_roots, uint32_t mask_probe0, const uint32_t* roots, uint32_t n_atoms,
                 const uint32_t* atoms, const uint32_t* code, uint32_t n_code, uint32_t n_resid,
@@ -1847,18 +1778,26 @@ int mg_walk_aim_mutate_host(const mg_leafgen* leaves, uint32_t n_leaves, const u
     return MG_OK;
 }
 
-// Host only: the same of the lane function of mg_walk_bound.h.
-int mg_walk_bound_mutate_host(const mg_leafgen* leaves, uint32_t n_leaves, const uint32_t* consts,
-                              uint32_t n_consts, const uint32_t* base, const uint32_t* rvals,
-                              uint32_t n_resid, const uint32_t* mvals, uint32_t n_roots,
-                              uint32_t n_atoms, const uint32_t* entries, uint32_t n_entries,
-                              const uint32_t* pieces, uint32_t n_pieces, const uint32_t* fixed,
-                              uint64_t seed, uint32_t r, uint32_t lanes, uint32_t lane0,
-                              uint32_t n_lanes, uint32_t* out, uint32_t* moves) {
+// Host only: what the three entries below share.  The argument and base
+// checks, the validator of the rung (`rung`: 0 bound, 1 uf, 2 sum), then lanes
+// lane0 .. lane0 + n_lanes - 1 of round r of the lane function of
+// mg_walk_sum.h, as the mutate kernel writes them.  A lower rung passes empty
+// UF tables, no destinations and mg_walk_no_lin.
+static int walk_sum_mutate_host(int rung, const mg_leafgen* leaves, uint32_t n_leaves,
+                                const uint32_t* consts, uint32_t n_consts, const uint32_t* base,
+                                const uint32_t* rvals, uint32_t n_resid, const uint32_t* mvals,
+                                uint32_t n_roots, uint32_t n_atoms, const uint32_t* entries,
+                                uint32_t n_entries, const uint32_t* pieces, uint32_t n_pieces,
+                                const uint32_t* fixed, const uint32_t* lin, const uint32_t* svals,
+                                uint32_t n_srows, const mg_uf_tables& t, const uint32_t* dest,
+                                uint64_t seed, uint32_t r, uint32_t lanes, uint32_t lane0,
+                                uint32_t n_lanes, uint32_t* out, uint32_t* moves) {
     if (!leaves || !base || !out || (n_consts && !consts) || n_leaves == 0) return MG_E_ARG;
     if (lanes < 1 || lanes > MG_REPAIR_MAX_LANES || r >= MG_REPAIR_MAX_ROUNDS) return MG_E_ARG;
     if (lane0 > lanes || n_lanes > lanes - lane0) return MG_E_ARG;
     if (n_roots > MG_WT_MAX_ROOTS || n_atoms > MG_WT_MAX_ATOMS) return MG_E_ARG;
+    if (t.n_slots && !dest) return MG_E_ARG;
+    if (n_srows && rvals && mvals && !svals) return MG_E_ARG;
     for (uint32_t i = 0; i < n_leaves; ++i) {
         if (leaves[i].width < 1 || leaves[i].width > MG_MAX_WIDTH) return MG_E_ARG;
         if ((uint64_t)leaves[i].pool_off + leaves[i].pool_n > n_consts) return MG_E_ARG;
@@ -1867,17 +1806,25 @@ int mg_walk_bound_mutate_host(const mg_leafgen* leaves, uint32_t n_leaves, const
         mg_repair_mask(v, leaves[i].width);
         if (memcmp(v, base + (size_t)i * 8, 32)) return MG_E_ARG;     // a base beyond its width
     }
-    if (!mg_walk_bound_ok(entries, n_entries, pieces, n_pieces, fixed, leaves, n_leaves, n_resid,
-                          n_roots, n_atoms))
-        return MG_E_ARG;
+    const bool ok =
+        rung == 2 ? mg_walk_sum_ok(entries, n_entries, pieces, n_pieces, fixed, lin, n_srows, leaves,
+                                   n_leaves, n_resid, n_roots, n_atoms, t)
+        : rung == 1 ? mg_walk_uf_ok(entries, n_entries, pieces, n_pieces, fixed, leaves, n_leaves,
+                                    n_resid, n_roots, n_atoms, t)
+                    : mg_walk_bound_ok(entries, n_entries, pieces, n_pieces, fixed, leaves,
+                                       n_leaves, n_resid, n_roots, n_atoms);
+    if (!ok) return MG_E_ARG;
+    for (uint32_t u = 0; u < t.n_slots; ++u)             // a destination is a leaf or none
+        if (dest[u] != MG_AIM_NONE && dest[u] >= n_leaves) return MG_E_ARG;
     uint32_t live[MG_AIM_LIVE_WORDS];
-    mg_walk_bound_live(entries, n_entries, rvals, mvals, MG_BOUND_MASK_WORDS(n_roots), live);
+    mg_walk_uf_live(entries, n_entries, pieces, rvals, mvals, MG_BOUND_MASK_WORDS(n_roots), dest,
+                    live);
     for (uint32_t a = 0; a < n_lanes; ++a) {
         for (size_t i = 0; i < (size_t)n_leaves * 8; ++i) out[i * n_lanes + a] = base[i];
         mg_repair_moves mv;
-        const uint32_t e = mg_walk_bound_lane(base, leaves, consts, n_leaves, seed, r, lane0 + a,
-                                              lanes, entries, pieces, fixed, rvals, live, out + a,
-                                              n_lanes, &mv);
+        const uint32_t e = mg_walk_sum_lane(base, leaves, consts, n_leaves, seed, r, lane0 + a,
+                                            lanes, entries, pieces, fixed, lin, rvals, svals,
+                                            live, dest, out + a, n_lanes, &mv);
         if (moves) {
             moves[5 * (size_t)a] = mv.n;
             moves[5 * (size_t)a + 1] = mv.kind[0] | mv.kind[1] << 8;
@@ -1887,6 +1834,20 @@ int mg_walk_bound_mutate_host(const mg_leafgen* leaves, uint32_t n_leaves, const
         }
     }
     return MG_OK;
+}
+
+// Host only: mg_walk_aim_mutate_host of the lane function of mg_walk_bound.h.
+int mg_walk_bound_mutate_host(const mg_leafgen* leaves, uint32_t n_leaves, const uint32_t* consts,
+                              uint32_t n_consts, const uint32_t* base, const uint32_t* rvals,
+                              uint32_t n_resid, const uint32_t* mvals, uint32_t n_roots,
+                              uint32_t n_atoms, const uint32_t* entries, uint32_t n_entries,
+                              const uint32_t* pieces, uint32_t n_pieces, const uint32_t* fixed,
+                              uint64_t seed, uint32_t r, uint32_t lanes, uint32_t lane0,
+                              uint32_t n_lanes, uint32_t* out, uint32_t* moves) {
+    return walk_sum_mutate_host(0, leaves, n_leaves, consts, n_consts, base, rvals, n_resid, mvals,
+                                n_roots, n_atoms, entries, n_entries, pieces, n_pieces, fixed,
+                                mg_walk_no_lin, nullptr, 0, mg_uf_tables{}, nullptr, seed, r,
+                                lanes, lane0, n_lanes, out, moves);
 }
 
 // Host only: the destinations of the slots (mg_walk_uf_resolve of
@@ -1921,44 +1882,12 @@ int mg_walk_uf_mutate_host(const mg_leafgen* leaves, uint32_t n_leaves, const ui
                            const uint32_t* ukeys, uint32_t n_ukeys, uint32_t n_urows,
                            const uint32_t* dest, uint64_t seed, uint32_t r, uint32_t lanes,
                            uint32_t lane0, uint32_t n_lanes, uint32_t* out, uint32_t* moves) {
-    if (!leaves || !base || !out || (n_consts && !consts) || n_leaves == 0) return MG_E_ARG;
-    if (lanes < 1 || lanes > MG_REPAIR_MAX_LANES || r >= MG_REPAIR_MAX_ROUNDS) return MG_E_ARG;
-    if (lane0 > lanes || n_lanes > lanes - lane0) return MG_E_ARG;
-    if (n_roots > MG_WT_MAX_ROOTS || n_atoms > MG_WT_MAX_ATOMS) return MG_E_ARG;
-    if (n_slots && !dest) return MG_E_ARG;
-    for (uint32_t i = 0; i < n_leaves; ++i) {
-        if (leaves[i].width < 1 || leaves[i].width > MG_MAX_WIDTH) return MG_E_ARG;
-        if ((uint64_t)leaves[i].pool_off + leaves[i].pool_n > n_consts) return MG_E_ARG;
-        uint32_t v[8];
-        memcpy(v, base + (size_t)i * 8, 32);
-        mg_repair_mask(v, leaves[i].width);
-        if (memcmp(v, base + (size_t)i * 8, 32)) return MG_E_ARG;     // a base beyond its width
-    }
     const mg_uf_tables t = {slots, n_slots, funcs, n_funcs, cands, n_cands, ukeys, n_ukeys,
                             n_urows};
-    if (!mg_walk_uf_ok(entries, n_entries, pieces, n_pieces, fixed, leaves, n_leaves, n_resid,
-                       n_roots, n_atoms, t))
-        return MG_E_ARG;
-    for (uint32_t u = 0; u < n_slots; ++u)               // a destination is a leaf or none
-        if (dest[u] != MG_AIM_NONE && dest[u] >= n_leaves) return MG_E_ARG;
-    uint32_t live[MG_AIM_LIVE_WORDS];
-    mg_walk_uf_live(entries, n_entries, pieces, rvals, mvals, MG_BOUND_MASK_WORDS(n_roots), dest,
-                    live);
-    for (uint32_t a = 0; a < n_lanes; ++a) {
-        for (size_t i = 0; i < (size_t)n_leaves * 8; ++i) out[i * n_lanes + a] = base[i];
-        mg_repair_moves mv;
-        const uint32_t e = mg_walk_uf_lane(base, leaves, consts, n_leaves, seed, r, lane0 + a,
-                                           lanes, entries, pieces, fixed, rvals, live, dest,
-                                           out + a, n_lanes, &mv);
-        if (moves) {
-            moves[5 * (size_t)a] = mv.n;
-            moves[5 * (size_t)a + 1] = mv.kind[0] | mv.kind[1] << 8;
-            moves[5 * (size_t)a + 2] = mv.leaf[0];
-            moves[5 * (size_t)a + 3] = mv.leaf[1];
-            moves[5 * (size_t)a + 4] = e;
-        }
-    }
-    return MG_OK;
+    return walk_sum_mutate_host(1, leaves, n_leaves, consts, n_consts, base, rvals, n_resid, mvals,
+                                n_roots, n_atoms, entries, n_entries, pieces, n_pieces, fixed,
+                                mg_walk_no_lin, nullptr, 0, t, dest, seed, r, lanes, lane0, n_lanes,
+                                out, moves);
 }
 
 // Host only: mg_walk_uf_mutate_host of the lane function of mg_walk_sum.h;
@@ -1975,45 +1904,12 @@ int mg_walk_sum_mutate_host(const mg_leafgen* leaves, uint32_t n_leaves, const u
                             const uint32_t* ukeys, uint32_t n_ukeys, uint32_t n_urows,
                             const uint32_t* dest, uint64_t seed, uint32_t r, uint32_t lanes,
                             uint32_t lane0, uint32_t n_lanes, uint32_t* out, uint32_t* moves) {
-    if (!leaves || !base || !out || (n_consts && !consts) || n_leaves == 0) return MG_E_ARG;
-    if (lanes < 1 || lanes > MG_REPAIR_MAX_LANES || r >= MG_REPAIR_MAX_ROUNDS) return MG_E_ARG;
-    if (lane0 > lanes || n_lanes > lanes - lane0) return MG_E_ARG;
-    if (n_roots > MG_WT_MAX_ROOTS || n_atoms > MG_WT_MAX_ATOMS) return MG_E_ARG;
-    if (n_slots && !dest) return MG_E_ARG;
-    if (n_srows && rvals && mvals && !svals) return MG_E_ARG;
-    for (uint32_t i = 0; i < n_leaves; ++i) {
-        if (leaves[i].width < 1 || leaves[i].width > MG_MAX_WIDTH) return MG_E_ARG;
-        if ((uint64_t)leaves[i].pool_off + leaves[i].pool_n > n_consts) return MG_E_ARG;
-        uint32_t v[8];
-        memcpy(v, base + (size_t)i * 8, 32);
-        mg_repair_mask(v, leaves[i].width);
-        if (memcmp(v, base + (size_t)i * 8, 32)) return MG_E_ARG;     // a base beyond its width
-    }
     const mg_uf_tables t = {slots, n_slots, funcs, n_funcs, cands, n_cands, ukeys, n_ukeys,
                             n_urows};
-    if (!mg_walk_sum_ok(entries, n_entries, pieces, n_pieces, fixed, lin, n_srows, leaves,
-                        n_leaves, n_resid, n_roots, n_atoms, t))
-        return MG_E_ARG;
-    for (uint32_t u = 0; u < n_slots; ++u)               // a destination is a leaf or none
-        if (dest[u] != MG_AIM_NONE && dest[u] >= n_leaves) return MG_E_ARG;
-    uint32_t live[MG_AIM_LIVE_WORDS];
-    mg_walk_uf_live(entries, n_entries, pieces, rvals, mvals, MG_BOUND_MASK_WORDS(n_roots), dest,
-                    live);
-    for (uint32_t a = 0; a < n_lanes; ++a) {
-        for (size_t i = 0; i < (size_t)n_leaves * 8; ++i) out[i * n_lanes + a] = base[i];
-        mg_repair_moves mv;
-        const uint32_t e = mg_walk_sum_lane(base, leaves, consts, n_leaves, seed, r, lane0 + a,
-                                            lanes, entries, pieces, fixed, lin, rvals, svals,
-                                            live, dest, out + a, n_lanes, &mv);
-        if (moves) {
-            moves[5 * (size_t)a] = mv.n;
-            moves[5 * (size_t)a + 1] = mv.kind[0] | mv.kind[1] << 8;
-            moves[5 * (size_t)a + 2] = mv.leaf[0];
-            moves[5 * (size_t)a + 3] = mv.leaf[1];
-            moves[5 * (size_t)a + 4] = e;
-        }
-    }
-    return MG_OK;
+    return walk_sum_mutate_host(2, leaves, n_leaves, consts, n_consts, base, rvals, n_resid, mvals,
+                                n_roots, n_atoms, entries, n_entries, pieces, n_pieces, fixed, lin,
+                                svals, n_srows, t, dest, seed, r, lanes, lane0, n_lanes, out,
+                                moves);
 }
 
 // Host only: the tree scoring (mg_walk_tree.h) on n lanes of host rows, as

@@ -24,21 +24,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "mg_walk_aim.h"
-#include "mg_walk_tree.h"
+#include "mg_walk_round.h"    // the block size, the grid and mg_walk_tree_score
 
-#define BLOCK 256
-// blocks per walker and launch: tiles beyond are grid-strided (as mg_walk.hip)
-#define MAX_BLOCKS 2048u
-
-static_assert(MG_AIM_MAX_ENTRIES <= BLOCK, "one thread per entry builds the live list");
-
-// the score kernel of mg_walk_tree.hip
-__global__ __launch_bounds__(BLOCK) void mg_walk_tree_score(
-    const uint32_t* __restrict__ masks, const uint32_t* __restrict__ amasks,
-    const uint32_t* __restrict__ resid, const uint32_t* __restrict__ roots,
-    const uint32_t* __restrict__ atoms, const uint32_t* __restrict__ code, uint32_t lanes,
-    uint32_t n_roots, mg_walk_state* __restrict__ st);
+#define BLOCK MG_WALK_BLOCK
 
 __global__ __launch_bounds__(BLOCK) void mg_walk_aim_mutate(
     const uint32_t* __restrict__ bases, const mg_leafgen* __restrict__ gen,
@@ -133,8 +121,7 @@ hipError_t mg_launch_walk_aim_round(const uint32_t* d_bases, const mg_leafgen* d
                                     uint32_t n_resid, const uint32_t* d_lives, uint32_t* d_leaves,
                                     hipStream_t stream) {
     if (!aim_shape_ok(walkers, lanes, n_leaves, r, n_entries)) return hipErrorInvalidValue;
-    const uint32_t tiles = (lanes + BLOCK - 1) / BLOCK;
-    const uint32_t blocks = tiles < MAX_BLOCKS ? tiles : MAX_BLOCKS;
+    const uint32_t blocks = mg_walk_grid_blocks(lanes);
     hipLaunchKernelGGL(mg_walk_aim_mutate, dim3(blocks, walkers), dim3(BLOCK), 0, stream, d_bases,
                        d_gen, d_consts, n_leaves, seed, r, lanes, d_entries, d_pieces, d_rstate,
                        n_resid, d_lives, d_leaves);
@@ -156,8 +143,7 @@ hipError_t mg_launch_walk_aim_pick(const uint32_t* d_masks, const uint32_t* d_am
     if (!aim_shape_ok(walkers, lanes, n_leaves, r, n_entries) || n_roots == 0 ||
         n_roots > MG_WT_MAX_ROOTS || r >= max_rounds)
         return hipErrorInvalidValue;
-    const uint32_t tiles = (lanes + BLOCK - 1) / BLOCK;
-    const uint32_t blocks = tiles < MAX_BLOCKS ? tiles : MAX_BLOCKS;
+    const uint32_t blocks = mg_walk_grid_blocks(lanes);
     hipLaunchKernelGGL(mg_walk_tree_score, dim3(blocks, walkers), dim3(BLOCK), 0, stream, d_masks,
                        d_amasks, d_resid, d_roots, d_atoms, d_code, lanes, n_roots, d_state);
     hipError_t e = hipGetLastError();

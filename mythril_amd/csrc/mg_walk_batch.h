@@ -2,8 +2,7 @@
  * sequence.  Host part, plain C++ with no HIP call: the shape of a job, the
  * checks of its counts and the plan of the batch's device buffer; the ABI
  * (mg_walk_batch, mg_walk_batch_plan_host) and the CPU suite run this code.
- * Device part (hipcc only): the job as the kernels of mg_walk_batch.hip read
- * it, and the adopt body that mg_walk_sum_adopt and mg_walk_batch_adopt share.
+ * The job is laid out as the kernels of mg_walk_batch.hip read it.
  *
  * One device buffer holds the whole batch, every region 256-byte aligned, in
  * this order:
@@ -175,93 +174,5 @@ static inline bool mg_walk_batch_plan(const mg_walk_shape* shapes, uint32_t n_jo
     if (probe_stride_w) *probe_stride_w = probe_b / 4;
     return true;
 }
-
-#ifdef __HIPCC__
-#define MG_WALK_BLOCK 256
-
-static_assert(MG_AIM_MAX_ENTRIES <= MG_WALK_BLOCK, "one thread per entry builds the live list");
-static_assert(MG_UF_MAX_SLOTS <= MG_WALK_BLOCK, "one thread per slot resolves it");
-
-/* The adoption of walker w, by one block of MG_WALK_BLOCK threads: the body
- * of mg_walk_sum_adopt (mg_walk_sum.hip says what it does) and of
- * mg_walk_batch_adopt.  total: the lanes of all walkers, the row stride of
- * the probe buffer. */
-static __device__ __forceinline__ void mg_walk_sum_adopt_body(
-    uint32_t w, size_t total, uint32_t* bases, const mg_leafgen* __restrict__ gen,
-    const uint32_t* __restrict__ consts, uint32_t n_leaves, uint64_t seed, uint32_t r,
-    uint32_t lanes, uint32_t max_rounds, const uint32_t* __restrict__ entries, uint32_t n_entries,
-    const uint32_t* __restrict__ pieces, const uint32_t* __restrict__ fixed,
-    const uint32_t* __restrict__ lin, const uint32_t* __restrict__ resid, uint32_t n_resid,
-    const uint32_t* __restrict__ masks, uint32_t n_mwords, uint32_t n_rwords,
-    const uint32_t* __restrict__ srows, uint32_t n_srows, uint32_t* sstate,
-    const uint32_t* __restrict__ urows, uint32_t n_urows, const uint32_t* __restrict__ slots,
-    uint32_t n_slots, const uint32_t* __restrict__ funcs, const uint32_t* __restrict__ cands,
-    const uint32_t* __restrict__ ukeys, uint32_t* rstate, uint32_t* mstate, uint32_t* ustate,
-    uint32_t* dests, uint32_t* lives, mg_walk_state* __restrict__ st,
-    uint32_t* __restrict__ trace) {
-    __shared__ uint32_t s_lane;                  // the adopted lane, or MG_AIM_NONE
-    __shared__ uint32_t s_flag[MG_WALK_BLOCK];
-    __shared__ uint32_t s_dest[MG_UF_MAX_SLOTS];
-    uint32_t* base = bases + (size_t)w * n_leaves * 8;
-    uint32_t* rvals = rstate + (size_t)w * n_resid * 8;
-    uint32_t* mvals = mstate + (size_t)w * n_mwords;
-    uint32_t* svals = sstate + (size_t)w * n_srows * 8;
-    uint32_t* uvals = ustate + (size_t)w * n_urows * 8;
-    uint32_t* dest = dests + (size_t)w * n_slots;
-    uint32_t* live = lives + (size_t)w * MG_AIM_LIVE_WORDS;
-    if (threadIdx.x == 0) {
-        const unsigned long long key = st[w].key;
-        const uint32_t nfail = (uint32_t)(key >> MG_WALK_NFAIL_SHIFT);
-        const uint32_t cost = (uint32_t)(key >> MG_WALK_COST_SHIFT) & MG_WALK_FIELD;
-        const uint32_t j = (uint32_t)key & MG_WALK_FIELD;
-        const bool better = nfail < st[w].nfail || (nfail == st[w].nfail && cost < st[w].cost);
-        const bool adopt = key != ~0ull && better && j < lanes;
-        if (adopt) {
-            // the moves and the gathered side are computed from the base
-            // before anything is stored; the old residual values, side rows,
-            // live list and destinations are read here, before the barrier,
-            // and replaced after it
-            mg_walk_sum_lane(base, gen, consts, n_leaves, mg_walk_seed(seed, w), r, j, lanes,
-                             entries, pieces, fixed, lin, rvals, svals, live, dest, base, 1,
-                             nullptr);
-            st[w].nfail = nfail;
-            st[w].cost = cost;
-        }
-        trace[((size_t)w * max_rounds + r) * 2] = nfail;
-        trace[((size_t)w * max_rounds + r) * 2 + 1] = cost;
-        st[w].key = ~0ull;
-        s_lane = adopt ? j : MG_AIM_NONE;
-    }
-    __syncthreads();                             // the new base is visible to the block
-    const uint32_t j = s_lane;                                             // block-uniform
-    if (j == MG_AIM_NONE) return;
-    const uint32_t* column = resid + (size_t)w * lanes + j;
-    const uint32_t* mcolumn = masks + (size_t)w * lanes + j;
-    const uint32_t* scolumn = srows + (size_t)w * lanes + j;
-    const uint32_t* ucolumn = urows + (size_t)w * lanes + j;
-    for (uint32_t i = threadIdx.x; i < n_resid * 8; i += MG_WALK_BLOCK)
-        rvals[i] = column[(size_t)i * total];
-    for (uint32_t i = threadIdx.x; i < n_mwords; i += MG_WALK_BLOCK)
-        mvals[i] = mcolumn[(size_t)i * total];
-    for (uint32_t i = threadIdx.x; i < n_srows * 8; i += MG_WALK_BLOCK)
-        svals[i] = scolumn[(size_t)i * total];
-    for (uint32_t i = threadIdx.x; i < n_urows * 8; i += MG_WALK_BLOCK)
-        uvals[i] = ucolumn[(size_t)i * total];
-    const uint32_t e = threadIdx.x;
-    if (e < n_slots) {
-        const uint32_t d = mg_walk_uf_resolve(slots, funcs, cands, ukeys, e, base, ucolumn, total);
-        s_dest[e] = d;
-        dest[e] = d;
-    }
-    __syncthreads();
-    s_flag[e] = e < n_entries && mg_walk_uf_is_live(entries, pieces, e, column, mcolumn, n_rwords,
-                                                    total, s_dest) ? 1u : 0u;
-    __syncthreads();
-    uint32_t before = 0;
-    for (uint32_t i = 0; i < MG_WALK_BLOCK; ++i) before += i < e ? s_flag[i] : 0u;
-    if (s_flag[e]) live[1 + before] = e;
-    if (e == MG_WALK_BLOCK - 1) live[0] = before + s_flag[e];
-}
-#endif
 
 #endif

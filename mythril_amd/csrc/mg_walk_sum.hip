@@ -1,41 +1,48 @@
-// mg_walk_sum — the tree-scored walk with aims through sums, differences,
-// masks and shifts (specification: mythril_amd/repair.py
-// walk_ref with sums).
+// mg_walk_bound, mg_walk_uf, mg_walk_sum — the tree-scored walks with moves
+// aimed by a failing equality's residual or a failing order's difference
+// (DESIGN.md §3.13), through the table entry a UF application reads (§3.14) and
+// through sums, differences, masks and shifts (§3.15); specification:
+// mythril_amd/repair.py walk_ref with bounds, ufs and sums.
 //
-// A round is the round of mg_walk_uf.hip with its two kernels exchanged:
-//   mg_walk_sum_mutate  mg_walk_sum_mutate with the lin words of the entries
-//                       and one more wave-uniform input per walker: the side
-//                       rows sstate[w][n_srows][8] of its base (the lane
-//                       function of mg_walk_sum.h)
+// The three rungs are nested (mg_walk_sum.h), so one round serves them all: a
+// lower rung runs it with lin words all 0, no side row, no slot and no U row.
+// A round is the round of mg_walk_aim.hip with its two kernels exchanged:
+//   mg_walk_sum_mutate  lane j of walker w writes neighbour j of base w: the
+//                       lane function of mg_walk_sum.h, which reads the
+//                       walker's residual values, side rows sstate[w][n_srows]
+//                       [8], live list and slot destinations dest[w][n_slots]
+//                       (all wave-uniform per walker) and the lin words of the
+//                       entries
 //   the interpreter     writes every neighbour's root mask, atom mask,
-//                       residual probes, side rows and U rows
+//                       residual probes, side rows and U rows (the arguments'
+//                       chunks, then the computed keys of argument-keyed
+//                       entries)
 //   mg_walk_tree_score  (mg_walk_tree.hip, unchanged)
-//   mg_walk_sum_adopt   mg_walk_sum_adopt; on adoption the block also gathers
-//                       the adopted lane's side rows into the walker's state
-// (the adopt body lives in mg_walk_batch.h: mg_walk_batch_adopt runs it too).
-// Thread 0 applies the adopted lane under the OLD side rows, before the
-// barrier; the block replaces them after it, as it replaces the residual
-// values.  Before round 0's adoption no entry is live and nothing is read.
+//   mg_walk_sum_adopt   block w: what mg_walk_aim_adopt does for walker w; on
+//                       adoption the block also gathers the adopted lane's
+//                       root-mask and atom-mask rows (at most (4 + 4) x 8
+//                       words), side rows and U rows into the walker's state
+//                       next to the residual rows, resolves every slot, one
+//                       thread per slot, against the updated base and that
+//                       lane's U rows (after the barrier that makes thread 0's
+//                       in-place update of the base visible), and rebuilds the
+//                       live list under the rule of mg_walk_uf.h, one thread
+//                       per entry ranked by prefix count: L stays in table
+//                       order whatever the schedule
+// The bodies of the kernels live in mg_walk_round.h: mg_walk_batch.hip runs
+// them too.  Thread 0 applies the adopted lane under the OLD side rows, before
+// the barrier; the block replaces them after it, as it replaces the residual
+// values.  The walkers' states start at ~0, so round 0 always adopts and the
+// residuals, masks, side rows and U rows are known from round 1 on; the
+// destinations start at MG_AIM_NONE and the live lists empty, so before round
+// 0's adoption no entry is live and nothing of them is read.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "mg_walk_batch.h"      // the adopt body, shared with mg_walk_batch_adopt
-#include "mg_walk_sum.h"
-#include "mg_walk_tree.h"
+#include "mg_walk_round.h"
 
-#define BLOCK MG_WALK_BLOCK
-// blocks per walker and launch: tiles beyond are grid-strided (as mg_walk.hip)
-#define MAX_BLOCKS 2048u
-
-// the score kernel of mg_walk_tree.hip
-__global__ __launch_bounds__(BLOCK) void mg_walk_tree_score(
-    const uint32_t* __restrict__ masks, const uint32_t* __restrict__ amasks,
-    const uint32_t* __restrict__ resid, const uint32_t* __restrict__ roots,
-    const uint32_t* __restrict__ atoms, const uint32_t* __restrict__ code, uint32_t lanes,
-    uint32_t n_roots, mg_walk_state* __restrict__ st);
-
-__global__ __launch_bounds__(BLOCK) void mg_walk_sum_mutate(
+__global__ __launch_bounds__(MG_WALK_BLOCK) void mg_walk_sum_mutate(
     const uint32_t* __restrict__ bases, const mg_leafgen* __restrict__ gen,
     const uint32_t* __restrict__ consts, uint32_t n_leaves, uint64_t seed, uint32_t r,
     uint32_t lanes, const uint32_t* __restrict__ entries, const uint32_t* __restrict__ pieces,
@@ -43,32 +50,11 @@ __global__ __launch_bounds__(BLOCK) void mg_walk_sum_mutate(
     const uint32_t* __restrict__ rstate, uint32_t n_resid, const uint32_t* __restrict__ sstate,
     uint32_t n_srows, const uint32_t* __restrict__ lives, const uint32_t* __restrict__ dests,
     uint32_t n_slots, uint32_t* out) {
-    const uint32_t w = blockIdx.y;
-    const size_t total = (size_t)gridDim.y * lanes;
-    const uint32_t* base = bases + (size_t)w * n_leaves * 8;
-    const uint32_t* rvals = rstate + (size_t)w * n_resid * 8;
-    const uint32_t* svals = sstate + (size_t)w * n_srows * 8;
-    const uint32_t* live = lives + (size_t)w * MG_AIM_LIVE_WORDS;
-    const uint32_t* dest = dests + (size_t)w * n_slots;
-    const uint64_t wseed = mg_walk_seed(seed, w);
-    const uint32_t tiles = (lanes + BLOCK - 1) / BLOCK;
-    for (uint32_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {   // uniform per block
-        const uint32_t j = tile * BLOCK + threadIdx.x;
-        if (j >= lanes) continue;
-        uint32_t* col = out + (size_t)w * lanes + j;
-        for (uint32_t leaf = 0; leaf < n_leaves; ++leaf)
-            for (uint32_t k = 0; k < 8; ++k)                               // one row: coalesced
-                col[((size_t)leaf * 8 + k) * total] = base[(size_t)leaf * 8 + k];
-        // the lane's own column again: its pieces applied, its moves over them
-        mg_walk_sum_lane(base, gen, consts, n_leaves, wseed, r, j, lanes, entries, pieces, fixed,
-                         lin, rvals, svals, live, dest, col, total, nullptr);
-    }
+    mg_walk_mutate_body(bases, gen, consts, n_leaves, seed, r, lanes, entries, pieces, fixed, lin,
+                        rstate, n_resid, sstate, n_srows, lives, dests, n_slots, out);
 }
 
-// masks: as mg_walk_bound_adopt; srows: the n_srows probes after the
-// residuals, urows: the n_urows probes after them; sstate: [walkers][n_srows][8],
-// ustate: [walkers][n_urows][8], dests: [walkers][n_slots]
-__global__ __launch_bounds__(BLOCK) void mg_walk_sum_adopt(
+__global__ __launch_bounds__(MG_WALK_BLOCK) void mg_walk_sum_adopt(
     uint32_t* bases, const mg_leafgen* __restrict__ gen, const uint32_t* __restrict__ consts,
     uint32_t n_leaves, uint64_t seed, uint32_t r, uint32_t lanes, uint32_t max_rounds,
     const uint32_t* __restrict__ entries, uint32_t n_entries,
@@ -81,11 +67,11 @@ __global__ __launch_bounds__(BLOCK) void mg_walk_sum_adopt(
     const uint32_t* __restrict__ cands, const uint32_t* __restrict__ ukeys, uint32_t* rstate,
     uint32_t* mstate, uint32_t* ustate, uint32_t* dests, uint32_t* lives,
     mg_walk_state* __restrict__ st, uint32_t* __restrict__ trace) {
-    mg_walk_sum_adopt_body(blockIdx.y, (size_t)gridDim.y * lanes, bases, gen, consts, n_leaves,
-                           seed, r, lanes, max_rounds, entries, n_entries, pieces, fixed, lin,
-                           resid, n_resid, masks, n_mwords, n_rwords, srows, n_srows, sstate,
-                           urows, n_urows, slots, n_slots, funcs, cands, ukeys, rstate, mstate,
-                           ustate, dests, lives, st, trace);
+    mg_walk_adopt_body(blockIdx.y, (size_t)gridDim.y * lanes, bases, gen, consts, n_leaves, seed, r,
+                       lanes, max_rounds, entries, n_entries, pieces, fixed, lin, resid, n_resid,
+                       masks, n_mwords, n_rwords, srows, n_srows, sstate, urows, n_urows, slots,
+                       n_slots, funcs, cands, ukeys, rstate, mstate, ustate, dests, lives, st,
+                       trace);
 }
 
 static bool sum_shape_ok(uint32_t walkers, uint32_t lanes, uint32_t n_leaves, uint32_t r,
@@ -97,9 +83,10 @@ static bool sum_shape_ok(uint32_t walkers, uint32_t lanes, uint32_t n_leaves, ui
            n_urows <= MG_UF_MAX_ROWS && n_srows <= MG_SUM_MAX_ROWS;
 }
 
-// The tables must have passed mg_walk_sum_ok (mg_walk_sum checks them before
-// it uploads); d_rstate, d_lives as mg_launch_walk_bound_round, d_dests as
-// mg_launch_walk_uf_round, d_sstate: [walkers][n_srows][8].
+// The tables must have passed mg_walk_sum_ok (every rung's entry checks them
+// before it uploads); d_rstate, d_lives as mg_launch_walk_aim_round, d_dests:
+// [walkers][n_slots], MG_AIM_NONE before round 0, d_sstate: [walkers][n_srows]
+// [8], d_lin: [n_entries], zero for a lower rung.
 hipError_t mg_launch_walk_sum_round(const uint32_t* d_bases, const mg_leafgen* d_gen,
                                    const uint32_t* d_consts, uint32_t n_leaves, uint64_t seed,
                                    uint32_t r, uint32_t lanes, uint32_t walkers,
@@ -111,12 +98,11 @@ hipError_t mg_launch_walk_sum_round(const uint32_t* d_bases, const mg_leafgen* d
                                    uint32_t n_slots, uint32_t* d_leaves, hipStream_t stream) {
     if (!sum_shape_ok(walkers, lanes, n_leaves, r, n_entries, n_slots, 0, n_srows))
         return hipErrorInvalidValue;
-    const uint32_t tiles = (lanes + BLOCK - 1) / BLOCK;
-    const uint32_t blocks = tiles < MAX_BLOCKS ? tiles : MAX_BLOCKS;
-    hipLaunchKernelGGL(mg_walk_sum_mutate, dim3(blocks, walkers), dim3(BLOCK), 0, stream, d_bases,
-                       d_gen, d_consts, n_leaves, seed, r, lanes, d_entries, d_pieces, d_fixed,
-                       d_lin, d_rstate, n_resid, d_sstate, n_srows, d_lives, d_dests, n_slots,
-                       d_leaves);
+    const uint32_t blocks = mg_walk_grid_blocks(lanes);
+    hipLaunchKernelGGL(mg_walk_sum_mutate, dim3(blocks, walkers), dim3(MG_WALK_BLOCK), 0, stream,
+                       d_bases, d_gen, d_consts, n_leaves, seed, r, lanes, d_entries, d_pieces,
+                       d_fixed, d_lin, d_rstate, n_resid, d_sstate, n_srows, d_lives, d_dests,
+                       n_slots, d_leaves);
     return hipGetLastError();
 }
 
@@ -147,16 +133,17 @@ hipError_t mg_launch_walk_sum_pick(const uint32_t* d_masks, const uint32_t* d_am
         d_srows != d_resid + (size_t)n_resid * 8 * walkers * lanes ||
         d_urows != d_srows + (size_t)n_srows * 8 * walkers * lanes)
         return hipErrorInvalidValue;
-    const uint32_t tiles = (lanes + BLOCK - 1) / BLOCK;
-    const uint32_t blocks = tiles < MAX_BLOCKS ? tiles : MAX_BLOCKS;
-    hipLaunchKernelGGL(mg_walk_tree_score, dim3(blocks, walkers), dim3(BLOCK), 0, stream, d_masks,
-                       d_amasks, d_resid, d_roots, d_atoms, d_code, lanes, n_roots, d_state);
+    const uint32_t blocks = mg_walk_grid_blocks(lanes);
+    hipLaunchKernelGGL(mg_walk_tree_score, dim3(blocks, walkers), dim3(MG_WALK_BLOCK), 0, stream,
+                       d_masks, d_amasks, d_resid, d_roots, d_atoms, d_code, lanes, n_roots,
+                       d_state);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(mg_walk_sum_adopt, dim3(1, walkers), dim3(BLOCK), 0, stream, d_bases, d_gen,
-                       d_consts, n_leaves, seed, r, lanes, max_rounds, d_entries, n_entries,
-                       d_pieces, d_fixed, d_lin, d_resid, n_resid, d_masks, n_mwords, n_rwords,
-                       d_srows, n_srows, d_sstate, d_urows, uf.n_urows, uf.slots, uf.n_slots, uf.funcs, uf.cands, uf.ukeys, d_rstate,
-                       d_mstate, d_ustate, d_dests, d_lives, d_state, d_trace);
+    hipLaunchKernelGGL(mg_walk_sum_adopt, dim3(1, walkers), dim3(MG_WALK_BLOCK), 0, stream,
+                       d_bases, d_gen, d_consts, n_leaves, seed, r, lanes, max_rounds, d_entries,
+                       n_entries, d_pieces, d_fixed, d_lin, d_resid, n_resid, d_masks, n_mwords,
+                       n_rwords, d_srows, n_srows, d_sstate, d_urows, uf.n_urows, uf.slots,
+                       uf.n_slots, uf.funcs, uf.cands, uf.ukeys, d_rstate, d_mstate, d_ustate,
+                       d_dests, d_lives, d_state, d_trace);
     return hipGetLastError();
 }

@@ -18,49 +18,19 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "mg_walk_tree.h"
-
-#define BLOCK 256
-// blocks per walker and launch: tiles beyond are grid-strided (as mg_walk.hip)
-#define MAX_BLOCKS 2048u
+#include "mg_walk_round.h"    // the score body, shared with mg_walk_batch_score
 
 hipError_t mg_launch_walk_adopt(uint32_t* d_bases, const mg_leafgen* d_gen,
                                 const uint32_t* d_consts, uint32_t n_leaves, uint64_t seed,
                                 uint32_t r, uint32_t lanes, uint32_t walkers, uint32_t max_rounds,
                                 mg_walk_state* d_state, uint32_t* d_trace, hipStream_t stream);
 
-__global__ __launch_bounds__(BLOCK) void mg_walk_tree_score(
+__global__ __launch_bounds__(MG_WALK_BLOCK) void mg_walk_tree_score(
     const uint32_t* __restrict__ masks, const uint32_t* __restrict__ amasks,
     const uint32_t* __restrict__ resid, const uint32_t* __restrict__ roots,
     const uint32_t* __restrict__ atoms, const uint32_t* __restrict__ code, uint32_t lanes,
     uint32_t n_roots, mg_walk_state* __restrict__ st) {
-    __shared__ unsigned long long s_best;
-    __shared__ uint32_t s_stack[MG_WT_STACK * BLOCK];
-    if (threadIdx.x == 0) s_best = ~0ull;
-    __syncthreads();
-    const uint32_t w = blockIdx.y;
-    const size_t total = (size_t)gridDim.y * lanes;
-    const uint32_t tiles = (lanes + BLOCK - 1) / BLOCK;
-    unsigned long long best = ~0ull;
-    for (uint32_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {   // uniform per block
-        const uint32_t j = tile * BLOCK + threadIdx.x;
-        // lanes past the walker's stay in the loop (the wave-wide OR and the
-        // wave-uniform programs need the whole wave) and read nothing
-        const bool active = j < lanes;
-        uint32_t nfail, cost;
-        mg_walk_tree_score_lane(masks, amasks, resid, total, (size_t)w * lanes + (active ? j : 0u),
-                                roots, atoms, code, n_roots, active, s_stack + threadIdx.x, BLOCK,
-                                &nfail, &cost);
-        const unsigned long long key = active ? mg_walk_key(nfail, cost, j) : ~0ull;
-        best = key < best ? key : best;
-    }
-    for (int off = 32; off > 0; off >>= 1) {
-        const unsigned long long o = __shfl_xor(best, off, 64);
-        best = o < best ? o : best;
-    }
-    if ((threadIdx.x & 63) == 0 && best != ~0ull) atomicMin(&s_best, best);
-    __syncthreads();
-    if (threadIdx.x == 0 && s_best != ~0ull) atomicMin(&st[w].key, s_best);
+    mg_walk_score_body(masks, amasks, resid, roots, atoms, code, lanes, n_roots, st);
 }
 
 // score with the tree tables, then the adopt of mg_walk.hip.  The tables must
@@ -77,9 +47,8 @@ hipError_t mg_launch_walk_tree_pick(const uint32_t* d_masks, const uint32_t* d_a
         n_leaves == 0 || n_roots == 0 || n_roots > MG_WT_MAX_ROOTS || r >= max_rounds ||
         r >= MG_REPAIR_MAX_ROUNDS)
         return hipErrorInvalidValue;
-    const uint32_t tiles = (lanes + BLOCK - 1) / BLOCK;
-    const uint32_t blocks = tiles < MAX_BLOCKS ? tiles : MAX_BLOCKS;
-    hipLaunchKernelGGL(mg_walk_tree_score, dim3(blocks, walkers), dim3(BLOCK), 0, stream, d_masks,
+    const uint32_t blocks = mg_walk_grid_blocks(lanes);
+    hipLaunchKernelGGL(mg_walk_tree_score, dim3(blocks, walkers), dim3(MG_WALK_BLOCK), 0, stream, d_masks,
                        d_amasks, d_resid, d_roots, d_atoms, d_code, lanes, n_roots, d_state);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;

@@ -521,14 +521,13 @@ class Engine:
         return WalkResult(out[:, :n_leaves], nfail.astype(np.int64), cost.astype(np.int64),
                           int(rounds.value), trace, int(winner.value), self.last_kernel_ms())
 
-    def walk_bound(self, lp: LoadedProgram, starts: np.ndarray, n_roots: int, trees, bounds,
-                   seed: int, lanes: int = 4096, max_rounds: int = 64, sync_every: int = 8,
-                   mask_probe0: int = 0, n_resid: Optional[int] = None):
-        """Tree-scored walk with moves aimed by equalities and orders
-        (mg_walk_bound, DESIGN.md §3.13): :meth:`walk_aim` with the table
-        ``bounds`` (``repair.bound_table``: ``entries`` (n, 5), ``pieces``
-        (m, 4) and ``fixed`` (n, 8) u32); with XOR entries only it is
-        :meth:`walk_aim` bit for bit."""
+    def _walk_rung(self, name: str, lp: LoadedProgram, starts: np.ndarray, n_roots: int, trees,
+                   bounds, ufs, sums, seed: int, lanes: int, max_rounds: int, sync_every: int,
+                   mask_probe0: int, n_resid: Optional[int]):
+        """What :meth:`walk_bound`, :meth:`walk_uf` and :meth:`walk_sum` share:
+        the arrays, the result buffers and the call of the C entry ``name``,
+        whose argument list has the lin words and side rows when ``sums`` is
+        given and the UF tables and U rows when ``ufs`` is."""
         from .repair import WalkResult
         n_leaves = len(lp.program.leaves)
         starts = np.ascontiguousarray(starts, dtype=np.uint32)
@@ -543,32 +542,46 @@ class Engine:
         entries = np.ascontiguousarray(bounds.entries, dtype=np.uint32)
         pieces = np.ascontiguousarray(bounds.pieces, dtype=np.uint32)
         fixed = np.ascontiguousarray(bounds.fixed, dtype=np.uint32)
+        lin = None if sums is None else np.ascontiguousarray(sums.lin, dtype=np.uint32)
         if entries.shape[1:] != (5,) or pieces.shape[1:] != (4,) or \
-                fixed.shape != (entries.shape[0], 8):
+                fixed.shape != (entries.shape[0], 8) or \
+                (lin is not None and lin.shape != (entries.shape[0],)):
             raise ValueError("bounds.entries must be (n, 5), bounds.pieces (m, 4), "
-                             "bounds.fixed (n, 8)")
+                             "bounds.fixed (n, 8)" + ("" if sums is None else ", sums.lin (n,)"))
+        tabs = None if ufs is None else _uf_arrays(ufs)
         n_resid = len(trees.probes) if n_resid is None else n_resid
         w1, r1 = max(1, min(walkers, 64)), max(1, min(int(max_rounds), 1 << 16))
         out = np.zeros((w1, max(1, n_leaves), 8), dtype=np.uint32)
         nfail, cost = np.zeros(w1, dtype=np.uint32), np.zeros(w1, dtype=np.uint32)
         trace = np.zeros((w1, r1, 2), dtype=np.uint32)
         rounds, winner = C.c_uint32(0), C.c_uint32(0)
-        rc = self.lib.mg_walk_bound(self._ctx, lp.handle,
-                                    _ptr(starts) if starts.size else _ptr(out), walkers,
-                                    max(0, int(n_roots)), mask_probe0,
-                                    _ptr(roots) if roots.size else _ptr(nfail), atoms.size,
-                                    _ptr(atoms) if atoms.size else None,
-                                    _ptr(code) if code.size else None, code.size,
-                                    max(0, int(n_resid)),
-                                    _ptr(entries) if entries.size else None, entries.shape[0],
-                                    _ptr(pieces) if pieces.size else None, pieces.shape[0],
-                                    _ptr(fixed) if fixed.size else None,
-                                    seed & (2**64 - 1), lanes, max_rounds, sync_every, _ptr(out),
-                                    _ptr(nfail), _ptr(cost), C.byref(rounds), _ptr(trace),
-                                    C.byref(winner))
-        self._check(rc, "mg_walk_bound")
+        args = [self._ctx, lp.handle, _ptr(starts) if starts.size else _ptr(out), walkers,
+                max(0, int(n_roots)), mask_probe0, _ptr(roots) if roots.size else _ptr(nfail),
+                atoms.size, _ptr(atoms) if atoms.size else None,
+                _ptr(code) if code.size else None, code.size, max(0, int(n_resid)),
+                _ptr(entries) if entries.size else None, entries.shape[0],
+                _ptr(pieces) if pieces.size else None, pieces.shape[0],
+                _ptr(fixed) if fixed.size else None]
+        if sums is not None:
+            args += [_ptr(lin) if lin.size else None, max(0, int(sums.n_srows))]
+        if ufs is not None:
+            args += [*_uf_args(tabs), max(0, int(ufs.n_urows))]
+        args += [seed & (2**64 - 1), lanes, max_rounds, sync_every, _ptr(out), _ptr(nfail),
+                 _ptr(cost), C.byref(rounds), _ptr(trace), C.byref(winner)]
+        self._check(getattr(self.lib, name)(*args), name)
         return WalkResult(out[:, :n_leaves], nfail.astype(np.int64), cost.astype(np.int64),
                           int(rounds.value), trace, int(winner.value), self.last_kernel_ms())
+
+    def walk_bound(self, lp: LoadedProgram, starts: np.ndarray, n_roots: int, trees, bounds,
+                   seed: int, lanes: int = 4096, max_rounds: int = 64, sync_every: int = 8,
+                   mask_probe0: int = 0, n_resid: Optional[int] = None):
+        """Tree-scored walk with moves aimed by equalities and orders
+        (mg_walk_bound, DESIGN.md §3.13): :meth:`walk_aim` with the table
+        ``bounds`` (``repair.bound_table``: ``entries`` (n, 5), ``pieces``
+        (m, 4) and ``fixed`` (n, 8) u32); with XOR entries only it is
+        :meth:`walk_aim` bit for bit."""
+        return self._walk_rung("mg_walk_bound", lp, starts, n_roots, trees, bounds, None, None,
+                               seed, lanes, max_rounds, sync_every, mask_probe0, n_resid)
 
     def walk_uf(self, lp: LoadedProgram, starts: np.ndarray, n_roots: int, trees, bounds, ufs,
                 seed: int, lanes: int = 4096, max_rounds: int = 64, sync_every: int = 8,
@@ -579,47 +592,8 @@ class Engine:
         program writes ``ufs.n_urows`` U rows after the residual probes
         (``repair.uf_view``).  With no slot piece it is :meth:`walk_bound` bit
         for bit."""
-        from .repair import WalkResult
-        n_leaves = len(lp.program.leaves)
-        starts = np.ascontiguousarray(starts, dtype=np.uint32)
-        if starts.ndim != 3 or starts.shape[1:] != (n_leaves, 8):
-            raise ValueError("starts must be (walkers, n_leaves, 8)")
-        walkers = starts.shape[0]
-        roots = np.ascontiguousarray(trees.roots, dtype=np.uint32)
-        atoms = np.ascontiguousarray(trees.atoms, dtype=np.uint32)
-        code = np.ascontiguousarray(trees.code, dtype=np.uint32)
-        if roots.shape != (max(0, int(n_roots)),) and 1 <= int(n_roots) <= 1024:
-            raise ValueError("trees.roots must have n_roots entries")
-        entries = np.ascontiguousarray(bounds.entries, dtype=np.uint32)
-        pieces = np.ascontiguousarray(bounds.pieces, dtype=np.uint32)
-        fixed = np.ascontiguousarray(bounds.fixed, dtype=np.uint32)
-        if entries.shape[1:] != (5,) or pieces.shape[1:] != (4,) or \
-                fixed.shape != (entries.shape[0], 8):
-            raise ValueError("bounds.entries must be (n, 5), bounds.pieces (m, 4), "
-                             "bounds.fixed (n, 8)")
-        tabs = _uf_arrays(ufs)
-        n_resid = len(trees.probes) if n_resid is None else n_resid
-        w1, r1 = max(1, min(walkers, 64)), max(1, min(int(max_rounds), 1 << 16))
-        out = np.zeros((w1, max(1, n_leaves), 8), dtype=np.uint32)
-        nfail, cost = np.zeros(w1, dtype=np.uint32), np.zeros(w1, dtype=np.uint32)
-        trace = np.zeros((w1, r1, 2), dtype=np.uint32)
-        rounds, winner = C.c_uint32(0), C.c_uint32(0)
-        rc = self.lib.mg_walk_uf(self._ctx, lp.handle,
-                                 _ptr(starts) if starts.size else _ptr(out), walkers,
-                                 max(0, int(n_roots)), mask_probe0,
-                                 _ptr(roots) if roots.size else _ptr(nfail), atoms.size,
-                                 _ptr(atoms) if atoms.size else None,
-                                 _ptr(code) if code.size else None, code.size,
-                                 max(0, int(n_resid)),
-                                 _ptr(entries) if entries.size else None, entries.shape[0],
-                                 _ptr(pieces) if pieces.size else None, pieces.shape[0],
-                                 _ptr(fixed) if fixed.size else None, *_uf_args(tabs),
-                                 max(0, int(ufs.n_urows)), seed & (2**64 - 1), lanes, max_rounds,
-                                 sync_every, _ptr(out), _ptr(nfail), _ptr(cost), C.byref(rounds),
-                                 _ptr(trace), C.byref(winner))
-        self._check(rc, "mg_walk_uf")
-        return WalkResult(out[:, :n_leaves], nfail.astype(np.int64), cost.astype(np.int64),
-                          int(rounds.value), trace, int(winner.value), self.last_kernel_ms())
+        return self._walk_rung("mg_walk_uf", lp, starts, n_roots, trees, bounds, ufs, None, seed,
+                               lanes, max_rounds, sync_every, mask_probe0, n_resid)
 
     def walk_sum(self, lp: LoadedProgram, starts: np.ndarray, n_roots: int, trees, bounds, ufs,
                  sums, seed: int, lanes: int = 4096, max_rounds: int = 64, sync_every: int = 8,
@@ -630,49 +604,8 @@ class Engine:
         ``bounds.entries``); the program writes ``sums.n_srows`` side rows
         after the residual probes and before the U rows.  With no linear entry
         it is :meth:`walk_uf` bit for bit."""
-        from .repair import WalkResult
-        n_leaves = len(lp.program.leaves)
-        starts = np.ascontiguousarray(starts, dtype=np.uint32)
-        if starts.ndim != 3 or starts.shape[1:] != (n_leaves, 8):
-            raise ValueError("starts must be (walkers, n_leaves, 8)")
-        walkers = starts.shape[0]
-        roots = np.ascontiguousarray(trees.roots, dtype=np.uint32)
-        atoms = np.ascontiguousarray(trees.atoms, dtype=np.uint32)
-        code = np.ascontiguousarray(trees.code, dtype=np.uint32)
-        if roots.shape != (max(0, int(n_roots)),) and 1 <= int(n_roots) <= 1024:
-            raise ValueError("trees.roots must have n_roots entries")
-        entries = np.ascontiguousarray(bounds.entries, dtype=np.uint32)
-        pieces = np.ascontiguousarray(bounds.pieces, dtype=np.uint32)
-        fixed = np.ascontiguousarray(bounds.fixed, dtype=np.uint32)
-        lin = np.ascontiguousarray(sums.lin, dtype=np.uint32)
-        if entries.shape[1:] != (5,) or pieces.shape[1:] != (4,) or \
-                fixed.shape != (entries.shape[0], 8) or lin.shape != (entries.shape[0],):
-            raise ValueError("bounds.entries must be (n, 5), bounds.pieces (m, 4), "
-                             "bounds.fixed (n, 8), sums.lin (n,)")
-        tabs = _uf_arrays(ufs)
-        n_resid = len(trees.probes) if n_resid is None else n_resid
-        w1, r1 = max(1, min(walkers, 64)), max(1, min(int(max_rounds), 1 << 16))
-        out = np.zeros((w1, max(1, n_leaves), 8), dtype=np.uint32)
-        nfail, cost = np.zeros(w1, dtype=np.uint32), np.zeros(w1, dtype=np.uint32)
-        trace = np.zeros((w1, r1, 2), dtype=np.uint32)
-        rounds, winner = C.c_uint32(0), C.c_uint32(0)
-        rc = self.lib.mg_walk_sum(self._ctx, lp.handle,
-                                  _ptr(starts) if starts.size else _ptr(out), walkers,
-                                  max(0, int(n_roots)), mask_probe0,
-                                  _ptr(roots) if roots.size else _ptr(nfail), atoms.size,
-                                  _ptr(atoms) if atoms.size else None,
-                                  _ptr(code) if code.size else None, code.size,
-                                  max(0, int(n_resid)),
-                                  _ptr(entries) if entries.size else None, entries.shape[0],
-                                  _ptr(pieces) if pieces.size else None, pieces.shape[0],
-                                  _ptr(fixed) if fixed.size else None,
-                                  _ptr(lin) if lin.size else None, max(0, int(sums.n_srows)),
-                                  *_uf_args(tabs), max(0, int(ufs.n_urows)), seed & (2**64 - 1),
-                                  lanes, max_rounds, sync_every, _ptr(out), _ptr(nfail),
-                                  _ptr(cost), C.byref(rounds), _ptr(trace), C.byref(winner))
-        self._check(rc, "mg_walk_sum")
-        return WalkResult(out[:, :n_leaves], nfail.astype(np.int64), cost.astype(np.int64),
-                          int(rounds.value), trace, int(winner.value), self.last_kernel_ms())
+        return self._walk_rung("mg_walk_sum", lp, starts, n_roots, trees, bounds, ufs, sums, seed,
+                               lanes, max_rounds, sync_every, mask_probe0, n_resid)
 
     def walk_batch(self, jobs, lanes: int = 4096, max_rounds: int = 64, sync_every: int = 8,
                    max_bytes: Optional[int] = None):

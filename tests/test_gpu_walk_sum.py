@@ -7,7 +7,9 @@ sync_every 1 and 8; on a generated case at the caps (64 side rows, 128 linear
 entries); tables without a linear entry against Engine.walk_uf; the refusals
 of the C ABI; repair_group(scored="sum") on the crafted cases, every model
 checked by oracle/smtlib_ref.py; and MYTHRIL_GPU_REPAIR=7 through get_model on
-a query of the `spend` shape in search form."""
+a query of the `spend` shape in search form.  mg_walk_bound and mg_walk_uf run
+the same kernels with narrower tables in the same workspace, so one test walks
+down the rungs on one engine, each against its own reference."""
 
 import ctypes as C
 import dataclasses
@@ -16,7 +18,9 @@ import functools
 import numpy as np
 import pytest
 
+import bound_cases as BC
 import sum_cases as SC
+import tree_cases as TC
 import uf_cases as UC
 import walk_cases as WK
 from mythril_amd import repair as RP
@@ -121,6 +125,45 @@ def test_a_table_without_a_linear_entry_is_walk_uf_bit_for_bit():
     starts = SC.starts("selector", 2)
     same(eng.walk_uf(lp, starts, n_roots, T, B, U, SC.SEED, 256, SHORT),
          eng.walk_sum(lp, starts, n_roots, T, B, U, S, SC.SEED, 256, SHORT))
+
+
+def test_a_lower_rung_reads_nothing_a_higher_rung_left_in_the_workspace():
+    """One engine, one workspace, down the rungs: linear entries and side rows,
+    then slots and U rows without them, then neither, then no entry at all.
+    3 walkers at 300 lanes: a full and a ragged tile each, several walker rows
+    of every state array."""
+    walkers, lanes = 3, 300
+    eng = get_engine(0)
+    load = lambda prog, view: eng.load(view, default_leafgen(prog), prog_seed=0)
+
+    name = "sum"
+    B, U, S = SC.tables(name)
+    assert S.n_linear > 0 and S.n_srows > 0
+    got = eng.walk_sum(load(SC.program(name), SC.view(name)), SC.starts(name, walkers),
+                       len(SC.case(name)[0]), SC.trees(name), B, U, S, SC.SEED, lanes,
+                       SC.MAX_ROUNDS[name])
+    same(got, SC.reference(name, walkers, lanes, SC.MAX_ROUNDS[name]))
+
+    name = "rekey"
+    B, U = UC.tables(name)
+    assert RP.has_slot_piece(B) and U.n_urows > 0
+    got = eng.walk_uf(load(UC.program(name), UC.view(name)), UC.starts(name, walkers),
+                      len(UC.case(name)[0]), UC.trees(name), B, U, UC.SEED, lanes,
+                      UC.MAX_ROUNDS[name])
+    same(got, UC.reference(name, walkers, lanes, UC.MAX_ROUNDS[name]))
+
+    name = "signed"
+    B = BC.bounds(name)
+    assert B.n_order > 0
+    lp = load(BC.program(name), BC.program(name))
+    got = eng.walk_bound(lp, BC.starts(name, walkers), len(BC.case(name)[0]), BC.trees(name), B,
+                         BC.SEED, lanes, BC.MAX_ROUNDS[name])
+    same(got, BC.reference(name, walkers, lanes, BC.MAX_ROUNDS[name]))
+
+    name = "nest"
+    got = eng.walk_bound(load(TC.program(name), TC.program(name)), TC.starts(name, walkers),
+                         len(TC.case(name)[0]), TC.trees(name), RP.make_bounds([]), TC.SEED, lanes, 16)
+    same(got, TC.reference(name, walkers, lanes, 16))
 
 
 # ---------------------------------------------------------------------------

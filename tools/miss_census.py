@@ -607,8 +607,8 @@ def uf_rows(wl, qi, n_cand, lanes, rounds, walkers):
     many sides of the read residual probes (both sides of every xor and
     difference a HAMMING or MAGNITUDE atom or simple root reads) resolve with
     the slots and how many did without, per reason the refused sides, every
-    walker's trace, and the device time per round beside mg_walk_bound's from
-    the same starts."""
+    walker's trace, and the device time per round beside mg_walk_bound's (the
+    same kernels on the table without slots) from the same starts."""
     import mythril_amd.model as M
     from mythril_amd import repair as RP
     from mythril_amd.smt import node as N
@@ -689,7 +689,7 @@ def sum_rows(wl, qi, n_cand, lanes, rounds, walkers):
     resolve or are linear with an eligible target under the rules of DESIGN.md
     3.15 beside how many resolved under 3.14's, per reason the sides still
     refused, every walker's trace, and the device time per round beside
-    scored="uf"'s from the same starts."""
+    scored="uf"'s (the same kernels on 3.14's table) from the same starts."""
     import mythril_amd.model as M
     from mythril_amd import repair as RP
     from mythril_amd.smt import node as N

@@ -1,10 +1,8 @@
 """Device time per round of mg_walk_bound beside mg_walk_aim on the same
 program, starts and XOR-only table (aim_cases `bytes`), in one run: aim, bound,
 aim alternating.  Prints median, min and max of kernel_ms / rounds.
-``--uf``: mg_walk_uf beside mg_walk_bound instead, on the same slot-free table:
-bound, uf, bound alternating.
-``--sum``: mg_walk_sum beside mg_walk_uf on the same linear-free table, 8
-rounds per call: uf, sum, uf alternating.
+(mg_walk_uf and mg_walk_sum run mg_walk_bound's kernels: there is nothing to
+time them against.)
 ``--batch G``: one Engine.walk_batch of G jobs beside G sequential
 Engine.walk_sum calls (measured twice) and a one-job batch beside the single
 walk, on the same program and table, 8 rounds per call, all variants
@@ -73,17 +71,7 @@ for walkers in (1, 16):
     starts = AC.starts(name, walkers)
     aim = lambda: eng.walk_aim(lp, starts, n_roots, T, A, AC.SEED, 4096, 64)
     bound = lambda: eng.walk_bound(lp, starts, n_roots, T, B, AC.SEED, 4096, 64)
-    uf = lambda: eng.walk_uf(lp, starts, n_roots, T, B, RP.no_ufs(), AC.SEED, 4096, 64)
-    uf8 = lambda: eng.walk_uf(lp, starts, n_roots, T, B, RP.no_ufs(), AC.SEED, 4096, 8)
-    sum8 = lambda: eng.walk_sum(lp, starts, n_roots, T, B, RP.no_ufs(), RP.no_sums(len(B)),
-                                AC.SEED, 4096, 8)
-    plan = (("uf_1", uf8), ("sum", sum8), ("uf_2", uf8)) if "--sum" in sys.argv else \
-        (("bound_1", bound), ("uf", uf), ("bound_2", bound)) if "--uf" in sys.argv else \
-        (("aim_1", aim), ("bound", bound), ("aim_2", aim))
-    if "--uf" in sys.argv:
-        aim = uf                                                     # the pair that is compared
-    if "--sum" in sys.argv:
-        aim, bound = sum8, uf8
+    plan = (("aim_1", aim), ("bound", bound), ("aim_2", aim))
     a, b = aim(), bound()                                            # warm up, and the same walk
     assert np.array_equal(a.leaves, b.leaves) and np.array_equal(a.trace, b.trace)
     assert a.rounds == b.rounds
