@@ -179,6 +179,71 @@ int mg_census(mg_ctx* ctx, const mg_prog* prog, const mg_gen* gen, uint64_t n_ca
               uint64_t* first_block, uint64_t* sole_block, int64_t* sole_index,
               uint64_t* nfail_hist, uint32_t* best_nfail, int64_t* best_index);
 
+/* The censuses of several programs over one candidate range in one launch
+ * sequence (csrc/mg_census_batch.h, mg_census_batch.hip).
+ * Like mg_census it serves the misses of Constraints.is_possible (reference
+ * laser/ethereum/state/constraints.py:26-45): a query that misses in several
+ * independent groups asks for one census per group.  jobs[k] names a program
+ * that carries its verdict mask as mg_census describes; all jobs share gen
+ * (seed and first_index), as the programs of mg_batch_search do.  Per chunk,
+ * one interpreter launch over all jobs and one launch of
+ * mg_census_batch_kernel; the counters of all jobs are preset by one upload
+ * and read by one copy.  Outputs: the seven outputs of mg_census for job k at
+ * pass + k * max_roots, first_block + k * max_roots, sole_block + k *
+ * max_roots, sole_index + k * max_roots, nfail_hist + k * (max_roots + 1),
+ * best_nfail[k] and best_index[k], each with mg_census's conventions and bit
+ * for bit what mg_census returns for job k alone; entries past a job's n_roots
+ * are zero (-1 in sole_index).  chunk 0: the largest multiple of 256, at most
+ * 2^16, at which the probe regions of all jobs fit 256 MiB.
+ * Refused with MG_E_ARG before any upload or launch, the message beginning
+ * "census_batch:": a null pointer; n_jobs outside 1..MG_CENSUS_BATCH_MAX_JOBS;
+ * a program of another context; a chunk that is not a multiple of 256, a
+ * first_index that is not a multiple of 64, 2^53 candidates or more; an
+ * explicit chunk whose probe regions exceed 256 MiB (the message gives the
+ * bytes needed), and jobs whose regions exceed it at 256 lanes (load the
+ * census view, or pass fewer jobs); and, as "census_batch: job k: ...", a
+ * job's n_roots above max_roots and whatever mg_census refuses for job k.
+ * n_cand = 0: empty censuses and no launch.  mg_last_kernel_ms covers the
+ * launches. */
+typedef struct mg_census_job {
+    const mg_prog* prog;
+    uint32_t n_roots, mask_probe0;
+} mg_census_job;
+/* The counts of one job that size its share of the batch's device buffer. */
+typedef struct mg_census_shape {
+    uint32_t n_probes;                /* of the job's program */
+    uint32_t n_roots, mask_probe0;
+} mg_census_shape;
+/* The cap of mg_walk_batch: the grid's y dimension allows 65535, and 256
+ * counter blocks of 1024 roots are about 10 MB to preset and to read. */
+#define MG_CENSUS_BATCH_MAX_JOBS 256u
+int mg_census_batch(mg_ctx* ctx, const mg_census_job* jobs, uint32_t n_jobs, const mg_gen* gen,
+                    uint64_t n_cand, uint64_t chunk, uint32_t max_roots, uint64_t* pass,
+                    uint64_t* first_block, uint64_t* sole_block, int64_t* sole_index,
+                    uint64_t* nfail_hist, uint32_t* best_nfail, int64_t* best_index);
+/* Host-only (no GPU): the plan of the device buffer mg_census_batch uses
+ * (csrc/mg_census_batch.h says what lies where).  out_offsets:
+ * [MG_CENSUS_BATCH_SHARED + n_jobs * MG_CENSUS_BATCH_JOB_REGIONS] byte
+ * offsets: the descriptors, the job records, then job by job its counter
+ * block and its probe region.  In address order — descriptors, records, all
+ * counter blocks, all probe regions — every region is 256-byte aligned and
+ * ends where the next begins, the last at *out_bytes.  *out_chunk: the
+ * candidates per launch (`chunk`, or what chunk 0 chooses).  MG_E_ARG for a
+ * null pointer, n_jobs outside 1..MG_CENSUS_BATCH_MAX_JOBS, a chunk that is
+ * no multiple of 256 or whose probe regions exceed 256 MiB, jobs that do not
+ * fit at 256 lanes, and sizes beyond 64 bits; `why` (may be NULL; why_len
+ * bytes) then receives the refusal as mg_census_batch words it, after the
+ * "census_batch: ". */
+#define MG_CENSUS_BATCH_SHARED 2
+#define MG_CENSUS_BATCH_JOB_REGIONS 2
+int mg_census_batch_plan_host(const mg_census_shape* shapes, uint32_t n_jobs, uint64_t n_cand,
+                              uint64_t chunk, uint64_t* out_offsets, uint64_t* out_bytes,
+                              uint64_t* out_chunk, char* why, size_t why_len);
+/* Host-only (no GPU): blocks per job of one mg_census_batch_kernel launch over
+ * n candidates: min(ceil(n / 256), max(1, 2048 / n_jobs)); tiles beyond are
+ * grid-strided.  0 for n_jobs = 0 or n = 0. */
+int mg_census_batch_blocks_host(uint32_t n_jobs, uint64_t n);
+
 /* Local search from a nearly satisfying assignment, e.g.
  * the census's best candidate.  No reference counterpart: like the census it
  * serves the misses of Constraints.is_possible (reference
@@ -627,6 +692,20 @@ int mg_batch_search(mg_ctx* ctx, mg_batch* batch, const mg_gen* gen, uint64_t n_
 int mg_batch_search_probes(mg_ctx* ctx, mg_batch* batch, const mg_gen* gen, uint64_t n_cand,
                            int64_t* first_sat, uint32_t* witness_leaves, uint32_t max_leaves,
                            uint32_t* witness_probes, uint32_t max_probes);
+/* The regeneration launch of mg_batch_search_probes with caller-given
+ * indices: pair i is candidate indices[i] of progs[i] under `seed`, its leaf
+ * values in leaves[i][max_leaves][8] and, when probes is not NULL, its probe
+ * values in probes[i][max_probes][8] — what mg_eval_gen returns for one lane
+ * at that index.  One launch for all pairs (65535 per launch).  A program may
+ * appear in many pairs.  Index -1 leaves the pair's rows zero.  It serves the
+ * misses of Constraints.is_possible, as mg_census does: the starts of a
+ * group's repair walks and the best candidate of its miss report are
+ * candidates its census names.  MG_E_ARG before any launch, the message
+ * beginning "batch_witness:": a null pointer, a program of another context,
+ * an index below -1, rows narrower than a program's leaves or probes. */
+int mg_batch_witness(mg_ctx* ctx, const mg_prog* const* progs, const int64_t* indices, uint32_t n,
+                     uint64_t seed, uint32_t* leaves, uint32_t max_leaves, uint32_t* probes,
+                     uint32_t max_probes);
 
 /* Compiled programs (batch path without interpretive dispatch; built on the
  * host by mythril_amd/jit.py): ``image`` is a gfx950 code object holding the

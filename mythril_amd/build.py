@@ -12,9 +12,9 @@ CSRC = os.path.join(ROOT, "mythril_amd", "csrc")
 LIBDIR = os.path.join(ROOT, "mythril_amd", "lib")
 LIB = os.path.join(LIBDIR, "libmythgpu.so")
 JIT_STUB = os.path.join(LIBDIR, "mg_jit_stub.s")
-SOURCES = ["mg_interp_asm.hip", "mg_keccak.hip", "mg_census.hip", "mg_repair.hip", "mg_walk.hip",
-           "mg_walk_tree.hip", "mg_walk_aim.hip", "mg_walk_sum.hip", "mg_walk_batch.hip",
-           "mg_host.cpp", "mg_api.cpp"]
+SOURCES = ["mg_interp_asm.hip", "mg_keccak.hip", "mg_census.hip", "mg_census_batch.hip",
+           "mg_repair.hip", "mg_walk.hip", "mg_walk_tree.hip", "mg_walk_aim.hip", "mg_walk_sum.hip",
+           "mg_walk_batch.hip", "mg_host.cpp", "mg_api.cpp"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("MYTHGPU_ARCH", "gfx950")
 
@@ -22,7 +22,8 @@ ARCH = os.environ.get("MYTHGPU_ARCH", "gfx950")
 def _deps():
     files = [os.path.join(CSRC, s) for s in SOURCES]
     files += [os.path.join(CSRC, "mg_device.h"), os.path.join(CSRC, "mg_host.h"),
-              os.path.join(CSRC, "mg_census.h"), os.path.join(CSRC, "mg_repair.h"),
+              os.path.join(CSRC, "mg_census.h"), os.path.join(CSRC, "mg_census_block.h"),
+              os.path.join(CSRC, "mg_census_batch.h"), os.path.join(CSRC, "mg_repair.h"),
               os.path.join(CSRC, "mg_walk.h"), os.path.join(CSRC, "mg_walk_tree.h"),
               os.path.join(CSRC, "mg_walk_aim.h"), os.path.join(CSRC, "mg_walk_bound.h"),
               os.path.join(CSRC, "mg_walk_uf.h"), os.path.join(CSRC, "mg_walk_sum.h"),

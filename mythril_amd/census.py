@@ -205,6 +205,56 @@ def _leafgen(prog: Program, form: str):
     return search_leafgen(prog) if form == "search" else default_leafgen(prog)
 
 
+def _explain_prepare(nodes: Sequence[N.Node], form: str):
+    """The host part of :func:`explain_group`: ``(out, job)`` with ``job`` None
+    for a group that launches nothing (``out`` is then its whole entry), else
+    ``(masked, plain, n_mask)``: the full masked program, the plain one and the
+    number of mask probes."""
+    from . import model as M
+    from .refute import refuted
+    out: dict = {"n_roots": len(nodes), "status": CENSUS}
+    if len(nodes) > 1 and refuted(nodes):
+        out["status"] = REFUTED
+        return out, None
+    if len(nodes) > MAX_ROOTS:
+        out.update(status=UNSUPPORTED, why="%d constraints (at most %d)" % (len(nodes), MAX_ROOTS))
+        return out, None
+    try:
+        plain = _compile(nodes, (), form)
+        ground = M._ground_value(plain)
+        if ground is not None:
+            out["status"] = GROUND_TRUE if ground else GROUND_FALSE
+            return out, None
+        masked = _compile(nodes, mask_probes(nodes), form)
+    except Unsupported as e:
+        out.update(status=UNSUPPORTED, why=str(e))
+        return out, None
+    n_mask = n_mask_probes(len(nodes))
+    if masked.n_user_probes != n_mask:
+        # solve mode drops the probes when the construction meets a false
+        # root: no model it builds can satisfy the group
+        out["status"] = DEAD if masked.n_user_probes == 0 else UNSUPPORTED
+        out["why"] = "%d mask probes compiled to %d" % (n_mask, masked.n_user_probes)
+        return out, None
+    return out, (masked, plain, n_mask)
+
+
+def _explain_census(out: dict, job, c: "Census") -> None:
+    masked, plain, _ = job
+    out.update(census=c, blockers=c.blockers(), records=masked.n_ins,
+               plain_records=plain.n_ins, plain_program=plain)
+
+
+def _explain_best(out: dict, job, n_roots: int, leaves, probes) -> None:
+    from .assign import unpack
+    masked, _, n_mask = job
+    c = out["census"]
+    holds = mask_bits(probes[:n_mask, :, None], n_roots)[0]
+    out["best"] = {"index": c.best_index, "nfail": c.best_nfail,
+                   "failing": [int(k) for k in np.flatnonzero(~holds)],
+                   "assignment": unpack(masked, leaves, probes if masked.solved else None)}
+
+
 def explain_group(nodes: Sequence[N.Node], n_cand: int = 1 << 16, form: str = "search",
                   device: int = 0, chunk: int = 0) -> dict:
     """The report entry of ONE independent group (root k = ``nodes[k]``):
@@ -212,48 +262,58 @@ def explain_group(nodes: Sequence[N.Node], n_cand: int = 1 << 16, form: str = "s
     ``blockers`` and the ``best`` candidate (index, failing roots, failing
     root indices, assignment regenerated on the full masked program)."""
     from . import model as M
-    from .assign import unpack
     from .engine import get_engine
-    from .refute import refuted
     nodes = list(nodes)
-    out: dict = {"n_roots": len(nodes), "status": CENSUS}
-    if len(nodes) > 1 and refuted(nodes):
-        out["status"] = REFUTED
+    out, job = _explain_prepare(nodes, form)
+    if job is None:
         return out
-    if len(nodes) > MAX_ROOTS:
-        out.update(status=UNSUPPORTED, why="%d constraints (at most %d)" % (len(nodes), MAX_ROOTS))
-        return out
-    try:
-        plain = _compile(nodes, (), form)
-        ground = M._ground_value(plain)
-        if ground is not None:
-            out["status"] = GROUND_TRUE if ground else GROUND_FALSE
-            return out
-        masked = _compile(nodes, mask_probes(nodes), form)
-    except Unsupported as e:
-        out.update(status=UNSUPPORTED, why=str(e))
-        return out
-    n_mask = n_mask_probes(len(nodes))
-    if masked.n_user_probes != n_mask:
-        # solve mode drops the probes when the construction meets a false
-        # root: no model it builds can satisfy the group
-        out["status"] = DEAD if masked.n_user_probes == 0 else UNSUPPORTED
-        out["why"] = "%d mask probes compiled to %d" % (n_mask, masked.n_user_probes)
-        return out
+    masked, _, n_mask = job
     eng = get_engine(device, nreg=masked.nreg)
     gens = _leafgen(masked, form)
     lp = eng.load(census_view(masked, n_mask), gens, prog_seed=0)
     c = eng.census(lp, M.SEARCH_SEED, 0, n_cand, len(nodes), 0, chunk)
-    out.update(census=c, blockers=c.blockers(), records=masked.n_ins,
-               plain_records=plain.n_ins, plain_program=plain)
+    _explain_census(out, job, c)
     if c.n_cand:
         full = eng.load(masked, gens, prog_seed=0)
         leaves, probes = eng.witness(full, M.SEARCH_SEED, c.best_index)
-        holds = mask_bits(probes[:n_mask, :, None], len(nodes))[0]
-        out["best"] = {"index": c.best_index, "nfail": c.best_nfail,
-                       "failing": [int(k) for k in np.flatnonzero(~holds)],
-                       "assignment": unpack(masked, leaves, probes if masked.solved else None)}
+        _explain_best(out, job, len(nodes), leaves, probes)
     return out
+
+
+def explain_groups(groups: Sequence[Sequence[N.Node]], n_cand: int = 1 << 16,
+                   form: str = "search", device: int = 0, chunk: int = 0) -> List[dict]:
+    """``[explain_group(g, ...) for g in groups]`` with the launches of all
+    groups batched: the censuses of the launched groups run
+    in one ``Engine.census_batch`` and their best candidates are regenerated
+    in one ``Engine.batch_witness`` — one of each per register layout, should
+    the groups' programs differ in it.  Every key of every entry is what
+    :func:`explain_group` returns but ``census.kernel_ms``, the device time of
+    the batch the group's census ran in."""
+    from . import model as M
+    from .engine import get_engine
+    groups = [list(g) for g in groups]
+    prepared = [_explain_prepare(g, form) for g in groups]
+    outs = [out for out, _ in prepared]
+    by_engine: Dict[int, list] = {}
+    for i, (_, job) in enumerate(prepared):
+        if job is not None:
+            eng = get_engine(device, nreg=job[0].nreg)
+            by_engine.setdefault(id(eng), [eng, []])[1].append(i)
+    for eng, idx in by_engine.values():
+        gens = {i: _leafgen(prepared[i][1][0], form) for i in idx}
+        views = [eng.load(census_view(prepared[i][1][0], prepared[i][1][2]), gens[i], prog_seed=0)
+                 for i in idx]
+        cs = eng.census_batch([(lp, len(groups[i]), 0) for lp, i in zip(views, idx)],
+                              M.SEARCH_SEED, 0, n_cand, chunk)
+        for i, c in zip(idx, cs):
+            _explain_census(outs[i], prepared[i][1], c)
+        best = [i for i in idx if outs[i]["census"].n_cand]
+        fulls = [eng.load(prepared[i][1][0], gens[i], prog_seed=0) for i in best]
+        wit = eng.batch_witness([(lp, outs[i]["census"].best_index) for lp, i in zip(fulls, best)],
+                                M.SEARCH_SEED)
+        for i, (leaves, probes) in zip(best, wit):
+            _explain_best(outs[i], prepared[i][1], len(groups[i]), leaves, probes)
+    return outs
 
 
 def explain(constraints: Sequence[N.Node], n_cand: int = 1 << 16, form: str = "search",
@@ -276,9 +336,9 @@ def explain(constraints: Sequence[N.Node], n_cand: int = 1 << 16, form: str = "s
     for i, c in enumerate(nodes):
         where.setdefault(c.id, []).append(i)
     groups = []
-    for b in dependence_buckets(nodes):
+    buckets = [list(b) for b in dependence_buckets(nodes)]
+    for b, g in zip(buckets, explain_groups(buckets, n_cand, form, device, chunk)):
         pos = [where[c.id].pop(0) for c in b]
-        g = explain_group(b, n_cand, form, device, chunk)
         g["constraints"] = pos
         if "blockers" in g:
             g["blockers"] = [pos[k] for k in g["blockers"]]

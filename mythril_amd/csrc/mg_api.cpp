@@ -24,6 +24,7 @@
 #include "mg_asm_handlers.h"
 #include "mg_host.h"
 #include "mg_census.h"
+#include "mg_census_batch.h"
 #include "mg_repair.h"
 #include "mg_walk.h"
 #include "mg_walk_tree.h"
@@ -60,6 +61,9 @@ hipError_t mg_launch_census(const uint32_t* d_rows, uint64_t stride, uint64_t n,
 // into the interpreter's eval-mode input; then, after the interpreter wrote
 // their verdict masks (rows = the first mask probe's rows, stride lanes), the
 // best neighbour into the base and its failing roots into trace[r]
+hipError_t mg_launch_census_batch(const mg_census_batch_job* d_jobs, uint32_t n_jobs,
+                                  uint64_t stride, uint64_t n, uint64_t first, uint64_t offset,
+                                  hipStream_t stream);
 hipError_t mg_launch_repair_round(uint32_t* d_base, const mg_leafgen* d_gen,
                                   const uint32_t* d_consts, uint32_t n_leaves, uint64_t seed,
                                   uint32_t r, uint32_t lanes, uint32_t* d_leaves,
@@ -828,11 +832,69 @@ int mg_search(mg_ctx* ctx, const mg_prog* prog, const mg_gen* gen, uint64_t n_ca
     return MG_OK;
 }
 
-// Candidates per census launch when the caller names none, and the largest
-// probe buffer one chunk may need (every probe of the loaded program has a
-// row set in it, written or not).
-#define MG_CENSUS_CHUNK (1ull << 16)
-#define MG_CENSUS_MAX_PROBE_BYTES ((size_t)256 << 20)
+// What mg_census refuses for one program and its mask (mg_census_batch asks
+// the same of every job): the message begins "census:".
+static int census_check_job(mg_ctx* ctx, const mg_prog* prog, uint32_t n_roots,
+                            uint32_t mask_probe0) {
+    if (!mg_census_roots_ok(n_roots))
+        return fail(ctx, MG_E_ARG, "census: n_roots %u outside 1..%u", n_roots, MG_CENSUS_MAX_ROOTS);
+    if (!mg_census_mask_ok(prog->n_probes, n_roots, mask_probe0))
+        return fail(ctx, MG_E_ARG, "census: mask probes %u..%u outside the program's %u probes",
+                    mask_probe0, mask_probe0 + (n_roots + 255) / 256 - 1, prog->n_probes);
+    return MG_OK;
+}
+
+// The arguments all programs of a census share; `who` begins the message
+// ("census", "census_batch").
+static int census_check_shared(mg_ctx* ctx, const char* who, const mg_gen* gen, uint64_t n_cand,
+                               uint64_t chunk) {
+    if (chunk % MG_BLOCK_LANES)
+        return fail(ctx, MG_E_ARG, "%s: chunk %llu is not a multiple of %u", who,
+                    (unsigned long long)chunk, MG_BLOCK_LANES);
+    if (gen->first_index % 64)
+        return fail(ctx, MG_E_ARG, "%s: first_index %llu is not a multiple of 64 (the "
+                    "generator draws one class per 64 indices)", who,
+                    (unsigned long long)gen->first_index);
+    if (n_cand >= (1ull << MG_CENSUS_OFFSET_BITS) ||
+        gen->first_index > (uint64_t)INT64_MAX - n_cand)
+        return fail(ctx, MG_E_ARG, "%s: %llu candidates from %llu: at most 2^%d, indices "
+                    "below 2^63", who, (unsigned long long)n_cand,
+                    (unsigned long long)gen->first_index, MG_CENSUS_OFFSET_BITS);
+    return MG_OK;
+}
+
+// The census of an empty range, and the outputs from a counter block h (as
+// mg_census.h lays it out for n_roots) read back from the device.
+static void census_empty(uint32_t n_roots, uint64_t* pass, uint64_t* first_block,
+                         uint64_t* sole_block, int64_t* sole_index, uint64_t* nfail_hist,
+                         uint32_t* best_nfail, int64_t* best_index) {
+    for (uint32_t k = 0; k < n_roots; ++k) {
+        pass[k] = first_block[k] = sole_block[k] = nfail_hist[k] = 0;
+        sole_index[k] = -1;
+    }
+    nfail_hist[n_roots] = 0;
+    *best_nfail = n_roots + 1;
+    *best_index = -1;
+}
+
+static void census_unpack(const unsigned long long* h, uint32_t n_roots, uint64_t first_index,
+                          uint64_t* pass, uint64_t* first_block, uint64_t* sole_block,
+                          int64_t* sole_index, uint64_t* nfail_hist, uint32_t* best_nfail,
+                          int64_t* best_index) {
+    for (uint32_t k = 0; k < n_roots; ++k) {
+        pass[k] = h[mg_census_pass(n_roots) + k];
+        first_block[k] = h[mg_census_first(n_roots) + k];
+        sole_block[k] = h[mg_census_sole(n_roots) + k];
+        const unsigned long long si = h[mg_census_sole_index(n_roots) + k];
+        sole_index[k] = si == ~0ull ? -1 : (int64_t)si;
+    }
+    for (uint32_t f = 0; f <= n_roots; ++f) nfail_hist[f] = h[mg_census_hist(n_roots) + f];
+    const unsigned long long best = h[mg_census_best(n_roots)];
+    if (best != ~0ull) {
+        *best_nfail = (uint32_t)(best >> MG_CENSUS_OFFSET_BITS);
+        *best_index = (int64_t)(first_index + (best & ((1ull << MG_CENSUS_OFFSET_BITS) - 1)));
+    }
+}
 
 int mg_census(mg_ctx* ctx, const mg_prog* prog, const mg_gen* gen, uint64_t n_cand,
               uint32_t n_roots, uint32_t mask_probe0, uint64_t chunk, uint64_t* pass,
@@ -841,44 +903,24 @@ int mg_census(mg_ctx* ctx, const mg_prog* prog, const mg_gen* gen, uint64_t n_ca
     if (!ctx || !prog || !gen || !pass || !first_block || !sole_block || !sole_index ||
         !nfail_hist || !best_nfail || !best_index)
         return fail(ctx, MG_E_ARG, "null argument");
-    if (n_roots < 1 || n_roots > MG_CENSUS_MAX_ROOTS)
-        return fail(ctx, MG_E_ARG, "census: n_roots %u outside 1..%u", n_roots, MG_CENSUS_MAX_ROOTS);
-    const uint32_t n_mask = (n_roots + 255) / 256;
-    if (mask_probe0 >= prog->n_probes || n_mask > prog->n_probes - mask_probe0)
-        return fail(ctx, MG_E_ARG, "census: mask probes %u..%u outside the program's %u probes",
-                    mask_probe0, mask_probe0 + n_mask - 1, prog->n_probes);
+    int rc = census_check_job(ctx, prog, n_roots, mask_probe0);
+    if (rc == MG_OK) rc = census_check_shared(ctx, "census", gen, n_cand, chunk);
+    if (rc != MG_OK) return rc;
     if (chunk == 0) chunk = MG_CENSUS_CHUNK;
-    if (chunk % MG_BLOCK_LANES)
-        return fail(ctx, MG_E_ARG, "census: chunk %llu is not a multiple of %u",
-                    (unsigned long long)chunk, MG_BLOCK_LANES);
-    if (gen->first_index % 64)
-        return fail(ctx, MG_E_ARG, "census: first_index %llu is not a multiple of 64 (the "
-                    "generator draws one class per 64 indices)",
-                    (unsigned long long)gen->first_index);
-    if (n_cand >= (1ull << MG_CENSUS_OFFSET_BITS) ||
-        gen->first_index > (uint64_t)INT64_MAX - n_cand)
-        return fail(ctx, MG_E_ARG, "census: %llu candidates from %llu: at most 2^%d, indices "
-                    "below 2^63", (unsigned long long)n_cand,
-                    (unsigned long long)gen->first_index, MG_CENSUS_OFFSET_BITS);
     if (chunk > MG_CENSUS_MAX_PROBE_BYTES / 32 / prog->n_probes)
         return fail(ctx, MG_E_ARG, "census: %u probes x %llu candidates per chunk exceed a %zu MiB "
                     "probe buffer; load the census view of the program (census.census_view: "
                     "only the mask probes are written) or pass a smaller chunk", prog->n_probes,
                     (unsigned long long)chunk, MG_CENSUS_MAX_PROBE_BYTES >> 20);
-    for (uint32_t k = 0; k < n_roots; ++k) {
-        pass[k] = first_block[k] = sole_block[k] = nfail_hist[k] = 0;
-        sole_index[k] = -1;
-    }
-    nfail_hist[n_roots] = 0;
-    *best_nfail = n_roots + 1;
-    *best_index = -1;
+    census_empty(n_roots, pass, first_block, sole_block, sole_index, nfail_hist, best_nfail,
+                 best_index);
     if (n_cand == 0) return MG_OK;
     HIPCHECK(ctx, hipSetDevice(ctx->device));
     const uint64_t lanes = n_cand < chunk ? n_cand : chunk;       // of the largest launch
     const size_t count_b = ((size_t)mg_census_words(n_roots) * 8 + 255) & ~(size_t)255;
     const size_t probe_b = (size_t)prog->n_probes * 8 * lanes * 4;
     void* ws;
-    int rc = workspace(ctx, count_b + probe_b + 256, &ws);
+    rc = workspace(ctx, count_b + probe_b + 256, &ws);
     if (rc) return rc;
     unsigned long long* d_count = (unsigned long long*)ws;
     uint32_t* d_probes = (uint32_t*)((uint8_t*)ws + count_b);
@@ -905,20 +947,135 @@ int mg_census(mg_ctx* ctx, const mg_prog* prog, const mg_gen* gen, uint64_t n_ca
                                  ctx->stream));
     HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
     timing_read(ctx);
-    for (uint32_t k = 0; k < n_roots; ++k) {
-        pass[k] = h[mg_census_pass(n_roots) + k];
-        first_block[k] = h[mg_census_first(n_roots) + k];
-        sole_block[k] = h[mg_census_sole(n_roots) + k];
-        const unsigned long long si = h[mg_census_sole_index(n_roots) + k];
-        sole_index[k] = si == ~0ull ? -1 : (int64_t)si;
-    }
-    for (uint32_t f = 0; f <= n_roots; ++f) nfail_hist[f] = h[mg_census_hist(n_roots) + f];
-    const unsigned long long best = h[mg_census_best(n_roots)];
-    if (best != ~0ull) {
-        *best_nfail = (uint32_t)(best >> MG_CENSUS_OFFSET_BITS);
-        *best_index = (int64_t)(gen->first_index + (best & ((1ull << MG_CENSUS_OFFSET_BITS) - 1)));
-    }
+    census_unpack(h.data(), n_roots, gen->first_index, pass, first_block, sole_block, sole_index,
+                  nfail_hist, best_nfail, best_index);
     return MG_OK;
+}
+
+// The censuses of several programs in one launch sequence (DESIGN.md §3.17,
+// csrc/mg_census_batch.h, mg_census_batch.hip): mg_census with a job axis.
+// Per chunk one interpreter launch over the batch's descriptor table, every
+// job writing its own probe region (probes_per_prog), and one launch of the
+// batched census kernel.  The row stride is the lanes of the largest launch
+// in every chunk, the last one included, so a job's rows stay where its
+// record says.
+int mg_census_batch(mg_ctx* ctx, const mg_census_job* jobs, uint32_t n_jobs, const mg_gen* gen,
+                    uint64_t n_cand, uint64_t chunk, uint32_t max_roots, uint64_t* pass,
+                    uint64_t* first_block, uint64_t* sole_block, int64_t* sole_index,
+                    uint64_t* nfail_hist, uint32_t* best_nfail, int64_t* best_index) {
+    if (!ctx) return MG_E_ARG;
+    if (!jobs || !gen || !pass || !first_block || !sole_block || !sole_index || !nfail_hist ||
+        !best_nfail || !best_index)
+        return fail(ctx, MG_E_ARG, "census_batch: null argument");
+    if (n_jobs < 1 || n_jobs > MG_CENSUS_BATCH_MAX_JOBS)
+        return fail(ctx, MG_E_ARG, "census_batch: %u jobs outside 1..%u", n_jobs,
+                    MG_CENSUS_BATCH_MAX_JOBS);
+    int rc = census_check_shared(ctx, "census_batch", gen, n_cand, chunk);
+    if (rc != MG_OK) return rc;
+    std::vector<mg_census_shape> shapes(n_jobs);
+    for (uint32_t g = 0; g < n_jobs; ++g) {
+        const mg_census_job& j = jobs[g];
+        if (!j.prog) return fail(ctx, MG_E_ARG, "census_batch: job %u: null program", g);
+        if (j.prog->ctx != ctx)
+            return fail(ctx, MG_E_ARG, "census_batch: job %u: a program of another context", g);
+        if (census_check_job(ctx, j.prog, j.n_roots, j.mask_probe0) != MG_OK) {
+            const std::string why = ctx->err;
+            return fail(ctx, MG_E_ARG, "census_batch: job %u: %s", g, why.c_str());
+        }
+        if (j.n_roots > max_roots)
+            return fail(ctx, MG_E_ARG, "census_batch: job %u: n_roots %u above max_roots %u", g,
+                        j.n_roots, max_roots);
+        shapes[g] = {j.prog->n_probes, j.n_roots, j.mask_probe0};
+    }
+    std::vector<uint64_t> off(MG_CB_SHARED + (size_t)n_jobs * MG_CB_JOB_REGIONS);
+    uint64_t bytes = 0, need = 0, count_w = 0, probe_w = 0, lanes_per = 0;
+    const int st = mg_census_batch_plan(shapes.data(), n_jobs, n_cand, chunk, off.data(), &bytes,
+                                        &lanes_per, &need, &count_w, &probe_w);
+    if (st != MG_CB_OK) {
+        char why[400];
+        mg_census_batch_why(st, n_jobs, chunk, need, why, sizeof why);
+        return fail(ctx, MG_E_ARG, "census_batch: %s", why);
+    }
+    chunk = lanes_per;
+    const size_t hist = (size_t)max_roots + 1;
+    for (uint32_t g = 0; g < n_jobs; ++g) {
+        // a row of max_roots entries per job: past the job's own roots, empty
+        census_empty(max_roots, pass + (size_t)g * max_roots, first_block + (size_t)g * max_roots,
+                     sole_block + (size_t)g * max_roots, sole_index + (size_t)g * max_roots,
+                     nfail_hist + g * hist, best_nfail + g, best_index + g);
+        best_nfail[g] = jobs[g].n_roots + 1;
+    }
+    if (n_cand == 0) return MG_OK;
+    HIPCHECK(ctx, hipSetDevice(ctx->device));
+    void* ws;
+    rc = workspace(ctx, (size_t)bytes + 256, &ws);
+    if (rc) return rc;
+    uint8_t* w = (uint8_t*)ws;
+    const uint64_t lanes = n_cand < chunk ? n_cand : chunk;       // of the largest launch
+    // the host image of everything uploaded: descriptors, job records and the
+    // counters (sums 0, minima ~0 per job), at the offsets of the plan
+    const size_t up_b = (size_t)off[MG_CB_OFF(0, MG_CB_PROBES)];
+    const size_t count0 = (size_t)off[MG_CB_OFF(0, MG_CB_COUNTS)];
+    std::vector<uint8_t> img(up_b, 0);
+    mg_pdesc* h_descs = (mg_pdesc*)(img.data() + off[MG_CB_DESCS]);
+    mg_census_batch_job* h_jobs = (mg_census_batch_job*)(img.data() + off[MG_CB_JOBS]);
+    uint32_t max_lds = 0;
+    for (uint32_t g = 0; g < n_jobs; ++g) {
+        const mg_census_job& j = jobs[g];
+        h_descs[g] = j.prog->h_desc;
+        if (j.prog->n_lds > max_lds) max_lds = j.prog->n_lds;
+        h_jobs[g].rows = (const uint32_t*)(w + off[MG_CB_OFF(g, MG_CB_PROBES)]) +
+                         (size_t)j.mask_probe0 * 8 * lanes;
+        h_jobs[g].out = (unsigned long long*)(w + off[MG_CB_OFF(g, MG_CB_COUNTS)]);
+        h_jobs[g].n_roots = j.n_roots;
+        unsigned long long* c = (unsigned long long*)(img.data() + off[MG_CB_OFF(g, MG_CB_COUNTS)]);
+        for (uint32_t k = mg_census_sole_index(j.n_roots); k < mg_census_words(j.n_roots); ++k)
+            c[k] = ~0ull;
+    }
+    HIPCHECK(ctx, hipMemcpyAsync(w, img.data(), up_b, hipMemcpyHostToDevice, ctx->stream));
+    const mg_pdesc* d_descs = (const mg_pdesc*)(w + off[MG_CB_DESCS]);
+    const mg_census_batch_job* d_jobs = (const mg_census_batch_job*)(w + off[MG_CB_JOBS]);
+    timing_begin(ctx);
+    for (uint64_t done = 0; done < n_cand; done += chunk) {
+        mg_run run = empty_run();
+        run.n_assign = n_cand - done < chunk ? n_cand - done : chunk;
+        run.stride = lanes;
+        run.probes = (uint32_t*)(w + off[MG_CB_OFF(0, MG_CB_PROBES)]);
+        run.probes_per_prog = 1;
+        run.probe_prog_words = probe_w;
+        run.seed = gen->seed;
+        run.first_index = gen->first_index + done;
+        HIPCHECK(ctx, launch(ctx, 1, d_descs, n_jobs, run, max_lds, ctx->stream));
+        HIPCHECK(ctx, mg_launch_census_batch(d_jobs, n_jobs, lanes, run.n_assign, run.first_index,
+                                             done, ctx->stream));
+    }
+    timing_end(ctx);
+    // all counter blocks in one copy (into the image's own counter regions)
+    HIPCHECK(ctx, hipMemcpyAsync(img.data() + count0, w + count0, up_b - count0,
+                                 hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
+    timing_read(ctx);
+    for (uint32_t g = 0; g < n_jobs; ++g)
+        census_unpack((const unsigned long long*)(img.data() + off[MG_CB_OFF(g, MG_CB_COUNTS)]),
+                      jobs[g].n_roots, gen->first_index, pass + (size_t)g * max_roots,
+                      first_block + (size_t)g * max_roots, sole_block + (size_t)g * max_roots,
+                      sole_index + (size_t)g * max_roots, nfail_hist + g * hist, best_nfail + g,
+                      best_index + g);
+    return MG_OK;
+}
+
+int mg_census_batch_plan_host(const mg_census_shape* shapes, uint32_t n_jobs, uint64_t n_cand,
+                              uint64_t chunk, uint64_t* out_offsets, uint64_t* out_bytes,
+                              uint64_t* out_chunk, char* why, size_t why_len) {
+    uint64_t need = 0;
+    const int st = mg_census_batch_plan(shapes, n_jobs, n_cand, chunk, out_offsets, out_bytes,
+                                        out_chunk, &need, nullptr, nullptr);
+    mg_census_batch_why(st, n_jobs, chunk, need, why, why_len);
+    return st == MG_CB_OK ? MG_OK : MG_E_ARG;
+}
+
+int mg_census_batch_blocks_host(uint32_t n_jobs, uint64_t n) {
+    return (int)mg_census_batch_blocks(n_jobs, n);
 }
 
 // The local search.  Rounds are queued back to back; after
@@ -2092,6 +2249,83 @@ int mg_batch_search_probes(mg_ctx* ctx, mg_batch* b, const mg_gen* gen, uint64_t
     HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
     timing_read(ctx);
     for (uint32_t i = 0; i < b->n; ++i) first_sat[i] = h[i] == ~0ull ? -1 : (int64_t)h[i];
+    return MG_OK;
+}
+
+// The regeneration launch above with caller-given indices:
+// lane 0 of pair i evaluates candidate indices[i] of progs[i].  The
+// descriptor table is built per call, one copy per pair, in the workspace.
+int mg_batch_witness(mg_ctx* ctx, const mg_prog* const* progs, const int64_t* indices, uint32_t n,
+                     uint64_t seed, uint32_t* leaves, uint32_t max_leaves, uint32_t* probes,
+                     uint32_t max_probes) {
+    if (!ctx) return MG_E_ARG;
+    if (n && (!progs || !indices || !leaves))
+        return fail(ctx, MG_E_ARG, "batch_witness: null argument");
+    uint32_t max_lds = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        if (!progs[i]) return fail(ctx, MG_E_ARG, "batch_witness: pair %u: null program", i);
+        if (progs[i]->ctx != ctx)
+            return fail(ctx, MG_E_ARG, "batch_witness: pair %u: a program of another context", i);
+        if (indices[i] < -1)
+            return fail(ctx, MG_E_ARG, "batch_witness: pair %u: index %lld", i,
+                        (long long)indices[i]);
+        if (progs[i]->n_leaves > max_leaves)
+            return fail(ctx, MG_E_ARG, "batch_witness: pair %u: leaf rows hold %u leaves, the "
+                        "program has %u", i, max_leaves, progs[i]->n_leaves);
+        if (probes && progs[i]->n_probes > max_probes)
+            return fail(ctx, MG_E_ARG, "batch_witness: pair %u: probe rows hold %u probes, the "
+                        "program has %u", i, max_probes, progs[i]->n_probes);
+        if (progs[i]->n_lds > max_lds) max_lds = progs[i]->n_lds;
+    }
+    if (n == 0) return MG_OK;
+    HIPCHECK(ctx, hipSetDevice(ctx->device));
+    const size_t desc_b = ((size_t)n * sizeof(mg_pdesc) + 255) & ~(size_t)255;
+    const size_t first_b = ((size_t)n * 8 + 255) & ~(size_t)255;
+    const size_t wit_b = (size_t)n * max_leaves * 8 * 4;
+    const size_t wit_b_al = (wit_b + 255) & ~(size_t)255;
+    const size_t prb_b = probes ? (size_t)n * max_probes * 8 * 4 : 0;
+    void* ws;
+    int rc = workspace(ctx, desc_b + first_b + wit_b_al + prb_b + 256, &ws);
+    if (rc) return rc;
+    uint8_t* w = (uint8_t*)ws;
+    // descriptors and indices in one upload (-1 is ~0: the pair's program returns)
+    std::vector<uint8_t> img(desc_b + first_b, 0);
+    mg_pdesc* h_descs = (mg_pdesc*)img.data();
+    uint64_t* h_first = (uint64_t*)(img.data() + desc_b);
+    for (uint32_t i = 0; i < n; ++i) {
+        h_descs[i] = progs[i]->h_desc;
+        h_first[i] = indices[i] < 0 ? ~0ull : (uint64_t)indices[i];
+    }
+    HIPCHECK(ctx, hipMemcpyAsync(w, img.data(), img.size(), hipMemcpyHostToDevice, ctx->stream));
+    const mg_pdesc* d_descs = (const mg_pdesc*)w;
+    const uint64_t* d_first = (const uint64_t*)(w + desc_b);
+    uint32_t* d_wit = (uint32_t*)(w + desc_b + first_b);
+    uint32_t* d_prb = prb_b ? (uint32_t*)(w + desc_b + first_b + wit_b_al) : nullptr;
+    if (wit_b) HIPCHECK(ctx, hipMemsetAsync(d_wit, 0, wit_b, ctx->stream));
+    if (prb_b) HIPCHECK(ctx, hipMemsetAsync(d_prb, 0, prb_b, ctx->stream));
+    timing_begin(ctx);
+    for (uint32_t p0 = 0; p0 < n; p0 += 65535) {
+        const uint32_t np = n - p0 < 65535 ? n - p0 : 65535;
+        mg_run run = empty_run();
+        run.n_assign = 1;
+        run.stride = 1;
+        run.seed = seed;
+        run.first_per_prog = d_first + p0;
+        run.leaves_out = d_wit + (size_t)p0 * max_leaves * 8;
+        run.lout_prog_words = (uint64_t)max_leaves * 8;
+        if (d_prb) {
+            run.probes = d_prb + (size_t)p0 * max_probes * 8;
+            run.probe_prog_words = (uint64_t)max_probes * 8;
+        }
+        HIPCHECK(ctx, launch(ctx, 1, d_descs + p0, np, run, max_lds, ctx->stream));
+    }
+    timing_end(ctx);
+    if (wit_b)
+        HIPCHECK(ctx, hipMemcpyAsync(leaves, d_wit, wit_b, hipMemcpyDeviceToHost, ctx->stream));
+    if (prb_b)
+        HIPCHECK(ctx, hipMemcpyAsync(probes, d_prb, prb_b, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
+    timing_read(ctx);
     return MG_OK;
 }
 

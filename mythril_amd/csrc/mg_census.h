@@ -4,6 +4,7 @@
 #ifndef MG_CENSUS_H
 #define MG_CENSUS_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #define MG_CENSUS_MAX_ROOTS 1024u
@@ -11,6 +12,12 @@
  * first index: 11 bits hold 0..1024 failing roots, so a census covers fewer
  * than 2^53 candidates */
 #define MG_CENSUS_OFFSET_BITS 53
+
+/* Candidates per census launch when the caller names none, and the largest
+ * probe buffer one chunk may need (every probe of the loaded program has a
+ * row set in it, written or not). */
+#define MG_CENSUS_CHUNK (1ull << 16)
+#define MG_CENSUS_MAX_PROBE_BYTES ((size_t)256 << 20)
 
 #define MG_CENSUS_FN static inline __attribute__((always_inline))
 #ifdef __HIPCC__

@@ -38,7 +38,8 @@ EXPORTS = ("mg_init", "mg_init_layout", "mg_layouts", "mg_free", "mg_last_error"
            "mg_walk_aim", "mg_walk_aim_mutate_host", "mg_walk_bound",
            "mg_walk_bound_mutate_host", "mg_walk_uf", "mg_walk_uf_resolve_host",
            "mg_walk_uf_mutate_host", "mg_walk_sum", "mg_walk_sum_mutate_host", "mg_walk_batch",
-           "mg_walk_batch_plan_host", "mg_walk_batch_shape_ok_host")
+           "mg_walk_batch_plan_host", "mg_walk_batch_shape_ok_host", "mg_census_batch",
+           "mg_census_batch_plan_host", "mg_census_batch_blocks_host", "mg_batch_witness")
 
 
 def layouts() -> Dict[int, Tuple[int, int]]:
@@ -103,7 +104,21 @@ class WalkShape(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("n_leaves", "n_probes") + _WALK_COUNTS]
 
 
+class CensusJob(C.Structure):
+    """mg_census_job (include/mythgpu.h): one job of mg_census_batch."""
+    _fields_ = [("prog", C.c_void_p), ("n_roots", C.c_uint32), ("mask_probe0", C.c_uint32)]
+
+
+class CensusShape(C.Structure):
+    """mg_census_shape: the counts that size a job's share of the census
+    batch's device buffer."""
+    _fields_ = [(n, C.c_uint32) for n in ("n_probes", "n_roots", "mask_probe0")]
+
+
 # include/mythgpu.h
+CENSUS_BATCH_MAX_JOBS = 256
+CENSUS_BATCH_SHARED = 2
+CENSUS_BATCH_JOB_REGIONS = 2
 WALK_BATCH_MAX_JOBS = 256
 WALK_BATCH_DEFAULT_BYTES = 1 << 30
 WALK_BATCH_SHARED = 5
@@ -183,6 +198,13 @@ def load_library(path: str = _LIB_PATH, check_digest: bool = True):
         lib.mg_walk_batch_plan_host.argtypes = [C.POINTER(WalkShape), u32, u32, u32, u32, p,
                                                 C.POINTER(u64)]
         lib.mg_walk_batch_shape_ok_host.argtypes = [C.POINTER(WalkShape)]
+        lib.mg_census_batch.argtypes = [p, C.POINTER(CensusJob), u32, C.POINTER(Gen), u64, u64, u32,
+                                        p, p, p, p, p, p, p]
+        lib.mg_census_batch_plan_host.argtypes = [C.POINTER(CensusShape), u32, u64, u64, p,
+                                                  C.POINTER(u64), C.POINTER(u64), C.c_char_p,
+                                                  C.c_size_t]
+        lib.mg_census_batch_blocks_host.argtypes = [u32, u64]
+        lib.mg_batch_witness.argtypes = [p, C.POINTER(p), p, u32, u64, p, u32, p, u32]
         lib.mg_batch_create.argtypes = [p, C.POINTER(p), u32, C.POINTER(p)]
         lib.mg_batch_free.argtypes = [p]
         lib.mg_batch_free.restype = None
@@ -380,6 +402,74 @@ class Engine:
                       sole_block=u[2][:n].astype(np.int64), sole_index=sole_index,
                       nfail_hist=u[3].astype(np.int64), best_nfail=int(best_nfail.value),
                       best_index=int(best_index.value), kernel_ms=self.last_kernel_ms())
+
+    def census_batch(self, jobs, seed: int, first_index: int, n_cand: int, chunk: int = 0):
+        """The censuses of several programs over the candidates [first_index,
+        first_index + n_cand) in one launch sequence (mg_census_batch,
+        DESIGN.md §3.17).  ``jobs``: a list of ``(lp, n_roots, mask_probe0)``,
+        the arguments of :meth:`census` that differ per program.  Returns one
+        :class:`mythril_amd.census.Census` per job, equal to ``census`` on it
+        alone (``kernel_ms``: the device time of the whole launch sequence the
+        job ran in).  More jobs than one batch takes, or jobs whose probe
+        regions exceed the library's probe buffer at 256 candidates per chunk,
+        run as consecutive sub-batches that fit (:func:`split_census_jobs`);
+        jobs are independent, so the results do not depend on the split."""
+        from .census import Census
+        jobs = [(lp, int(r), int(m)) for lp, r, m in jobs]
+        if not jobs:
+            return []
+        shapes = [CensusShape(lp.program.n_probes, max(0, r) & 0xFFFFFFFF, max(0, m) & 0xFFFFFFFF)
+                  for lp, r, m in jobs]
+        g = Gen(seed & (2**64 - 1), first_index)
+        out = []
+        for lo, hi in split_census_jobs(shapes):
+            n = hi - lo
+            arr = (CensusJob * n)()
+            for i, (lp, r, m) in enumerate(jobs[lo:hi]):
+                arr[i].prog, arr[i].n_roots, arr[i].mask_probe0 = lp.handle, max(0, r), max(0, m)
+            width = max(1, min(max(r for _, r, _ in jobs[lo:hi]), 1024))
+            u = [np.zeros((n, width), dtype=np.uint64) for _ in range(3)]
+            hist = np.zeros((n, width + 1), dtype=np.uint64)
+            sole_index = np.full((n, width), -1, dtype=np.int64)
+            best_nfail, best_index = np.zeros(n, dtype=np.uint32), np.full(n, -1, dtype=np.int64)
+            rc = self.lib.mg_census_batch(self._ctx, arr, n, C.byref(g), n_cand, chunk, width,
+                                          _ptr(u[0]), _ptr(u[1]), _ptr(u[2]), _ptr(sole_index),
+                                          _ptr(hist), _ptr(best_nfail), _ptr(best_index))
+            self._check(rc, "mg_census_batch")
+            ms = self.last_kernel_ms()
+            for i, (_, r, _) in enumerate(jobs[lo:hi]):
+                out.append(Census(n_roots=r, first_index=first_index, n_cand=n_cand,
+                                  pass_=u[0][i, :r].astype(np.int64),
+                                  first_block=u[1][i, :r].astype(np.int64),
+                                  sole_block=u[2][i, :r].astype(np.int64),
+                                  sole_index=sole_index[i, :r].copy(),
+                                  nfail_hist=hist[i, :r + 1].astype(np.int64),
+                                  best_nfail=int(best_nfail[i]), best_index=int(best_index[i]),
+                                  kernel_ms=ms))
+        return out
+
+    def batch_witness(self, pairs, seed: int, want_probes: bool = True):
+        """Leaves and probe values of many (program, candidate index) pairs in
+        one launch (mg_batch_witness): per pair ``(leaves,
+        probes)`` as :meth:`witness` returns them (``probes`` None without
+        ``want_probes``).  A program may appear in many pairs; index -1 gives
+        zero rows."""
+        pairs = [(lp, int(i)) for lp, i in pairs]
+        if not pairs:
+            return []
+        n = len(pairs)
+        max_leaves = max(1, max(len(lp.program.leaves) for lp, _ in pairs))
+        max_probes = max(1, max(lp.program.n_probes for lp, _ in pairs))
+        arr = (C.c_void_p * n)(*[lp.handle for lp, _ in pairs])
+        idx = np.array([i for _, i in pairs], dtype=np.int64)
+        wit = np.zeros((n, max_leaves, 8), dtype=np.uint32)
+        prb = np.zeros((n, max_probes, 8), dtype=np.uint32) if want_probes else None
+        rc = self.lib.mg_batch_witness(self._ctx, arr, _ptr(idx), n, seed & (2**64 - 1), _ptr(wit),
+                                       max_leaves, _ptr(prb), max_probes)
+        self._check(rc, "mg_batch_witness")
+        return [(wit[k, :len(lp.program.leaves)].copy(),
+                 prb[k, :lp.program.n_probes].copy() if want_probes else None)
+                for k, (lp, _) in enumerate(pairs)]
 
     def repair(self, lp: LoadedProgram, start_leaves: np.ndarray, n_roots: int, seed: int,
                lanes: int = 4096, max_rounds: int = 64, sync_every: int = 8,
@@ -994,6 +1084,57 @@ def split_walk_jobs(shapes: Sequence[WalkShape], walkers: int, lanes: int, max_r
             plan = walk_batch_plan_host(shapes[lo:lo + 1], walkers, lanes, max_rounds)
             raise EngineError("walk_batch: job %d alone needs %s bytes, max_bytes is %d"
                               % (lo, "more than 2^64" if plan is None else plan[1], max_bytes))
+        parts.append((lo, hi))
+        lo = hi
+    return parts
+
+
+def census_batch_plan_host(shapes: Sequence[CensusShape], n_cand: int, chunk: int = 0):
+    """Host-only (no GPU): ``(offsets, bytes, chunk)`` of the device buffer
+    mg_census_batch uses for jobs of these shapes (mg_census_batch_plan_host:
+    ``offsets`` u64, CENSUS_BATCH_SHARED shared regions and then
+    CENSUS_BATCH_JOB_REGIONS per job; ``chunk``: the candidates per launch).
+    :class:`EngineError` with the library's words when it refuses."""
+    lib = load_library(check_digest=False)
+    n = len(shapes)
+    arr = (CensusShape * max(1, n))(*shapes)
+    offs = np.zeros(CENSUS_BATCH_SHARED + max(1, n) * CENSUS_BATCH_JOB_REGIONS, dtype=np.uint64)
+    total, got = C.c_uint64(0), C.c_uint64(0)
+    why = C.create_string_buffer(512)
+    rc = lib.mg_census_batch_plan_host(arr, n, n_cand, chunk, _ptr(offs), C.byref(total),
+                                       C.byref(got), why, 512)
+    if rc != 0:
+        raise EngineError("census_batch: " + why.value.decode(errors="replace"))
+    return (offs[:CENSUS_BATCH_SHARED + n * CENSUS_BATCH_JOB_REGIONS], int(total.value),
+            int(got.value))
+
+
+def census_batch_blocks_host(n_jobs: int, n: int) -> int:
+    """Host-only: blocks per job of one mg_census_batch_kernel launch over
+    ``n`` candidates (mg_census_batch_blocks_host)."""
+    return int(load_library(check_digest=False).mg_census_batch_blocks_host(n_jobs, n))
+
+
+def split_census_jobs(shapes: Sequence[CensusShape], max_jobs: int = CENSUS_BATCH_MAX_JOBS):
+    """Consecutive ``(lo, hi)`` ranges that cover ``shapes`` once, in order,
+    each the longest run from its start that stays within ``max_jobs`` and
+    whose probe regions fit the library's probe buffer at 256 candidates per
+    chunk, the smallest chunk there is (with chunk 0 the library then chooses
+    the largest that fits).  A run of one job is always tried: what is wrong
+    with it alone, the library says."""
+    lib = load_library(check_digest=False)
+    offs = np.zeros(CENSUS_BATCH_SHARED + max_jobs * CENSUS_BATCH_JOB_REGIONS, dtype=np.uint64)
+    total, got = C.c_uint64(0), C.c_uint64(0)
+
+    def fits(lo, hi):
+        arr = (CensusShape * (hi - lo))(*shapes[lo:hi])
+        return lib.mg_census_batch_plan_host(arr, hi - lo, 256, 256, _ptr(offs), C.byref(total),
+                                             C.byref(got), None, 0) == 0
+    parts, lo, n = [], 0, len(shapes)
+    while lo < n:
+        hi = lo + 1
+        while hi < n and hi - lo < max_jobs and fits(lo, hi + 1):
+            hi += 1
         parts.append((lo, hi))
         lo = hi
     return parts

@@ -2019,11 +2019,48 @@ def repair_group(nodes: Sequence, n_cand: int = 1 << 16, form: str = "search", l
     steps = _repair_steps(nodes, n_cand, form, lanes, max_rounds, device, seed, sync_every, scored,
                           walkers)
     try:
-        walk = next(steps)
+        step = next(steps)
         while True:
-            walk = steps.send(walk.single())
+            step = steps.send(step.single())
     except StopIteration as done:
         return done.value
+
+
+class _CensusJob:
+    """Where :func:`_repair_steps` hands the census of its group to its driver:
+    ``single()`` is the ``Engine.census`` call :func:`repair_group` always
+    made; ``job`` is the same census as a job of ``Engine.census_batch`` on
+    ``eng`` (every group of a call shares seed, range and chunk)."""
+    stage = 0
+
+    def __init__(self, eng, view, n_roots, n_cand):
+        self.eng, self.view, self.n_roots, self.n_cand = eng, view, n_roots, n_cand
+        self.job = (view, n_roots, 0)
+
+    def single(self):
+        from . import model as M
+        return self.eng.census(self.view, M.SEARCH_SEED, 0, self.n_cand, self.n_roots, 0)
+
+
+class _WitnessJob:
+    """Where :func:`_repair_steps` asks for the leaves of the candidates
+    ``picks`` of the full masked program: a list of (n_leaves, 8) rows, one per
+    pick.  ``single()`` makes the ``Engine.witness`` calls :func:`repair_group`
+    always made, one per distinct index in the order of ``picks``; ``pairs``
+    are the same as pairs of ``Engine.batch_witness`` on ``eng``."""
+    stage = 1
+
+    def __init__(self, eng, full, picks):
+        self.eng, self.full, self.picks = eng, full, list(picks)
+        self.pairs = [(full, i) for i in self.picks]
+
+    def single(self):
+        from . import model as M
+        rows = {}
+        for i in self.picks:
+            if i not in rows:
+                rows[i] = self.eng.witness(self.full, M.SEARCH_SEED, i)[0]
+        return [rows[i] for i in self.picks]
 
 
 class _TreeWalk:
@@ -2033,6 +2070,8 @@ class _TreeWalk:
     a kind without a table gets the empty one, which by §3.12 - §3.15 is that
     kind bit for bit)."""
 
+    stage = 2
+
     def __init__(self, eng, job, single):
         self.eng, self.job, self.single = eng, job, single
 
@@ -2040,12 +2079,15 @@ class _TreeWalk:
 def _repair_steps(nodes, n_cand, form, lanes, max_rounds, device, seed, sync_every, scored,
                   walkers):
     """:func:`repair_group` in three steps, as a generator.  Prepare: compile,
-    build the tables, run the census, pick the starts.  Walk: a tree-scored
-    walk is yielded as a :class:`_TreeWalk` and its ``WalkResult`` sent back
-    (:func:`repair_group` runs it alone, :func:`repair_groups` in one batch
-    with the other groups'); the table-scored walk and the count walk run
-    here.  Finish: the fresh evaluation, ``failing``, ``atom_state``, the
-    assignment.  Returns the group's dict."""
+    build the tables, then two hand-overs: the census is yielded as a
+    :class:`_CensusJob` and its ``Census`` sent back, and the starts, picked
+    from it here on the host, as a :class:`_WitnessJob` whose rows are sent
+    back.  Walk: a tree-scored walk is yielded as a :class:`_TreeWalk` and its
+    ``WalkResult`` sent back.  :func:`repair_group` serves every hand-over with
+    the single call, :func:`repair_groups` with one batched call for all
+    groups; the table-scored walk and the count walk run here.  Finish: the
+    fresh evaluation, ``failing``, ``atom_state``, the assignment.  Returns the
+    group's dict."""
     from . import census as CS
     from . import model as M
     from .assign import unpack
@@ -2177,22 +2219,25 @@ def _repair_steps(nodes, n_cand, form, lanes, max_rounds, device, seed, sync_eve
     gens = CS._leafgen(masked, form)
     view = eng.load(CS.census_view(masked, n_mask), gens, prog_seed=0)
     full = eng.load(masked, gens, prog_seed=0)
-    c = eng.census(view, M.SEARCH_SEED, 0, n_cand, len(nodes), 0)
+    c = yield _CensusJob(eng, view, len(nodes), n_cand)
     out["census"] = c
     if not c.n_cand:
         return out
-    leaves, _ = eng.witness(full, M.SEARCH_SEED, c.best_index)
-    out["start"] = {"index": c.best_index, "nfail": c.best_nfail}
-    out["repair"] = None
-    seed = M.SEARCH_SEED if seed is None else seed
+    # the starts, picked on the host: the best candidate, then the sole
+    # blockers' candidates in rank order, padded with the best
+    picks = [c.best_index]
     if c.best_nfail and scored:
-        picks = [c.best_index]
         for k in c.blockers():
             if c.sole_index[k] >= 0 and int(c.sole_index[k]) not in picks:
                 picks.append(int(c.sole_index[k]))
         picks = (picks + [c.best_index] * walkers)[:walkers]
-        starts = np.stack([leaves if i == c.best_index else eng.witness(full, M.SEARCH_SEED, i)[0]
-                           for i in picks])
+    rows = yield _WitnessJob(eng, full, picks)
+    leaves = rows[0]
+    out["start"] = {"index": c.best_index, "nfail": c.best_nfail}
+    out["repair"] = None
+    seed = M.SEARCH_SEED if seed is None else seed
+    if c.best_nfail and scored:
+        starts = np.stack(rows)
         wide = eng.load(CS.census_view(masked, n_mask + n_amask + len(resid)), gens, prog_seed=0)
         n = len(nodes)
         if trees is not None and sums is not None:
@@ -2269,39 +2314,62 @@ def repair_groups(groups: Sequence[Sequence], n_cand: int = 1 << 16, form: str =
                   lanes: int = 4096, max_rounds: int = 64, device: int = 0,
                   seed: Optional[int] = None, sync_every: int = 8, scored=False,
                   walkers: int = 1, max_bytes: Optional[int] = None) -> List[dict]:
-    """``[repair_group(g, ...) for g in groups]`` with the tree-scored walks
-    of all groups in one ``Engine.walk_batch`` (``mg_walk_batch``, DESIGN.md
-    §3.16) — one per register layout, should the groups' programs differ in
-    it: every key of every dict is what :func:`repair_group` returns but
-    ``repair.kernel_ms``, the device time of the batch the group's walk ran
-    in.  Every group is prepared first (compile, tables, census and witness
-    launches, per group as before), then the walks run together, then every
-    group is finished.  Groups that end without a walk (refuted, ground,
-    unsupported, dead, satisfied by the census) and groups that fall back to
-    the table or the count run as :func:`repair_group` runs them."""
+    """``[repair_group(g, ...) for g in groups]`` with the launches of all
+    groups batched: their censuses in one ``Engine.census_batch``, their
+    starts in one ``Engine.batch_witness`` and their
+    tree-scored walks in one ``Engine.walk_batch`` (``mg_walk_batch``,
+    DESIGN.md §3.16) — one of each per register layout, should the groups'
+    programs differ in it: every key of every dict is what
+    :func:`repair_group` returns but ``census.kernel_ms`` and
+    ``repair.kernel_ms``, the device times of the batches the group ran in.
+    Every group is compiled and driven to its census, then to its starts,
+    then the walks run together, then every group is finished, per group.
+    Groups that end without a walk (refuted, ground, unsupported, dead,
+    satisfied by the census) and groups that fall back to the table or the
+    count run as :func:`repair_group` runs them."""
+    from . import model as M
     runs = [_repair_steps(g, n_cand, form, lanes, max_rounds, device, seed, sync_every, scored,
                           walkers) for g in groups]
     out: List[Optional[dict]] = [None] * len(runs)
-    waiting, engines = {}, []
-    for i, steps in enumerate(runs):
+    waiting = {}
+
+    def advance(i, value=None):
         try:
-            waiting[i] = next(steps)
+            waiting[i] = next(runs[i]) if value is None else runs[i].send(value)
         except StopIteration as done:
+            waiting.pop(i, None)
             out[i] = done.value
-            continue
-        if not any(e is waiting[i].eng for e in engines):
-            engines.append(waiting[i].eng)
-    for eng in engines:
-        idx = [i for i in waiting if waiting[i].eng is eng]
-        results = eng.walk_batch([waiting[i].job for i in idx], lanes, max_rounds, sync_every,
-                                 max_bytes)
-        for i, res in zip(idx, results):
-            try:
-                runs[i].send(res)
-            except StopIteration as done:
-                out[i] = done.value
+
+    for i in range(len(runs)):
+        advance(i)
+    walked = set()
+    while waiting:
+        # every group is driven to the earliest hand-over point any group waits
+        # at: all censuses, then all witnesses, then all walks
+        stage = min(w.stage for w in waiting.values())
+        engines = []
+        for w in waiting.values():
+            if w.stage == stage and not any(e is w.eng for e in engines):
+                engines.append(w.eng)
+        for eng in engines:
+            idx = [i for i in waiting if waiting[i].stage == stage and waiting[i].eng is eng]
+            if stage == _CensusJob.stage:
+                results = eng.census_batch([waiting[i].job for i in idx], M.SEARCH_SEED, 0, n_cand)
+            elif stage == _WitnessJob.stage:
+                pairs = [q for i in idx for q in waiting[i].pairs]
+                rows = [r for r, _ in eng.batch_witness(pairs, M.SEARCH_SEED, want_probes=False)]
+                results, at = [], 0
+                for i in idx:
+                    results.append(rows[at:at + len(waiting[i].picks)])
+                    at += len(waiting[i].picks)
             else:
-                raise RuntimeError("a group asked for a second walk")
+                if walked & set(idx):
+                    raise RuntimeError("a group asked for a second walk")
+                walked |= set(idx)
+                results = eng.walk_batch([waiting[i].job for i in idx], lanes, max_rounds,
+                                         sync_every, max_bytes)
+            for i, res in zip(idx, results):
+                advance(i, res)
     return out
 
 
