@@ -90,6 +90,12 @@ typedef struct mgc_input {
     int32_t abi_presets;
     int32_t n_cval;            /* length of cval (limbs)                       */
     int32_t n_string_bytes;    /* length of strings (bytes)                    */
+    /* eval form (solve == 0): 0 lowers through the simplifying constructor
+     * (constant folding and operand identities); 1 keeps the
+     * one-to-one lowering.  Last field, so a zero-initialised input has the
+     * pass on.  Either way the leaf table and the first n_const_values table
+     * rows are those of the one-to-one lowering. */
+    int32_t no_simplify;
 } mgc_input;
 
 typedef struct mgc_result mgc_result;
@@ -105,7 +111,10 @@ const char* mgc_error(const mgc_result* r);
 /* n_ins x 4 instruction words (mythgpu_ir.h layout) */
 const uint32_t* mgc_code(const mgc_result* r, int32_t* n_ins);
 /* constant table: n_rows x 8 limbs; the first n_const_values rows are the
- * CONST values (ascending), the rest the leaf pools */
+ * CONST values of the one-to-one lowering (ascending; the candidate
+ * generator's pool), then the leaf pools, then the `appended` rows (their
+ * count is in mgc_meta): constants only the simplifying constructor created
+ * (ascending), which instructions read and the generator never draws */
 const uint32_t* mgc_table(const mgc_result* r, int32_t* n_rows, int32_t* n_const_values);
 /* everything else as one JSON object:
  *   leaves        [[name, width, kind, source, chunk, entry], ...] in leaf
@@ -117,6 +126,8 @@ const uint32_t* mgc_table(const mgc_result* r, int32_t* n_rows, int32_t* n_const
  *   derived       [[leaf index, probe index], ...] (search mode)
  *   entry_keys    [[table, [[probe index per 256-bit key chunk], ...]], ...]
  *   lnodes, spills, reloads, hist [[op, count]], hist_order [op, ...]
+ *   folded        constructor calls a simplification rule answered
+ *   appended      table rows behind the leaf pools (see mgc_table)
  *   presets       {"vars": [[name, hex]], "arrays": [[name, [[offset, byte]]]]}
  *                 (abi_presets, when offsets were pinned) */
 const char* mgc_meta(const mgc_result* r);

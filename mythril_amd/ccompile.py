@@ -54,7 +54,7 @@ class _Input(ctypes.Structure):
          ("remat_mode", ctypes.c_int32), ("remat_k", ctypes.c_int32),
          ("keep_clean", ctypes.c_int32), ("search_hints", ctypes.c_int32),
          ("abi_presets", ctypes.c_int32), ("n_cval", ctypes.c_int32),
-         ("n_string_bytes", ctypes.c_int32)]
+         ("n_string_bytes", ctypes.c_int32), ("no_simplify", ctypes.c_int32)]
 
 
 def load():
@@ -115,9 +115,11 @@ def compile_native(constraints: Sequence, probes: Sequence = (),
                    nreg: int = I.NREG, extra_consts: Sequence[int] = (), leaf_pools: bool = False,
                    const_keys: bool = False, solve: bool = False, leaf_remat: Optional[str] = None,
                    keep_clean: Optional[bool] = None, search_hints: bool = False,
-                   abi_presets: bool = False):
+                   abi_presets: bool = False, simplify: Optional[bool] = None):
     """``ir.compile_constraints`` through the native compiler: the DAG is
-    walked by the _mythcc front-end in C, compiled by mgc_compile."""
+    walked by the _mythcc front-end in C, compiled by mgc_compile.
+    ``simplify``: the eval form's simplifying constructor (default
+    ``ir.SIMPLIFY``)."""
     from . import ir
     ext = _load_ext()
     M = (1 << 256) - 1
@@ -129,7 +131,7 @@ def compile_native(constraints: Sequence, probes: Sequence = (),
         list(constraints), list(probes), _OPS, list((table_sizes or {}).items()), default_entries,
         nreg, extra, int(leaf_pools), int(const_keys), int(solve), mode, k,
         int(ir.KEEP_CLEAN if keep_clean is None else keep_clean), int(search_hints),
-        int(abi_presets))
+        int(abi_presets), int(not (ir.SIMPLIFY if simplify is None else simplify)))
     if rc != MGC_OK:
         if rc == MGC_UNSUPPORTED:
             raise ir.Unsupported(err)
@@ -222,7 +224,8 @@ def compile_native_ctypes(constraints: Sequence, probes: Sequence = (),
                           nreg: int = I.NREG, extra_consts: Sequence[int] = (),
                           leaf_pools: bool = False, const_keys: bool = False, solve: bool = False,
                           leaf_remat: Optional[str] = None, keep_clean: Optional[bool] = None,
-                          search_hints: bool = False, abi_presets: bool = False):
+                          search_hints: bool = False, abi_presets: bool = False,
+                          simplify: Optional[bool] = None):
     """The same compile through the plain C ABI (libmythcc.so, ctypes): the
     DAG flattened in Python (:func:`flatten`) into mgc_input arrays — what
     another FFI host does."""
@@ -241,7 +244,8 @@ def compile_native_ctypes(constraints: Sequence, probes: Sequence = (),
                  len(f["table_name"]), P["table_name"], P["table_size"], default_entries, nreg,
                  len(f["extra"]) // 32, P["extra"], int(leaf_pools), int(const_keys), int(solve),
                  mode, k, int(ir.KEEP_CLEAN if keep_clean is None else keep_clean),
-                 int(search_hints), int(abi_presets), len(f["cval"]) // 4, len(f["strings"]))
+                 int(search_hints), int(abi_presets), len(f["cval"]) // 4, len(f["strings"]),
+                 int(not (ir.SIMPLIFY if simplify is None else simplify)))
     res = ctypes.c_void_p()
     rc = lib.mgc_compile(ctypes.byref(inp), ctypes.byref(res))
     try:
@@ -311,7 +315,8 @@ class LeafRecords(_abc.Sequence):
 def _program(code, raw: bytes, ncv: int, meta):
     from . import ir
     consts = np.frombuffer(raw, dtype="<u4").reshape(-1, 8).astype(np.uint32)
-    const_values = [int.from_bytes(raw[32 * i:32 * i + 32], "little") for i in range(ncv)]
+    rows = [int.from_bytes(raw[32 * i:32 * i + 32], "little") for i in range(len(raw) // 32)]
+    const_values = ir.ConstValues(rows[:ncv], rows[ncv:])
     Leaf = ir.Leaf
     if meta.get("leaves_rs") is not None:
         leaves = LeafRecords(meta["leaves_rs"], meta["leaf_widths"])
@@ -320,7 +325,8 @@ def _program(code, raw: bytes, ncv: int, meta):
     hist_counts = dict(meta["hist"])
     stats = {"lnodes": meta["lnodes"], "n_ins": int(code.shape[0]), "spills": meta["spills"],
              "reloads": meta["reloads"],
-             "hist": {I.OPNAME[op]: hist_counts[op] for op in meta["hist_order"]}}
+             "hist": {I.OPNAME[op]: hist_counts[op] for op in meta["hist_order"]},
+             "folded": meta["folded"]}
     prog = ir.Program(code, consts, const_values, leaves, meta["n_lds"], meta["n_probes"],
                       meta["n_roots"], dict(meta["table_sizes"]), dict(meta["table_kinds"]),
                       {k: [int(h, 16) for h in v] for k, v in meta["table_ckeys"]}, stats,
@@ -329,6 +335,7 @@ def _program(code, raw: bytes, ncv: int, meta):
     # native compile phases (us): decode, lower, solve, sinks, schedule,
     # allocate, pools, metadata — diagnostics only (tools/compile_profile.py)
     prog.compile_us = meta.get("t_us")
+    prog.appended = meta["appended"]
     pre = meta.get("presets")
     if pre is not None:
         from .abi import Plan

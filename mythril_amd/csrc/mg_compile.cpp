@@ -131,6 +131,16 @@ static inline const U& mask(int w) { return MASKS[w < 0 ? 0 : (w > 64 * U::N ? 6
 static U U1(int k) { return shl(U::of(1), k); }
 static bool nz(const U& a) { return !a.zero(); }
 
+// plain long division (one quotient bit per step); b != 0
+static void udivmod(const U& a, const U& b, U& q, U& r) {
+    q = U(); r = U();
+    for (int i = a.bitlen() - 1; i >= 0; i--) {
+        r = shl(r, 1);
+        if (a.bit(i)) r.w[0] |= 1;
+        if (r >= b) { r = r - b; q.w[i >> 6] |= 1ull << (i & 63); }
+    }
+}
+
 static std::string hex(const U& a) {
     char buf[8];
     std::string s;
@@ -411,7 +421,199 @@ struct Lowerer {
         slot_id.swap(ids);
         slot_hash.swap(hs);
     }
+    // -- the simplifying constructor (eval form; ir._Lowerer._rule) ------------
+    bool simplify = false;
+    int64_t folded = 0;
+
+    static bool simplify_op(int op) {            // ir._SIMPLIFY_OPS
+        switch (op) {
+        case MG_ADD: case MG_SUB: case MG_MUL: case MG_NEG: case MG_AND: case MG_OR: case MG_XOR:
+        case MG_NOT: case MG_SHL: case MG_LSHR: case MG_ASHR: case MG_UDIV: case MG_UREM:
+        case MG_SDIV: case MG_SREM: case MG_SMOD: case MG_ITE: case MG_CONCAT: case MG_EXTRACT:
+        case MG_SEXT: case MG_EQ: case MG_ULT: case MG_ULE: case MG_SLT: case MG_SLE:
+        case MG_UMULNO: return true;
+        default: return false;
+        }
+    }
+
+    // ir.const_eval: a value op at width w on canonical operand values
+    static U const_eval(int op, int w, const U* v, int imm) {
+        const U m = mask(w);
+        if (op == MG_CONCAT) return (shl(v[0], imm) | v[1]) & m;
+        if (op == MG_EXTRACT) return shr(v[0], imm) & m;
+        if (op == MG_SEXT) {
+            U x = v[0] & mask(imm);
+            if (x.bit(imm - 1)) x = x | ~mask(imm);
+            return x & m;
+        }
+        auto neg = [&m](const U& x) { return (U() - x) & m; };
+        const U a = v[0] & m;
+        if (op == MG_NEG) return neg(a);
+        if (op == MG_NOT) return ~a & m;
+        const U b = v[1] & m;
+        const U bit1 = U::of(1), none = U();
+        switch (op) {
+        case MG_ADD: return (a + b) & m;
+        case MG_SUB: return (a - b) & m;
+        case MG_MUL: return (a * b) & m;
+        case MG_AND: return a & b;
+        case MG_OR: return a | b;
+        case MG_XOR: return a ^ b;
+        case MG_SHL: return b >= U::of((uint64_t)w) ? none : shl(a, (int)b.w[0]) & m;
+        case MG_LSHR: return b >= U::of((uint64_t)w) ? none : shr(a, (int)b.w[0]);
+        case MG_ASHR: {
+            U sa = a.bit(w - 1) ? (a | ~m) : a;
+            int k = b >= U::of((uint64_t)(w - 1)) ? w - 1 : (int)b.w[0];
+            return sar(sa, k) & m;
+        }
+        case MG_UDIV: case MG_UREM: {
+            if (b.zero()) return op == MG_UDIV ? m : a;
+            U q, r;
+            udivmod(a, b, q, r);
+            return op == MG_UDIV ? q : r;
+        }
+        case MG_SDIV: case MG_SREM: case MG_SMOD: {
+            bool na = a.bit(w - 1), nb = b.bit(w - 1);
+            U ua = na ? neg(a) : a, ub = nb ? neg(b) : b;
+            U q = m, r = ua;
+            if (!ub.zero()) udivmod(ua, ub, q, r);
+            if (op == MG_SDIV) return na != nb ? neg(q) : q;
+            if (op == MG_SREM) return na ? neg(r) : r;
+            if (r.zero() || !(na || nb)) return r;
+            if (na && nb) return neg(r);
+            return (na ? b - r : r + b) & m;
+        }
+        case MG_EQ: return a == b ? bit1 : none;
+        case MG_ULT: return a < b ? bit1 : none;
+        case MG_ULE: return a <= b ? bit1 : none;
+        case MG_SLT: case MG_SLE: {
+            U h = U1(w - 1);                 // signed order = unsigned order of x ^ sign bit
+            U x = a ^ h, y = b ^ h;
+            return (op == MG_SLT ? x < y : x <= y) ? bit1 : none;
+        }
+        case MG_UMULNO: {
+            if (a.zero() || b.zero()) return bit1;
+            if (a.bitlen() + b.bitlen() >= w + 2) return none;   // a * b >= 2^w
+            return a * b <= m ? bit1 : none;                      // < 2^257: fits
+        }
+        default: throw std::runtime_error("const_eval: op");
+        }
+    }
+
+    int shl_form(int x, int k, int w) {          // ir._Lowerer._shl_form
+        if (k == 0) return x;
+        if (k >= w) return cnst(0, w);
+        int e = mki(MG_EXTRACT, w - k, {x}, 0);
+        int z = cnst(0, k);
+        return mki(MG_CONCAT, w, {e, z}, k);
+    }
+    int div_guard(int x, int w, uint64_t other) {   // ir._Lowerer._div_guard
+        int z = cnst(0, w);
+        int e = mk(MG_EQ, w, {x, z});
+        int ones = cnst(mask(w), w);
+        int t = cnst(other, w);
+        return mk(MG_ITE, w, {e, ones, t});
+    }
+
+    // ir._Lowerer._rule; -1 for None
+    int rule(int op, int w, const Args& args, const U& imm) {
+        const U m = mask(w);
+        auto isc = [this](int x) { return ln[x].op == MG_CONST; };
+        if (op == MG_ITE) {
+            int c = args[0], a = args[1], b = args[2];
+            if (isc(c)) return (ln[c].imm.w[0] & 1) ? a : b;
+            if (a == b) return a;
+            return -1;
+        }
+        bool all = true;
+        for (int x : args) if (!isc(x)) { all = false; break; }
+        if (all) {
+            U v[2];
+            for (size_t i = 0; i < args.size() && i < 2; i++) v[i] = ln[args[i]].imm;
+            return cnst(const_eval(op, w, v, (int)imm.w[0]), is_pred(op) ? 1 : w);
+        }
+        if (args.size() != 2 || op == MG_CONCAT) return -1;
+        int a = args[0], b = args[1];
+        if (a == b) {
+            switch (op) {
+            case MG_SUB: case MG_XOR: return cnst(0, w);
+            case MG_AND: case MG_OR: return ln[a].width <= w ? a : -1;
+            case MG_EQ: case MG_ULE: case MG_SLE: return cnst(1, 1);
+            case MG_ULT: case MG_SLT: return cnst(0, 1);
+            case MG_UREM: case MG_SREM: case MG_SMOD: return cnst(0, w);
+            case MG_UDIV: case MG_SDIV: return div_guard(a, w, 1);
+            default: return -1;
+            }
+        }
+        if (op == MG_ADD || op == MG_MUL || op == MG_AND || op == MG_OR || op == MG_XOR ||
+            op == MG_UMULNO) {                   // commutative
+            int x;
+            U c;
+            if (isc(a)) { x = b; c = ln[a].imm & m; }
+            else if (isc(b)) { x = a; c = ln[b].imm & m; }
+            else return -1;
+            bool fits = ln[x].width <= w;
+            const U one = U::of(1);
+            switch (op) {
+            case MG_ADD:
+                if (c.zero() && fits) return x;
+                break;
+            case MG_MUL:
+                if (c.zero()) return cnst(0, w);
+                if (c == one && fits) return x;
+                if ((c & (c - one)).zero() && fits) return shl_form(x, c.bitlen() - 1, w);
+                if ((c & (c + one)).zero() && fits) {
+                    int s = shl_form(x, c.bitlen(), w);
+                    return mk(MG_SUB, w, {s, x});
+                }
+                break;
+            case MG_AND:
+                if (c.zero()) return cnst(0, w);
+                if (c == m && fits) return x;
+                break;
+            case MG_OR:
+                if (c.zero() && fits) return x;
+                if (c == m) return cnst(m, w);
+                break;
+            case MG_XOR:
+                if (c.zero() && fits) return x;
+                break;
+            default:
+                if (c <= one) return cnst(1, 1);
+                break;
+            }
+            return -1;
+        }
+        if (isc(b)) {
+            const U c = ln[b].imm & m;
+            bool fits = ln[a].width <= w;
+            if (c.zero()) {
+                if ((op == MG_SUB || op == MG_UREM || op == MG_SREM || op == MG_SHL ||
+                     op == MG_LSHR || op == MG_ASHR) && fits)
+                    return a;
+                if (op == MG_UDIV) return cnst(m, w);
+                if (op == MG_ULT) return cnst(0, 1);
+            }
+            if (c == U::of(1)) {
+                if ((op == MG_UDIV || op == MG_SDIV) && fits) return a;
+                if (op == MG_UREM || op == MG_SREM) return cnst(0, w);
+            }
+            if (c == m && op == MG_ULE) return cnst(1, 1);
+        } else if (isc(a) && (ln[a].imm & m).zero()) {
+            if (op == MG_UDIV || op == MG_SDIV) return div_guard(b, w, 0);
+            if (op == MG_UREM || op == MG_SREM || op == MG_SHL || op == MG_LSHR || op == MG_ASHR)
+                return cnst(0, w);
+            if (op == MG_ULE) return cnst(1, 1);
+        }
+        return -1;
+    }
+
     int mk(int op, int width, Args args, bool has_imm = false, const U& imm = U()) {
+        if (simplify && !args.empty() && simplify_op(op)) {
+            const U im = has_imm ? imm : U();     // (imm may live in ln: copy before it grows)
+            int r = rule(op, width, args, im);
+            if (r >= 0) { folded++; return r; }
+        }
         if (op == MG_CONCAT && width == MG_MAX_WIDTH && ln[args[0]].op == MG_EXTRACT &&
             ln[args[0]].imm.zero() && ln[ln[args[0]].args[0]].width == MG_MAX_WIDTH)
             args[0] = ln[args[0]].args[0];
@@ -1047,6 +1249,7 @@ struct Lowerer {
 static const int PASSES = 6;
 static const int MAX_REFUSALS = 4;          // solve.MAX_REFUSALS
 static const int SCHEDULE_MIN_SCRATCH = 10; // ir.SCHEDULE_MIN_SCRATCH
+static const double SIMPLIFY_MIN_HEAVY = 0.01;   // ir.SIMPLIFY_MIN_HEAVY
 static const int MAX_DOMAIN = 16;
 static const int MAX_BRANCHES = 4;
 static const int MAX_OR = 64;
@@ -3037,6 +3240,8 @@ static void compile(const mgc_input* in, mgc_result* res) {
         lw.table_sizes.put(strings[in->table_name[t]], in->table_size[t]);
     }
     lw.solve = in->solve != 0;
+    lw.simplify = !in->no_simplify && !in->solve;
+    const OMap<std::string, int> given_sizes = lw.table_sizes;
     if (in->const_keys || in->solve) {
         std::unordered_map<std::string, int> sym_counts;
         const std::vector<int> all_order = topo(S, all);  // after the presets
@@ -3074,9 +3279,19 @@ static void compile(const mgc_input* in, mgc_result* res) {
     tp[3] = now_us();
     Memo probe_memo;
     Chunks sinks;
+    std::unordered_set<int> rooted;
     for (size_t i = 0; i < roots.size(); i++) {
         lw.birth = births[i];
-        sinks.push_back(lw.mk(MG_ROOT, 1, {roots[i]}));
+        if (lw.simplify && rooted.count(roots[i])) {
+            // roots that fold to one node (a constant): each constraint
+            // keeps a ROOT record of its own (not hash-consed)
+            lw.ln.push_back(LN{MG_ROOT, 1, Args{roots[i]}, false, U(),
+                               std::max(births[i], lw.ln[roots[i]].birth)});
+            sinks.push_back((int)lw.ln.size() - 1);
+        } else {
+            sinks.push_back(lw.mk(MG_ROOT, 1, {roots[i]}));
+        }
+        rooted.insert(roots[i]);
     }
     int probe_chunks = 0;
     for (int p : probes) {
@@ -3123,10 +3338,64 @@ static void compile(const mgc_input* in, mgc_result* res) {
     tp[4] = now_us();
     std::unordered_set<int> fused;
     std::vector<int> order = fuse_roots(lw.ln, schedule(lw.ln, sinks), fused);
+    // a leaf whose readers all folded away is still generated (last, into a
+    // slot that stays free): the leaves a launch writes back are the whole
+    // candidate
+    std::vector<int> unread;
+    if (lw.folded) {
+        std::vector<char> have(lw.leaves.size(), 0);
+        for (int n : order) if (lw.ln[n].op == MG_LEAF) have[(size_t)lw.ln[n].imm.w[0]] = 1;
+        for (size_t i = 0; i < lw.leaves.size(); i++)
+            if (!have[i]) unread.push_back(lw.mki(MG_LEAF, lw.leaves[i].width, {}, (int64_t)i));
+        order.insert(order.end(), unread.begin(), unread.end());
+    }
     tp[5] = now_us();
     U M256 = mask(256);
-    std::vector<U> const_values;
-    for (int n : order) if (lw.ln[n].op == MG_CONST) const_values.push_back(lw.ln[n].imm & M256);
+    std::vector<U> used_consts, const_values;
+    for (int n : order) if (lw.ln[n].op == MG_CONST) used_consts.push_back(lw.ln[n].imm & M256);
+    if (lw.folded) {
+        // the candidate stream must not move (ir._plain_lowering): the
+        // generator's pool is the constant set of the lowering without the
+        // rules, and a leaf keeps its index
+        Lowerer plain(S, in->default_entries);
+        plain.table_sizes = given_sizes;
+        plain.table_ckeys = lw.table_ckeys;
+        Chunks stack;
+        for (int c : cons) stack.push_back(plain.lower(c)[0]);
+        for (int p : probes) { Chunks chs = plain.lower(p); stack.insert(stack.end(), chs.begin(), chs.end()); }
+        if (stack.empty()) stack.push_back(plain.cnst(1, 1));
+        bool same = plain.leaves.size() == lw.leaves.size();
+        for (size_t i = 0; same && i < lw.leaves.size(); i++) {
+            const Leaf &x = plain.leaves[i], &y = lw.leaves[i];
+            same = x.name == y.name && x.width == y.width && x.kind == y.kind &&
+                   x.source == y.source && x.chunk == y.chunk && x.entry == y.entry;
+        }
+        std::vector<char> seen(plain.ln.size(), 0);
+        size_t reach = 0, heavy = 0;
+        while (!stack.empty()) {
+            int n = stack.back();
+            stack.pop_back();
+            if (seen[n]) continue;
+            seen[n] = 1;
+            reach++;
+            const LN& x = plain.ln[n];
+            if (x.op == MG_CONST) const_values.push_back(x.imm & M256);
+            heavy += x.op == MG_MUL || x.op == MG_UDIV || x.op == MG_UREM || x.op == MG_SDIV ||
+                     x.op == MG_SREM || x.op == MG_SMOD || x.op == MG_UMULNO;
+            for (int a : x.args) stack.push_back(a);
+        }
+        // a table key that folded, or a program without heavy arithmetic
+        // (ir.SIMPLIFY_MIN_HEAVY): the plain program
+        if (!same || (double)heavy < SIMPLIFY_MIN_HEAVY * (double)reach) {
+            mgc_input off = *in;
+            off.no_simplify = 1;
+            *res = mgc_result();
+            compile(&off, res);
+            return;
+        }
+    } else {
+        const_values = used_consts;
+    }
     for (int i = 0; i < in->n_extra; i++) {
         U v;
         for (int j = 0; j < 8; j++) v.w[j / 2] |= (uint64_t)in->extra[8 * i + j] << (32 * (j & 1));
@@ -3137,6 +3406,22 @@ static void compile(const mgc_input* in, mgc_result* res) {
     const_values.erase(std::unique(const_values.begin(), const_values.end()), const_values.end());
     std::unordered_map<U, int, UHash> const_index;
     for (size_t i = 0; i < const_values.size(); i++) const_index[const_values[i]] = (int)i;
+    // the leaf pools sit behind the CONST values; behind them the constants
+    // only the rules created (never candidate values)
+    std::vector<std::vector<U>> pools;
+    size_t n_pool_rows = 0;
+    if (in->leaf_pools) {
+        pools = leaf_pools(lw.ln, order, lw.leaves);
+        for (const auto& pl : pools) n_pool_rows += pl.size();
+    }
+    std::sort(used_consts.begin(), used_consts.end());
+    used_consts.erase(std::unique(used_consts.begin(), used_consts.end()), used_consts.end());
+    std::vector<U> appended;
+    for (const U& u : used_consts)
+        if (!const_index.count(u)) {
+            const_index[u] = (int)(const_values.size() + n_pool_rows + appended.size());
+            appended.push_back(u);
+        }
     Alloc al0(lw.ln, order, const_index, fused, in->nreg, in->remat_mode, in->remat_k,
               in->keep_clean != 0);
     al0.run();
@@ -3151,6 +3436,7 @@ static void compile(const mgc_input* in, mgc_result* res) {
     std::unique_ptr<Alloc> al2;
     if (!in->solve && !in->leaf_pools && al0.n_lds - LDS_TIER >= SCHEDULE_MIN_SCRATCH) {
         order2 = fuse_roots(lw.ln, schedule_demand(lw.ln, sinks), fused2);
+        order2.insert(order2.end(), unread.begin(), unread.end());
         try {
             al2.reset(new Alloc(lw.ln, order2, const_index, fused2, in->nreg, in->remat_mode,
                                 in->remat_k, in->keep_clean != 0));
@@ -3178,10 +3464,8 @@ static void compile(const mgc_input* in, mgc_result* res) {
     // constant table: the CONST values, then every non-empty leaf pool,
     // written straight as limbs
     std::vector<std::pair<int, int>> pool_ranges;
-    std::vector<std::vector<U>> pools;
     size_t n_rows = const_values.size();
     if (in->leaf_pools) {
-        pools = leaf_pools(lw.ln, order, lw.leaves);
         for (size_t li = 0; li < pools.size(); li++) {
             if (!pools[li].empty()) {
                 pool_ranges.push_back({(int)n_rows, (int)pools[li].size()});
@@ -3191,6 +3475,7 @@ static void compile(const mgc_input* in, mgc_result* res) {
             }
         }
     }
+    n_rows += appended.size();
     res->n_rows = (int32_t)n_rows;
     res->n_const_values = (int32_t)const_values.size();
     res->table.resize(8 * n_rows);
@@ -3202,6 +3487,7 @@ static void compile(const mgc_input* in, mgc_result* res) {
     for (const U& u : const_values) put(u);
     for (const auto& pl : pools)
         for (const U& u : pl) put(u);
+    for (const U& u : appended) put(u);
 
     tp[7] = now_us();
     // -- metadata ---------------------------------------------------------------
@@ -3307,6 +3593,8 @@ static void compile(const mgc_input* in, mgc_result* res) {
     o += "],\"lnodes\":" + std::to_string(ord.size());
     o += ",\"spills\":" + std::to_string(al.n_spill);
     o += ",\"reloads\":" + std::to_string(al.n_reload);
+    o += ",\"folded\":" + std::to_string(lw.folded);
+    o += ",\"appended\":" + std::to_string(appended.size());
     o += ",\"hist\":[";
     {
         bool first = true;

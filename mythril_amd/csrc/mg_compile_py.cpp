@@ -6,7 +6,7 @@
 //
 // _mythcc.compile(constraints, probes, ops, tables, default_entries, nreg,
 //                 extra, leaf_pools, const_keys, solve, remat_mode, remat_k,
-//                 keep_clean, search_hints, abi_presets)
+//                 keep_clean, search_hints, abi_presets[, no_simplify])
 //   -> (rc, error, code bytes, table bytes, n_const_values, meta json)
 // `ops` maps operator names to mgc_source_ops() codes, `tables` is a list of
 // (name, size), `extra` the extra constants as 32-byte little-endian rows.
@@ -239,10 +239,11 @@ fail:
 PyObject* py_compile(PyObject*, PyObject* a) {
     PyObject *cons, *probes, *ops, *tables, *extra;
     int default_entries, nreg, leaf_pools, const_keys, solve, remat_mode, remat_k, keep_clean;
-    int search_hints, abi_presets;
-    if (!PyArg_ParseTuple(a, "OOO!OiiSiiiiiiii", &cons, &probes, &PyDict_Type, &ops, &tables,
+    int search_hints, abi_presets, no_simplify = 0;
+    if (!PyArg_ParseTuple(a, "OOO!OiiSiiiiiiii|i", &cons, &probes, &PyDict_Type, &ops, &tables,
                           &default_entries, &nreg, &extra, &leaf_pools, &const_keys, &solve,
-                          &remat_mode, &remat_k, &keep_clean, &search_hints, &abi_presets))
+                          &remat_mode, &remat_k, &keep_clean, &search_hints, &abi_presets,
+                          &no_simplify))
         return nullptr;
     PyObject* oth = PyDict_GetItemString(ops, "?");
     if (!oth) { PyErr_SetString(PyExc_KeyError, "ops has no '?'"); return nullptr; }
@@ -291,6 +292,7 @@ PyObject* py_compile(PyObject*, PyObject* a) {
     in.leaf_pools = leaf_pools; in.const_keys = const_keys; in.solve = solve;
     in.remat_mode = remat_mode; in.remat_k = remat_k; in.keep_clean = keep_clean;
     in.search_hints = search_hints; in.abi_presets = abi_presets;
+    in.no_simplify = no_simplify;
     in.n_cval = (int32_t)f.cval.size(); in.n_string_bytes = (int32_t)f.strings.size();
     mgc_result* res = nullptr;
     int rc;

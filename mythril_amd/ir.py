@@ -89,11 +89,34 @@ class Leaf:
     entry: int = 0
 
 
+class ConstValues(list):
+    """``Program.const_values``: the CONST values the candidate generator
+    draws from — its length, iteration and equality are that pool's, rows
+    0 .. len - 1 of the constant table.  An index past the pool reads the
+    table row of that index (a leaf pool's entry, or a constant only the
+    simplifying constructor created), so ``const_values[imm]`` is the value
+    of any CONST record."""
+
+    __slots__ = ("rest",)
+
+    def __init__(self, pool=(), rest=()):
+        super().__init__(pool)
+        self.rest = tuple(rest)
+
+    def __getitem__(self, i):
+        if isinstance(i, int) and i >= len(self):
+            return self.rest[i - len(self)]
+        return super().__getitem__(i)
+
+    def __reduce__(self):
+        return (ConstValues, (list(self), self.rest))
+
+
 @dataclass
 class Program:
     code: np.ndarray                  # (n_ins, 4) uint32
     consts: np.ndarray                # (n_consts, 8) uint32
-    const_values: List[int]
+    const_values: List[int]           # (a ConstValues)
     leaves: List[Leaf]
     n_lds: int
     n_probes: int
@@ -124,6 +147,9 @@ class Program:
     # register slots of the layout it was compiled for (16, or 11: the
     # four-wave layout); a context of that layout loads it (Engine.load)
     nreg: int = 16
+    # rows of ``consts`` behind ``const_values`` and the leaf pools: constants
+    # only the simplifying constructor created (never candidate values)
+    appended: int = 0
 
     @property
     def solved(self) -> bool:
@@ -146,6 +172,104 @@ def _limbs(value: int) -> List[int]:
     return [(value >> (32 * j)) & 0xFFFFFFFF for j in range(8)]
 
 
+# The simplifying constructor of the eval form (``_Lowerer._rule``; DESIGN.md
+# §3.1): on unless MYTHRIL_GPU_SIMPLIFY=0, which gives the programs of the
+# plain one-to-one lowering (the A/B knob, both compilers).
+SIMPLIFY = _os.environ.get("MYTHRIL_GPU_SIMPLIFY", "1") != "0"
+# ... for programs with heavy arithmetic only: multiply / division / overflow
+# test LNodes per LNode of the plain lowering (every C2 program has over 4 %,
+# the query streams' programs at most 0.3 %, as with AUTO_ALWAYS_HEAVY below).
+# A stream program's folds are constant keys of store chains and the ITEs
+# over them; folding them moves its spill placement and the handler variants
+# it executes and removes no VALU-bound work.
+SIMPLIFY_MIN_HEAVY = 0.01
+_PRED_OPS = (I.EQ, I.ULT, I.ULE, I.SLT, I.SLE, I.UMULNO)
+_SIMPLIFY_OPS = frozenset((I.ADD, I.SUB, I.MUL, I.NEG, I.AND, I.OR, I.XOR, I.NOT, I.SHL, I.LSHR,
+                           I.ASHR, I.UDIV, I.UREM, I.SDIV, I.SREM, I.SMOD, I.ITE, I.CONCAT,
+                           I.EXTRACT, I.SEXT) + _PRED_OPS)
+# every rule's tag (``_Lowerer.fired`` counts them; tests/test_simplify.py
+# demands that each one fires)
+SIMPLIFY_RULES = tuple(
+    ["const:" + I.OPNAME[op] for op in sorted(_SIMPLIFY_OPS - {I.ITE})] +
+    ["same:" + I.OPNAME[op] for op in (I.SUB, I.XOR, I.AND, I.OR, I.EQ, I.ULE, I.SLE, I.ULT, I.SLT,
+                                       I.UREM, I.SREM, I.SMOD, I.UDIV, I.SDIV)] +
+    ["ITE:const", "ITE:same", "ADD:0", "MUL:0", "MUL:1", "MUL:pow2", "MUL:pow2m1", "AND:0",
+     "AND:ones", "OR:0", "OR:ones", "XOR:0", "UMULNO:01", "UDIV:x,0", "ULT:x,0", "ULE:x,ones",
+     "ULE:0,x"] +
+    [I.OPNAME[op] + ":x,0" for op in (I.SUB, I.UREM, I.SREM, I.SHL, I.LSHR, I.ASHR)] +
+    [I.OPNAME[op] + ":x,1" for op in (I.UDIV, I.SDIV, I.UREM, I.SREM)] +
+    [I.OPNAME[op] + ":0,x" for op in (I.UDIV, I.SDIV, I.UREM, I.SREM, I.SHL, I.LSHR, I.ASHR)])
+
+
+def const_eval(op: int, w: int, v: Sequence[int], imm) -> int:
+    """Value of a value op at width ``w`` (a comparison's operand width) on
+    the canonical operand values ``v``: SMT-LIB 2.6 as include/mythgpu_ir.h
+    states it (division by zero: quotient all ones, remainder the dividend)."""
+    m = (1 << w) - 1
+    if op == I.CONCAT:
+        return ((v[0] << imm) | v[1]) & m
+    if op == I.EXTRACT:
+        return (v[0] >> imm) & m
+    if op == I.SEXT:
+        x = v[0] & ((1 << imm) - 1)
+        return (x - (1 << imm) if x >> (imm - 1) else x) & m
+    a = v[0] & m
+    if op == I.NEG:
+        return -a & m
+    if op == I.NOT:
+        return ~a & m
+    b = v[1] & m
+    if op == I.ADD:
+        return (a + b) & m
+    if op == I.SUB:
+        return (a - b) & m
+    if op == I.MUL:
+        return (a * b) & m
+    if op == I.AND:
+        return a & b
+    if op == I.OR:
+        return a | b
+    if op == I.XOR:
+        return a ^ b
+    if op == I.SHL:
+        return 0 if b >= w else (a << b) & m
+    if op == I.LSHR:
+        return 0 if b >= w else a >> b
+    if op == I.ASHR:
+        sa = a - (1 << w) if a >> (w - 1) else a
+        return (sa >> min(b, w - 1)) & m
+    if op == I.UDIV:
+        return m if b == 0 else a // b
+    if op == I.UREM:
+        return a if b == 0 else a % b
+    if op in (I.SDIV, I.SREM, I.SMOD):
+        na, nb = a >> (w - 1), b >> (w - 1)
+        ua, ub = (-a & m if na else a), (-b & m if nb else b)
+        if op == I.SDIV:
+            q = m if ub == 0 else ua // ub
+            return -q & m if na != nb else q
+        r = ua if ub == 0 else ua % ub
+        if op == I.SREM:
+            return -r & m if na else r
+        if r == 0 or not (na or nb):
+            return r
+        if na and nb:
+            return -r & m
+        return (b - r if na else r + b) & m
+    if op == I.EQ:
+        return int(a == b)
+    if op == I.ULT:
+        return int(a < b)
+    if op == I.ULE:
+        return int(a <= b)
+    if op in (I.SLT, I.SLE):
+        h = 1 << (w - 1)                     # signed order = unsigned order of x ^ sign bit
+        return int((a ^ h) < (b ^ h)) if op == I.SLT else int((a ^ h) <= (b ^ h))
+    if op == I.UMULNO:
+        return int(a * b <= m)
+    raise AssertionError("const_eval: op %d" % op)
+
+
 class _Lowerer:
     def __init__(self, table_sizes: Dict[str, int], default_entries: int):
         self.table = {}
@@ -164,9 +288,140 @@ class _Lowerer:
         self.solve = False
         self.solve_tables: set = set()
         self.arg_entries: Dict[str, List[Tuple[List[LNode], List[LNode]]]] = {}
+        # eval form: the simplifying constructor, the constructor calls a
+        # rule answered and how often each rule did
+        self.simplify = False
+        self.folded = 0
+        self.fired: Dict[str, int] = {}
+
+    # -- the simplifying constructor (eval form) ----------------
+    def _hit(self, tag: str, n: LNode) -> LNode:
+        self.fired[tag] = self.fired.get(tag, 0) + 1
+        return n
+
+    def _shl_form(self, x: LNode, k: int, w: int) -> LNode:
+        """x << k at width w as ``_by_constant`` builds a constant SHL."""
+        if k == 0:
+            return x
+        if k >= w:
+            return self.const(0, w)
+        return self.mk(I.CONCAT, w, (self.mk(I.EXTRACT, w - k, (x,), 0), self.const(0, k)), k)
+
+    def _div_guard(self, x: LNode, w: int, other: int) -> LNode:
+        """ITE(x = 0, ones, other): x / x (other 1) and 0 / x (other 0)."""
+        e = self.mk(I.EQ, w, (x, self.const(0, w)))
+        ones = self.const((1 << w) - 1, w)
+        return self.mk(I.ITE, w, (e, ones, self.const(other, w)))
+
+    def _rule(self, op: int, w: int, args, imm) -> Optional[LNode]:
+        """The node a rule of the simplifying constructor answers
+        ``mk(op, w, args, imm)`` with, or None.  Operands are simplified
+        already; a rewritten form is built through ``mk`` again.  ``w`` is
+        the operand width of a comparison (its result is one bit).  A rule
+        that answers with an operand needs it no wider than the node."""
+        C = I.CONST
+        m = (1 << w) - 1
+        hit, const = self._hit, self.const
+        if op == I.ITE:
+            c, a, b = args
+            if c.op == C:
+                return hit("ITE:const", a if c.imm & 1 else b)
+            if a is b:
+                return hit("ITE:same", a)
+            return None
+        for x in args:
+            if x.op != C:
+                break
+        else:
+            v = const_eval(op, w, [x.imm for x in args], imm)
+            return hit("const:" + I.OPNAME[op], const(v, 1 if op in _PRED_OPS else w))
+        if len(args) != 2 or op in (I.CONCAT,):
+            return None
+        a, b = args
+        if a is b:
+            if op in (I.SUB, I.XOR):
+                return hit("same:" + I.OPNAME[op], const(0, w))
+            if op in (I.AND, I.OR) and a.width <= w:
+                return hit("same:" + I.OPNAME[op], a)
+            if op in (I.EQ, I.ULE, I.SLE):
+                return hit("same:" + I.OPNAME[op], const(1, 1))
+            if op in (I.ULT, I.SLT):
+                return hit("same:" + I.OPNAME[op], const(0, 1))
+            if op in (I.UREM, I.SREM, I.SMOD):
+                return hit("same:" + I.OPNAME[op], const(0, w))
+            if op in (I.UDIV, I.SDIV):
+                return hit("same:" + I.OPNAME[op], self._div_guard(a, w, 1))
+            return None
+        if op in (I.ADD, I.MUL, I.AND, I.OR, I.XOR, I.UMULNO):       # commutative
+            if a.op == C:
+                x, c = b, a.imm & m
+            elif b.op == C:
+                x, c = a, b.imm & m
+            else:
+                return None
+            fits = x.width <= w
+            if op == I.ADD:
+                if c == 0 and fits:
+                    return hit("ADD:0", x)
+            elif op == I.MUL:
+                if c == 0:
+                    return hit("MUL:0", const(0, w))
+                if c == 1 and fits:
+                    return hit("MUL:1", x)
+                if c & (c - 1) == 0 and fits:
+                    return hit("MUL:pow2", self._shl_form(x, c.bit_length() - 1, w))
+                if c & (c + 1) == 0 and fits:
+                    return hit("MUL:pow2m1",
+                               self.mk(I.SUB, w, (self._shl_form(x, c.bit_length(), w), x)))
+            elif op == I.AND:
+                if c == 0:
+                    return hit("AND:0", const(0, w))
+                if c == m and fits:
+                    return hit("AND:ones", x)
+            elif op == I.OR:
+                if c == 0 and fits:
+                    return hit("OR:0", x)
+                if c == m:
+                    return hit("OR:ones", const(m, w))
+            elif op == I.XOR:
+                if c == 0 and fits:
+                    return hit("XOR:0", x)
+            elif c <= 1:
+                return hit("UMULNO:01", const(1, 1))
+            return None
+        if b.op == C:
+            c = b.imm & m
+            fits = a.width <= w
+            if c == 0:
+                if op in (I.SUB, I.UREM, I.SREM, I.SHL, I.LSHR, I.ASHR) and fits:
+                    return hit(I.OPNAME[op] + ":x,0", a)
+                if op == I.UDIV:
+                    return hit("UDIV:x,0", const(m, w))
+                if op == I.ULT:
+                    return hit("ULT:x,0", const(0, 1))
+            if c == 1:
+                if op in (I.UDIV, I.SDIV) and fits:
+                    return hit(I.OPNAME[op] + ":x,1", a)
+                if op in (I.UREM, I.SREM):
+                    return hit(I.OPNAME[op] + ":x,1", const(0, w))
+            if c == m and op == I.ULE:
+                return hit("ULE:x,ones", const(1, 1))
+        elif a.op == C and a.imm & m == 0:
+            if op in (I.UDIV, I.SDIV):
+                return hit(I.OPNAME[op] + ":0,x", self._div_guard(b, w, 0))
+            if op in (I.UREM, I.SREM, I.SHL, I.LSHR, I.ASHR):
+                return hit(I.OPNAME[op] + ":0,x", const(0, w))
+            if op == I.ULE:
+                return hit("ULE:0,x", const(1, 1))
+        return None
 
     # -- hash-consed constructors ------------------------------------------
     def mk(self, op: int, width: int, args=(), imm=None) -> LNode:
+        if self.simplify and args and op in _SIMPLIFY_OPS:
+            n = self._rule(op, width, args, imm)
+            if n is not None:
+                self.folded += 1
+                return n
         if op == I.CONCAT and width == I.MAX_WIDTH and args[0].op == I.EXTRACT and \
                 args[0].imm == 0 and args[0].args[0].width == I.MAX_WIDTH:
             # concat(y[h:0], e) at 256 bits = (y << |e|) | e mod 2^256: the
@@ -1129,6 +1384,37 @@ def lw_tables(constraints, probes) -> set:
     return out
 
 
+def _reach(stack: List[LNode]) -> Tuple[set, int, int]:
+    """(CONST values, heavy LNodes, LNodes) under the nodes of ``stack``."""
+    seen, values, heavy = set(), set(), 0
+    while stack:
+        n = stack.pop()
+        if n.id in seen:
+            continue
+        seen.add(n.id)
+        if n.op == I.CONST:
+            values.add(n.imm & ((1 << 256) - 1))
+        heavy += n.op in _HEAVY
+        stack.extend(n.args)
+    return values, heavy, len(seen)
+
+
+def _plain_lowering(constraints, probes, table_sizes, default_entries, table_ckeys):
+    """(CONST values the sinks reach, leaf table, heavy LNodes, LNodes
+    reached) of the eval-form lowering without the simplifying constructor:
+    what the candidate generator is keyed to, and what ``SIMPLIFY_MIN_HEAVY``
+    is measured on.  No schedule, no allocation."""
+    lw = _Lowerer(table_sizes or {}, default_entries)
+    lw.table_ckeys = table_ckeys
+    stack = [lw.lower(c)[0] for c in constraints]
+    for p in probes:
+        stack.extend(lw.lower(p))
+    if not stack:
+        stack.append(lw.const(1, 1))
+    values, heavy, reach = _reach(stack)
+    return values, lw.leaves, heavy, reach
+
+
 # Which compiler compile_constraints runs: "native" (include/mythcc.h, the
 # C++ port of this module and solve.py, identical output) or "py" (this
 # module; the specification the native one is tested against).
@@ -1215,7 +1501,8 @@ def compile_constraints_py(constraints: Sequence[Node], probes: Sequence[Node] =
                            default_entries: int = 2, nreg: int = I.NREG,
                            extra_consts: Sequence[int] = (), leaf_pools: bool = False,
                            const_keys: bool = False, solve: bool = False,
-                           search_hints: bool = False, abi_presets: bool = False) -> Program:
+                           search_hints: bool = False, abi_presets: bool = False,
+                           simplify: Optional[bool] = None) -> Program:
     """Compile Bool constraint nodes (their conjunction is the root bit) and
     optional probe nodes (256-bit values written per assignment).  ``nreg``
     is the library's register-file size (``Engine.nreg``); ``extra_consts``
@@ -1235,8 +1522,16 @@ def compile_constraints_py(constraints: Sequence[Node], probes: Sequence[Node] =
     caller-supplied assignments.  ``search_hints`` adds the constraints'
     numerals as candidates (:func:`harvest_hints`); ``abi_presets`` pins the
     ABI offset words of calldata read at symbolic offsets (``abi.plan``) and
-    compiles the query under them (``Plan.view``, ``Program.presets``)."""
+    compiles the query under them (``Plan.view``, ``Program.presets``).
+    ``simplify`` (default ``SIMPLIFY``; eval form only) lowers through the
+    simplifying constructor (``_Lowerer._rule``): the leaf table and
+    ``const_values`` stay those of the plain lowering, the constants the
+    rules create get table rows behind everything else
+    (``Program.appended``)."""
     constraints, probes = list(constraints), list(probes)
+    simplify = (SIMPLIFY if simplify is None else simplify) and not solve
+    given = (constraints, probes, table_sizes, default_entries, nreg, extra_consts, leaf_pools,
+             const_keys, solve, search_hints, abi_presets)
     if search_hints:
         extra_consts = list(extra_consts) + harvest_hints(constraints)
     plan = None
@@ -1247,6 +1542,7 @@ def compile_constraints_py(constraints: Sequence[Node], probes: Sequence[Node] =
             constraints, probes = plan.view(constraints), plan.view(probes)
     lw = _Lowerer(table_sizes or {}, default_entries)
     lw.solve = solve
+    lw.simplify = simplify
     if const_keys or solve:
         sym_counts: Dict[str, int] = {}
         ck = scan_const_keys(list(constraints) + list(probes), sym_counts=sym_counts,
@@ -1275,9 +1571,17 @@ def compile_constraints_py(constraints: Sequence[Node], probes: Sequence[Node] =
         if solver.dead:                       # a false root: that root alone
             births, probes = births[:1], ()
     sinks: List[LNode] = []
+    rooted = set()
     for r, b in zip(roots, births):
         lw.birth = b
-        sinks.append(lw.mk(I.ROOT, 1, (r,), None))
+        if simplify and r.id in rooted:
+            # roots that fold to one node (a constant): each constraint
+            # keeps a ROOT record of its own
+            lw.nid += 1
+            sinks.append(LNode(I.ROOT, 1, (r,), None, lw.nid, max(b, r.birth)))
+        else:
+            sinks.append(lw.mk(I.ROOT, 1, (r,), None))
+        rooted.add(r.id)
     probe_chunks = 0
     for p in probes:
         if p.is_array():
@@ -1316,9 +1620,32 @@ def compile_constraints_py(constraints: Sequence[Node], probes: Sequence[Node] =
             n.imm = n.width
             n.width = 1
     order, fused = _fuse_roots(_schedule(sinks))
-    const_values = sorted({n.imm & ((1 << 256) - 1) for n in order if n.op == I.CONST} |
-                          {v & ((1 << 256) - 1) for v in extra_consts})
+    # a leaf whose readers all folded away is still generated (last, into a
+    # slot that stays free): the leaves a launch writes back are the whole
+    # candidate (witness regeneration, ``want_leaves``)
+    unread: List[LNode] = []
+    if lw.folded:
+        have = {n.imm for n in order if n.op == I.LEAF}
+        unread = [lw.mk(I.LEAF, l.width, (), i) for i, l in enumerate(lw.leaves) if i not in have]
+        order = order + unread
+    M256 = (1 << 256) - 1
+    used_consts = {n.imm & M256 for n in order if n.op == I.CONST}
+    pool_consts = used_consts
+    if lw.folded:
+        # the candidate stream must not move: the generator's pool is the
+        # constant set of the plain lowering, and a leaf keeps its index;
+        # programs without heavy arithmetic keep the plain lowering
+        pool_consts, plain_leaves, heavy, reach = _plain_lowering(
+            constraints, probes, table_sizes, default_entries, lw.table_ckeys)
+        if plain_leaves != lw.leaves or heavy < SIMPLIFY_MIN_HEAVY * reach:
+            return compile_constraints_py(*given, simplify=False)
+    const_values = sorted(pool_consts | {v & M256 for v in extra_consts})
     const_index = {v: i for i, v in enumerate(const_values)}
+    pools = _leaf_pools(order, lw.leaves) if leaf_pools else []
+    # constants only the rules created: rows behind the pools, never drawn
+    appended = sorted(used_consts - set(const_values))
+    first = len(const_values) + sum(len(p) for p in pools)
+    const_index.update({v: first + i for i, v in enumerate(appended)})
     ins, n_lds, n_spill, n_reload = _allocate(order, const_index, fused, nreg)
     if not solve and not leaf_pools and SCHEDULE_CHOICE and \
             n_lds - LDS_TIER >= SCHEDULE_MIN_SCRATCH:
@@ -1329,6 +1656,7 @@ def compile_constraints_py(constraints: Sequence[Node], probes: Sequence[Node] =
         # Search programs keep source order: their compile latency is in
         # front of every query, and their leaf pools follow that order.
         order2, fused2 = _fuse_roots(_schedule_demand(sinks))
+        order2 = order2 + unread
         try:
             alt = _allocate(order2, const_index, fused2, nreg)
         except Unsupported:
@@ -1345,19 +1673,21 @@ def compile_constraints_py(constraints: Sequence[Node], probes: Sequence[Node] =
     table = list(const_values)
     pool_ranges: List[Tuple[int, int]] = []
     if leaf_pools:
-        for li, p in enumerate(_leaf_pools(order, lw.leaves)):
+        for li, p in enumerate(pools):
             if p:
                 pool_ranges.append((len(table), len(p)))
                 table.extend(p)
             else:
                 pool_ranges.append((0, len(const_values)))
+    table.extend(appended)
     consts = np.frombuffer(b"".join(v.to_bytes(32, "little") for v in table),
                            dtype="<u4").reshape(-1, 8).astype(np.uint32)
+    const_values = ConstValues(const_values, table[len(const_values):])
     hist: Dict[str, int] = {}
     for n in order:
         hist[I.OPNAME[n.op]] = hist.get(I.OPNAME[n.op], 0) + 1
     stats = {"lnodes": len(order), "n_ins": len(ins), "spills": n_spill, "reloads": n_reload,
-             "hist": hist}
+             "hist": hist, "folded": lw.folded}
     ckeys = {k: v for k, v in lw.table_ckeys.items() if k in lw.table_kinds}
     tsizes = dict(lw.table_sizes)
     for name in lw.solve_tables & set(lw.table_kinds):
@@ -1367,6 +1697,7 @@ def compile_constraints_py(constraints: Sequence[Node], probes: Sequence[Node] =
                    len(constraints), tsizes, lw.table_kinds, ckeys, stats, pool_ranges,
                    derived, entry_keys, n_user_probes)
     prog.nreg = nreg
+    prog.appended = len(appended)
     if plan is not None:
         prog.presets = plan
     return prog

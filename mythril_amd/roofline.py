@@ -38,6 +38,18 @@ reported frac 1.054 under the generic weights):
         compares, selects and index adds weigh 0 unless something other than
         a calldata word reads them.
 
+Round 15: the eval-form lowering simplifies (``ir._Lowerer._rule``: constant
+folding and operand identities), so the work it removes is priced at what
+is left of it (``dag_work``; ``node_weight`` keeps the generic values, and
+MYTHRIL_GPU_SIMPLIFY=0 prices as before):
+
+    a node the pass turns into a constant or into one of its operands    0
+    x / x and 0 / x (UDIV, SDIV): ITE(x = 0, ones, 1 or 0)              16
+    MUL by a constant 2^k (the constant shift's CONCAT of an EXTRACT)    8
+    MUL by a constant 2^m - 1 (that shift and a SUB)                    16
+
+The node COUNT does not change, as with the calldata word.
+
 Peak: the SIMD's int32 VALU issue capacity, MEASURED per SIMD
 (``tools/valu_rate.hip``, ``profiles/r02/valu_rate.log``: every wave stamps
 s_memtime and its HW_ID, and each SIMD's instructions are divided by the span
@@ -170,13 +182,91 @@ def calldata_word(n: Node):
     return arr.params[0], inner
 
 
+def _lowered(order, roots, ts, simplify):
+    from . import ir
+    lw = ir._Lowerer(ts, 2)
+    lw.simplify = simplify
+    for r in roots:
+        lw.lower(r)
+    return lw
+
+
+def simplified_weights(order, roots, ts: Dict[str, int]) -> Dict[int, float]:
+    """Weight of every source node the simplifying lowering makes cheaper
+    than ``node_weight`` prices it (module docstring), by node id: what the
+    node lowers to with the rules against without them, so a node that was
+    its operand already (``zero_extend``, a shift by 0) keeps its price."""
+    from . import ir
+    from . import irdefs as I
+    if not ir.SIMPLIFY:
+        return {}
+    try:
+        on, off = _lowered(order, roots, ts, True), _lowered(order, roots, ts, False)
+    except ir.Unsupported:
+        return {}
+    if not on.folded:
+        return {}
+    _, heavy, reach = ir._reach([off.memo[r.id][0] for r in roots])
+    if heavy < ir.SIMPLIFY_MIN_HEAVY * reach:           # the compilers' gate: plain program
+        return {}
+
+    def kind(lw, n):
+        """'gone' (a constant or an operand), or the LNode op."""
+        ch = lw.memo.get(n.id)
+        if ch is None or len(ch) != 1:
+            return None
+        x = ch[0]
+        if x.op == I.CONST:
+            return "gone"
+        for a in n.args:
+            ca = lw.memo.get(a.id)
+            if ca is not None and len(ca) == 1 and ca[0] is x:
+                return "gone"
+        return x.op
+
+    out: Dict[int, float] = {}
+    for n in order:
+        if n.op in _LEAF or n.op in ("select", "apply", "store") or n.width > 256:
+            continue
+        k_on, k_off = kind(on, n), kind(off, n)
+        if k_on is None or k_off is None or k_off == "gone":
+            continue
+        w = n.args[0].width if n.args and n.args[0].is_bv() else n.width
+        if k_on == "gone":
+            out[n.id] = 0.0
+        elif n.op in ("bvudiv", "bvsdiv") and k_on == I.ITE and k_off in (I.UDIV, I.SDIV):
+            out[n.id] = 16.0 * _scale(w)
+        elif n.op == "bvmul":
+            # the chain ir._Lowerer._fold builds, step by step
+            acc, total = on.memo[n.args[0].id][0], 0.0
+            for a in n.args[1:]:
+                b = on.memo[a.id][0]
+                new = on.mk(I.MUL, n.width, (acc, b))
+                if new.op == I.MUL:
+                    total += 192.0 * _scale(w)
+                elif new is acc or new is b or new.op == I.CONST:
+                    pass
+                elif new.op == I.CONCAT:
+                    total += 8.0 * _scale(w)
+                else:                                  # the shift and a SUB
+                    total += 16.0 * _scale(w)
+                acc = new
+            if total < node_weight(n, ts):
+                out[n.id] = total
+    return out
+
+
 def dag_work(roots: Iterable[Node], table_sizes: Dict[str, int] = None) -> Tuple[int, float]:
     """(node count, int32-op weight) of the DAG reachable from ``roots``.
     The node count is the metric's unit and does not depend on how a node is
     priced; the weight prices fused calldata words as one lookup each (module
-    docstring) and their byte terms at 0 unless a non-word node reads them."""
+    docstring) and their byte terms at 0 unless a non-word node reads them,
+    and what the simplifying lowering removes at what is left of it
+    (``simplified_weights``)."""
     ts = table_sizes or {}
-    order = topo_order(list(roots))
+    roots = list(roots)
+    order = topo_order(roots)
+    cheaper = simplified_weights(order, roots, dict(ts))
     users: Dict[int, list] = {}
     for n in order:
         for a in n.args:
@@ -204,5 +294,5 @@ def dag_work(roots: Iterable[Node], table_sizes: Dict[str, int] = None) -> Tuple
         if n.id in words:
             weight += words[n.id]
         elif n.id not in absorbed:
-            weight += node_weight(n, ts)
+            weight += cheaper[n.id] if n.id in cheaper else node_weight(n, ts)
     return nodes, weight
