@@ -658,6 +658,73 @@ int mg_walk_batch_plan_host(const mg_walk_shape* shapes, uint32_t n_jobs, uint32
  * mg_walk_sum accepts (what it checks before it reads a table), else 0. */
 int mg_walk_batch_shape_ok_host(const mg_walk_shape* shape);
 
+/* Witness carry (csrc/mg_carry.h, mg_carry.hip): remembered
+ * witnesses evaluated on the programs of the groups that extend them.  It
+ * serves the path queries of Constraints.is_possible (reference
+ * laser/ethereum/state/constraints.py:26-45): at a JUMPI the parent's model
+ * satisfies one of the two children, and one evaluation confirms which.
+ * A job names an eval-form program (loaded with its leaf generators), pin rows
+ * and a pin mask.  Lane i of job j evaluates the candidate whose pinned leaves
+ * (bit l % 32 of pin_mask[l / 32]) are the pin rows and whose free leaf l is
+ * generator v9's value (above mg_leafgen) for (gen->seed, the program's
+ * prog_seed, l, gen->first_index + i), the leaf's mg_leafgen and the program's
+ * constant pool; every value is masked to the leaf's width, upper limbs zero.
+ * first[j]: the lowest lane of 0 .. lanes - 1 on which every root of job j
+ * holds, or -1; leaves[j]: that lane's leaf rows, zero where there is none and
+ * past the program's leaves.  fill_out (may be NULL): the jobs' leaf regions
+ * as the fill kernel wrote them, [n_jobs][leaf_stride_w] words with job j's
+ * [n_leaves][8][lanes] at the front (mg_carry_plan_host gives the stride).
+ * One call is a fixed sequence whatever n_jobs: one upload (descriptors, jobs,
+ * masks, rows, generator tables), the fill launch, one eval-mode interpreter
+ * launch over the job axis, the gather launch, one download.
+ * mg_last_kernel_ms covers the three launches.
+ * Refused with MG_E_ARG before any upload or launch, the message beginning
+ * "carry_batch:": a null pointer (fill_out excepted); n_jobs outside
+ * 1..MG_CARRY_MAX_JOBS; lanes outside 1..2^20; max_leaves above 2^20; a
+ * program of another context; a program with more leaves than max_leaves; a
+ * device buffer above 1 GiB (the message gives the bytes needed). */
+typedef struct mg_carry_job {
+    const mg_prog* prog;        /* eval-form program, loaded with its leaf generators */
+    const uint32_t* pin_rows;   /* [n_leaves][8]; rows of free leaves ignored          */
+    const uint32_t* pin_mask;   /* [(n_leaves + 31) / 32], bit l: leaf l is pinned     */
+} mg_carry_job;
+/* as the census batch: the grid's job dimension allows 65535, callers with
+ * more jobs run several batches (mythril_amd/engine.py carry_batch does) */
+#define MG_CARRY_MAX_JOBS 256u
+#define MG_CARRY_MAX_LEAVES (1u << 20)
+int mg_carry_batch(mg_ctx* ctx, const mg_carry_job* jobs, uint32_t n_jobs, const mg_gen* gen,
+                   uint32_t lanes, int64_t* first /*[n_jobs], -1: none*/,
+                   uint32_t* leaves /*[n_jobs][max_leaves][8]*/, uint32_t max_leaves,
+                   uint32_t* fill_out /*NULL, or every job's leaf region copied back*/);
+/* Host-only (no GPU): lanes lane0 .. lane0 + n_lanes - 1 of one job as the fill
+ * kernel writes them, from the same lane function: out [n_leaves][8][n_lanes].
+ * classes ([n_leaves][n_lanes] or NULL): the generator branch a free leaf took
+ * (0 r0, 1 boundary, 2 pool, 3 uniform), 0xFFFFFFFF for a pinned leaf.
+ * MG_E_ARG for a null pointer (consts may be NULL when n_consts is 0), a width
+ * outside 1..256, a pool outside the constants, lanes outside 1..2^20 and a
+ * lane range outside lanes. */
+int mg_carry_fill_host(const mg_leafgen* leaves, uint32_t n_leaves, const uint32_t* consts,
+                       uint32_t n_consts, uint64_t prog_seed,
+                       const uint32_t* pin_rows /*[n_leaves][8]*/,
+                       const uint32_t* pin_mask /*[(n_leaves + 31) / 32]*/, uint64_t seed,
+                       uint64_t first_index, uint32_t lanes, uint32_t lane0, uint32_t n_lanes,
+                       uint32_t* out, uint32_t* classes);
+/* Host-only (no GPU): the plan of the device buffer mg_carry_batch uses
+ * (csrc/mg_carry.h says what lies where).  out_offsets: [MG_CARRY_SHARED +
+ * n_jobs * MG_CARRY_JOB_REGIONS] byte offsets: descriptors, job records, first
+ * words, the output block; then job by job its mask, rows, generators and leaf
+ * region.  In address order — descriptors, records, first words, every job's
+ * mask, rows and generators, the output block, all leaf regions — every region
+ * is 256-byte aligned and ends where the next begins, the last at *out_bytes.
+ * *out_leaf_stride_w: words between two jobs' leaf regions, the batch's
+ * largest n_leaves x 8 x lanes rounded up to 256 bytes.  MG_E_ARG for a null
+ * pointer, n_jobs or lanes out of range and sizes beyond 64 bits. */
+#define MG_CARRY_SHARED 4
+#define MG_CARRY_JOB_REGIONS 4
+int mg_carry_plan_host(const uint32_t* n_leaves /*[n_jobs]*/, uint32_t n_jobs, uint32_t lanes,
+                       uint32_t max_leaves, uint64_t* out_offsets, uint64_t* out_bytes,
+                       uint64_t* out_leaf_stride_w);
+
 /* Corpus batches: many programs, one launch.  Device-pointer API for
  * resident benchmarking; stream is a hipStream_t (NULL = the context's own
  * stream, which the synchronous calls also use).

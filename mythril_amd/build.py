@@ -14,7 +14,7 @@ LIB = os.path.join(LIBDIR, "libmythgpu.so")
 JIT_STUB = os.path.join(LIBDIR, "mg_jit_stub.s")
 SOURCES = ["mg_interp_asm.hip", "mg_keccak.hip", "mg_census.hip", "mg_census_batch.hip",
            "mg_repair.hip", "mg_walk.hip", "mg_walk_tree.hip", "mg_walk_aim.hip", "mg_walk_sum.hip",
-           "mg_walk_batch.hip", "mg_host.cpp", "mg_api.cpp"]
+           "mg_walk_batch.hip", "mg_carry.hip", "mg_host.cpp", "mg_api.cpp"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("MYTHGPU_ARCH", "gfx950")
 
@@ -28,6 +28,7 @@ def _deps():
               os.path.join(CSRC, "mg_walk_aim.h"), os.path.join(CSRC, "mg_walk_bound.h"),
               os.path.join(CSRC, "mg_walk_uf.h"), os.path.join(CSRC, "mg_walk_sum.h"),
               os.path.join(CSRC, "mg_walk_batch.h"), os.path.join(CSRC, "mg_walk_round.h"),
+              os.path.join(CSRC, "mg_carry.h"),
               os.path.join(CSRC, "mg_jit_stub.hip"),
               os.path.join(ROOT, "include", "mythgpu.h"),
               os.path.join(ROOT, "include", "mythgpu_ir.h"),

@@ -1,0 +1,250 @@
+"""Witness carry: a group's model reused on the groups that
+extend it.
+
+LASER builds its queries along a path: it appends one JUMPI condition, asks
+``is_possible``, appends the next.  The group-miss memo of ``model.py`` answers
+a group that repeats or extends a MISSED group; this module does the same for
+hits.  A group that found a witness is remembered (:class:`HitMemo`); an exact
+repeat is answered from the memo, and a group that properly extends remembered
+groups is evaluated ONCE under their witnesses: the extended group is compiled
+in eval form, the leaves the carried assignment interprets are pinned to its
+values (:func:`pins`), the leaves of fresh symbols come from the device
+generator, and ``Engine.carry_batch`` runs every such job of a query — or of a
+whole ``batch_is_possible`` call — in one launch sequence.
+
+The carry never concludes UNSAT: a group it misses is searched as before, and a
+carried witness is accepted by the same rule as any other (``model._accept``).
+Opt-in: ``MYTHRIL_GPU_CARRY=1``.
+"""
+
+from __future__ import annotations
+
+from collections import OrderedDict
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+
+from .assign import Assignment, leaf_values, unpack
+from .ir import Program, compile_constraints
+
+# candidates of a job with at least one free leaf (MYTHRIL_GPU_CARRY_LANES);
+# a job with no free leaf runs one.  256 is one block of the interpreter and
+# four groups of the generator's classes; DESIGN.md §7 records how the hit
+# rate on extensions moves with it
+CARRY_LANES = 256
+DEFAULT_ENTRIES = 2            # compile_constraints' default table size
+# the largest carried table an extension is evaluated with
+# (MYTHRIL_GPU_CARRY_MAX_ENTRIES).  The eval form lowers a read of a table of n
+# entries to n compare-and-select steps, so its size and compile time grow with
+# every read times n; a witness that went through the ABI presets holds
+# calldata tables of 68 constant-keyed entries, at which the eval form of a path
+# group measured 2400 - 3700 records and 12 - 24 ms of compile, several times
+# the solve-mode compile and search the carry is there to save (DESIGN.md §7
+# round 16).  16 is eight times the default: what a few transactions' storage
+# and balance tables reach, below any calldata table that carries presets.
+MAX_ENTRIES = 16
+EVAL_CACHE_SIZE = 2048
+
+
+class HitMemo:
+    """Group key (``model._group_key``: the frozenset of a group's node ids)
+    -> the Assignment that satisfied the group.  Bounded (``size`` entries,
+    oldest dropped) and indexed by each key's minimum id, as the group-miss
+    memo is: a subset of a key that contains the key's minimum has it as its
+    own minimum, and one that does not is found under the id that is.  An
+    entry never expires: node ids are hash-consed and never reused, so a
+    group's witness is a function of its key."""
+
+    def __init__(self, size: int):
+        self.size = size
+        self.hits: Dict[frozenset, Assignment] = {}
+        self.progs: Dict[frozenset, Program] = {}     # a program of the group (table sizes)
+        self.index: Dict[int, List[frozenset]] = {}
+        self.seq: Dict[frozenset, int] = {}
+        self._n = 0
+
+    def note(self, key: frozenset, asg: Assignment, prog: Optional[Program] = None) -> None:
+        if not key or asg is None:
+            return
+        if key not in self.hits:
+            while len(self.hits) >= max(1, self.size):
+                self._drop(next(iter(self.hits)))
+            self.index.setdefault(min(key), []).append(key)
+        self.hits[key] = asg
+        self._n += 1
+        self.seq[key] = self._n
+        if prog is not None:
+            self.progs[key] = prog
+
+    def _drop(self, old: frozenset) -> None:
+        del self.hits[old]
+        self.seq.pop(old, None)
+        self.progs.pop(old, None)
+        lst = self.index.get(min(old), [])
+        if old in lst:
+            lst.remove(old)
+        if not lst:
+            self.index.pop(min(old), None)
+
+    def clear(self) -> None:
+        self.hits.clear()
+        self.progs.clear()
+        self.index.clear()
+        self.seq.clear()
+
+    def subsets(self, key: frozenset) -> List[frozenset]:
+        """The remembered proper subsets of ``key``, largest first and newest
+        first among equals."""
+        out = []
+        for c in key:
+            for m in self.index.get(c, ()):
+                if len(m) < len(key) and m <= key:
+                    out.append(m)
+        out.sort(key=lambda m: (-len(m), -self.seq.get(m, 0)))
+        return out
+
+    def __len__(self):
+        return len(self.hits)
+
+
+def _names(a: Assignment) -> set:
+    return set(a.vars) | set(a.arrays) | set(a.funcs)
+
+
+def union(parts: Sequence[Assignment]) -> Tuple[Assignment, List[int]]:
+    """The pin set of an extension: the assignments of ``parts`` in order,
+    skipping any that interprets a name one taken before it interprets (two
+    remembered groups that share a symbol may disagree on it; each was a
+    witness only as a whole).  Returns the union and the indices taken."""
+    out, taken, seen = Assignment(), [], set()
+    for i, a in enumerate(parts):
+        names = _names(a)
+        if names & seen:
+            continue
+        seen |= names
+        out.vars.update(a.vars)
+        out.arrays.update(a.arrays)
+        out.funcs.update(a.funcs)
+        taken.append(i)
+    return out, taken
+
+
+def plan(key: frozenset, memo: HitMemo):
+    """What the memo offers a group, a pure function of (key, memo):
+    ``("exact", assignment)`` for a remembered key, ``("extend", assignment,
+    subset keys taken)`` when remembered proper subsets give a pin set that
+    interprets at least one name, else None."""
+    hit = memo.hits.get(key)
+    if hit is not None:
+        return ("exact", hit)
+    subs = memo.subsets(key)
+    if not subs:
+        return None
+    asg, taken = union([memo.hits[m] for m in subs])
+    if not _names(asg):
+        return None
+    return ("extend", asg, [subs[i] for i in taken])
+
+
+def table_sizes(asg: Assignment, default: int = DEFAULT_ENTRIES) -> Dict[str, int]:
+    """``table_sizes`` for the eval form of a group evaluated under ``asg``:
+    the maximum of the default and the carried tables' entry counts (as
+    ``Model.eval_node`` sizes its programs)."""
+    return {name: max(default, len(entries))
+            for name, (entries, _) in list(asg.arrays.items()) + list(asg.funcs.items())}
+
+
+_EVAL_CACHE: "OrderedDict[tuple, Program]" = OrderedDict()
+
+
+def clear() -> None:
+    _EVAL_CACHE.clear()
+
+
+def compile_eval(nodes, asg: Assignment) -> Program:
+    """The eval form of a group to be evaluated under ``asg``: EVERY constraint
+    of the group, so a carried hit rests on the same evidence as a search hit —
+    every root true on the device.  Cached by node ids and table sizes."""
+    sizes = table_sizes(asg)
+    key = (tuple(n.id for n in nodes), tuple(sorted(sizes.items())))
+    prog = _EVAL_CACHE.get(key)
+    if prog is not None:
+        _EVAL_CACHE.move_to_end(key)
+        return prog
+    prog = compile_constraints(nodes, solve=False, leaf_pools=True, table_sizes=sizes or None)
+    _EVAL_CACHE[key] = prog
+    if len(_EVAL_CACHE) > EVAL_CACHE_SIZE:
+        _EVAL_CACHE.popitem(last=False)
+    return prog
+
+
+def pinned(leaf, asg: Assignment) -> bool:
+    """A leaf is pinned iff the carried assignment interprets its source."""
+    if leaf.kind == "var":
+        return leaf.source in asg.vars
+    if leaf.kind == "aux":
+        return False
+    return leaf.source in asg.arrays or leaf.source in asg.funcs
+
+
+def pins(program: Program, asg: Assignment) -> Tuple[np.ndarray, np.ndarray]:
+    """``(mask, rows)`` of one carry job: bit l of ``mask`` ((n_leaves + 31) //
+    32 uint32 words) is set iff ``asg`` interprets leaf l's source — a var in
+    ``vars``, a table in ``arrays`` or ``funcs``; ``rows`` ((n_leaves, 8)
+    uint32) holds what ``assign.leaf_values`` gives for the pinned leaves, per
+    chunk and masked to the leaf's width, and zero for the free ones (leaves of
+    fresh symbols: a new transaction's calldata, call value, sender)."""
+    n = len(program.leaves)
+    mask = np.zeros((n + 31) // 32, dtype=np.uint32)
+    rows = np.zeros((n, 8), dtype=np.uint32)
+    vals = leaf_values(program, asg) if n else []
+    for l, (leaf, v) in enumerate(zip(program.leaves, vals)):
+        if not pinned(leaf, asg):
+            continue
+        mask[l >> 5] |= np.uint32(1 << (l & 31))
+        rows[l] = np.frombuffer(int(v).to_bytes(32, "little"), dtype="<u4")
+    return mask, rows
+
+
+def n_free(program: Program, mask: np.ndarray) -> int:
+    n = len(program.leaves)
+    return n - sum(bin(int(w)).count("1") for w in mask)
+
+
+def run(eng, items, seed: int, leafgen, lanes: Optional[int] = None, phase=None):
+    """One ``Engine.carry_batch`` call for ``items``, a list of ``(nodes,
+    assignment)``: per item ``(assignment, program, candidates)`` — the witness
+    of the group (None on a miss), its eval-form program and the candidates it
+    ran — or None where the group has no eval form (``Unsupported``).
+    ``leafgen(program)``: the generator parameters of the free leaves
+    (``model.search_leafgen``).  A batch none of whose jobs has a free leaf
+    runs one candidate; else ``lanes`` (default ``CARRY_LANES``), of which a
+    job without a free leaf counts one.  ``phase(name)``: a context manager
+    that accounts the compile, load and search steps (``model._Phase``)."""
+    import contextlib
+    from .ir import Unsupported
+    phase = phase or (lambda name: contextlib.nullcontext())
+    lanes = CARRY_LANES if lanes is None else lanes
+    jobs, progs, free, where = [], [], [], []
+    with phase("compile"):
+        for k, (nodes, asg) in enumerate(items):
+            try:
+                prog = compile_eval(nodes, asg)
+                mask, rows = pins(prog, asg)
+            except (Unsupported, ValueError):
+                continue
+            progs.append(prog)
+            free.append(n_free(prog, mask))
+            jobs.append((prog, rows, mask))
+            where.append(k)
+    out: List = [None] * len(items)
+    if not jobs:
+        return out
+    width = max(1, int(lanes)) if any(free) else 1
+    with phase("load"):
+        loaded = [(eng.load(p, leafgen(p), prog_seed=0), r, m) for p, r, m in jobs]
+    with phase("search"):
+        res = eng.carry_batch(loaded, seed, 0, width)
+        for k, prog, f, (first, leaves) in zip(where, progs, free, res):
+            out[k] = (unpack(prog, leaves) if first >= 0 else None, prog, width if f else 1)
+    return out

@@ -31,6 +31,7 @@
 #include "mg_walk_aim.h"
 #include "mg_walk_sum.h"
 #include "mg_walk_batch.h"
+#include "mg_carry.h"
 
 // the interpreter of each register layout (mg_interp_asm.hip, one
 // translation unit per layout; mg_find_layout lists them)
@@ -153,6 +154,15 @@ hipError_t mg_launch_walk_batch_round(const mg_walk_batch_job* d_jobs, const uin
 hipError_t mg_launch_walk_batch_pick(const mg_walk_batch_job* d_jobs, const uint32_t* d_frozen,
                                     uint32_t n_jobs, uint32_t r, uint32_t lanes, uint32_t walkers,
                                     uint32_t max_rounds, hipStream_t stream);
+
+// the two kernels around mg_carry_batch's interpreter launch (mg_carry.hip)
+hipError_t mg_launch_carry_fill(const mg_carry_dev_job* d_jobs, uint32_t n_jobs,
+                                uint32_t most_leaves, uint64_t seed, uint64_t first_index,
+                                uint32_t lanes, hipStream_t stream);
+hipError_t mg_launch_carry_gather(const mg_carry_dev_job* d_jobs, uint32_t n_jobs,
+                                  const unsigned long long* d_first, uint32_t lanes,
+                                  uint32_t max_leaves, long long* d_out_first,
+                                  uint32_t* d_out_leaves, hipStream_t stream);
 
 struct mg_ctx {
     int device = 0;
@@ -1893,6 +1903,145 @@ int mg_walk_batch_plan_host(const mg_walk_shape* shapes, uint32_t n_jobs, uint32
 
 int mg_walk_batch_shape_ok_host(const mg_walk_shape* shape) {
     return shape && mg_walk_batch_shape_ok(*shape) ? 1 : 0;
+}
+
+// Witness carry (include/mythgpu.h mg_carry_batch, DESIGN.md §3.18;
+// csrc/mg_carry.h, mg_carry.hip): fill, one eval-mode launch over the job
+// axis, gather; one upload before and one download after.
+int mg_carry_batch(mg_ctx* ctx, const mg_carry_job* jobs, uint32_t n_jobs, const mg_gen* gen,
+                   uint32_t lanes, int64_t* first, uint32_t* leaves, uint32_t max_leaves,
+                   uint32_t* fill_out) {
+    if (!ctx) return MG_E_ARG;
+    if (!jobs || !gen || !first || !leaves)
+        return fail(ctx, MG_E_ARG, "carry_batch: null argument");
+    if (n_jobs < 1 || n_jobs > MG_CARRY_MAX_JOBS)
+        return fail(ctx, MG_E_ARG, "carry_batch: %u jobs outside 1..%u", n_jobs,
+                    MG_CARRY_MAX_JOBS);
+    if (lanes < 1 || lanes > MG_REPAIR_MAX_LANES)
+        return fail(ctx, MG_E_ARG, "carry_batch: %u lanes outside 1..%u", lanes,
+                    MG_REPAIR_MAX_LANES);
+    if (max_leaves > MG_CARRY_MAX_LEAVES)
+        return fail(ctx, MG_E_ARG, "carry_batch: max_leaves %u above %u", max_leaves,
+                    MG_CARRY_MAX_LEAVES);
+    std::vector<uint32_t> n_leaves(n_jobs);
+    uint32_t most = 0, max_lds = 0;
+    for (uint32_t g = 0; g < n_jobs; ++g) {
+        const mg_carry_job& j = jobs[g];
+        if (!j.prog) return fail(ctx, MG_E_ARG, "carry_batch: job %u: null program", g);
+        if (j.prog->ctx != ctx)
+            return fail(ctx, MG_E_ARG, "carry_batch: job %u: a program of another context", g);
+        if (j.prog->n_leaves > max_leaves)
+            return fail(ctx, MG_E_ARG, "carry_batch: job %u: %u leaves above max_leaves %u", g,
+                        j.prog->n_leaves, max_leaves);
+        if (j.prog->n_leaves && (!j.pin_rows || !j.pin_mask))
+            return fail(ctx, MG_E_ARG, "carry_batch: job %u: null pin rows or pin mask", g);
+        if (j.prog->leafgen.size() != j.prog->n_leaves ||
+            !mg_carry_gen_ok(j.prog->leafgen.data(), j.prog->n_leaves, j.prog->n_consts))
+            return fail(ctx, MG_E_ARG, "carry_batch: job %u: the program's leaf generators are "
+                        "not loaded", g);
+        n_leaves[g] = j.prog->n_leaves;
+        most = n_leaves[g] > most ? n_leaves[g] : most;
+        max_lds = j.prog->n_lds > max_lds ? j.prog->n_lds : max_lds;
+    }
+    std::vector<uint64_t> off(MG_CY_SHARED + (size_t)n_jobs * MG_CY_JOB_REGIONS);
+    uint64_t bytes = 0, leaf_w = 0;
+    if (!mg_carry_plan(n_leaves.data(), n_jobs, lanes, max_leaves, off.data(), &bytes, &leaf_w))
+        return fail(ctx, MG_E_ARG, "carry_batch: the batch's buffer exceeds 64 bits");
+    if (bytes > MG_WALK_BATCH_DEFAULT_BYTES)
+        return fail(ctx, MG_E_ARG, "carry_batch: %llu bytes needed for %u jobs at %u lanes, at "
+                    "most %llu; pass fewer jobs or lanes", (unsigned long long)bytes, n_jobs,
+                    lanes, (unsigned long long)MG_WALK_BATCH_DEFAULT_BYTES);
+    HIPCHECK(ctx, hipSetDevice(ctx->device));
+    void* ws;
+    int rc = workspace(ctx, (size_t)bytes + 256, &ws);
+    if (rc) return rc;
+    uint8_t* w = (uint8_t*)ws;
+    // the host image of everything uploaded, at the offsets of the plan
+    const size_t up_b = (size_t)off[MG_CY_OUT];
+    std::vector<uint8_t> img(up_b, 0);
+    mg_pdesc* h_descs = (mg_pdesc*)(img.data() + off[MG_CY_DESCS]);
+    mg_carry_dev_job* h_jobs = (mg_carry_dev_job*)(img.data() + off[MG_CY_JOBS]);
+    memset(img.data() + off[MG_CY_FIRST], 0xFF, (size_t)n_jobs * 8);
+    for (uint32_t g = 0; g < n_jobs; ++g) {
+        const mg_carry_job& j = jobs[g];
+        const uint32_t n = n_leaves[g];
+        auto at = [&](uint32_t k) { return off[MG_CY_OFF(g, k)]; };
+        if (n) {
+            memcpy(img.data() + at(MG_CY_MASK), j.pin_mask, (size_t)((n + 31) / 32) * 4);
+            memcpy(img.data() + at(MG_CY_ROWS), j.pin_rows, (size_t)n * 32);
+            memcpy(img.data() + at(MG_CY_GEN), j.prog->leafgen.data(), (size_t)n * sizeof(mg_leafgen));
+        }
+        h_descs[g] = j.prog->h_desc;
+        mg_carry_dev_job& d = h_jobs[g];
+        d.mask = (const uint32_t*)(w + at(MG_CY_MASK));
+        d.rows = (const uint32_t*)(w + at(MG_CY_ROWS));
+        d.gen = (const mg_leafgen*)(w + at(MG_CY_GEN));
+        d.consts = j.prog->h_desc.consts;              // the first n_consts entries: as loaded
+        d.leaves = (uint32_t*)(w + at(MG_CY_LEAVES));
+        d.prog_seed = j.prog->h_desc.prog_seed;
+        d.n_leaves = n;
+        d.pad = 0;
+    }
+    const mg_pdesc* d_descs = (const mg_pdesc*)(w + off[MG_CY_DESCS]);
+    const mg_carry_dev_job* d_jobs = (const mg_carry_dev_job*)(w + off[MG_CY_JOBS]);
+    unsigned long long* d_first = (unsigned long long*)(w + off[MG_CY_FIRST]);
+    long long* d_out_first = (long long*)(w + off[MG_CY_OUT]);
+    uint32_t* d_out_leaves = (uint32_t*)(w + off[MG_CY_OUT] + (size_t)n_jobs * 8);
+    HIPCHECK(ctx, hipMemcpyAsync(w, img.data(), up_b, hipMemcpyHostToDevice, ctx->stream));
+    mg_run run = empty_run();
+    run.leaves = (const uint32_t*)(w + off[MG_CY_OFF(0, MG_CY_LEAVES)]);
+    run.leaves_prog_words = leaf_w;
+    run.first_sat = d_first;                           // first_index 0: the lane itself
+    run.stride = lanes;
+    run.n_assign = lanes;
+    timing_begin(ctx);
+    HIPCHECK(ctx, mg_launch_carry_fill(d_jobs, n_jobs, most, gen->seed, gen->first_index, lanes,
+                                       ctx->stream));
+    HIPCHECK(ctx, launch(ctx, 0, d_descs, n_jobs, run, max_lds, ctx->stream));
+    HIPCHECK(ctx, mg_launch_carry_gather(d_jobs, n_jobs, d_first, lanes, max_leaves, d_out_first,
+                                         d_out_leaves, ctx->stream));
+    timing_end(ctx);
+    const size_t out_b = (size_t)n_jobs * 8 + (size_t)n_jobs * max_leaves * 32;
+    std::vector<uint8_t> h_out(out_b);
+    HIPCHECK(ctx, hipMemcpyAsync(h_out.data(), d_out_first, out_b, hipMemcpyDeviceToHost,
+                                 ctx->stream));
+    if (fill_out && leaf_w)
+        HIPCHECK(ctx, hipMemcpyAsync(fill_out, run.leaves, (size_t)n_jobs * leaf_w * 4,
+                                     hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
+    timing_read(ctx);
+    memcpy(first, h_out.data(), (size_t)n_jobs * 8);
+    memcpy(leaves, h_out.data() + (size_t)n_jobs * 8, (size_t)n_jobs * max_leaves * 32);
+    return MG_OK;
+}
+
+int mg_carry_fill_host(const mg_leafgen* leaves, uint32_t n_leaves, const uint32_t* consts,
+                       uint32_t n_consts, uint64_t prog_seed, const uint32_t* pin_rows,
+                       const uint32_t* pin_mask, uint64_t seed, uint64_t first_index,
+                       uint32_t lanes, uint32_t lane0, uint32_t n_lanes, uint32_t* out,
+                       uint32_t* classes) {
+    if (n_leaves == 0 || n_lanes == 0) return MG_OK;
+    if (!leaves || !pin_rows || !pin_mask || !out || (n_consts && !consts)) return MG_E_ARG;
+    if (lanes < 1 || lanes > MG_REPAIR_MAX_LANES || lane0 >= lanes || n_lanes > lanes - lane0)
+        return MG_E_ARG;
+    if (!mg_carry_gen_ok(leaves, n_leaves, n_consts)) return MG_E_ARG;
+    for (uint32_t l = 0; l < n_leaves; ++l)
+        for (uint32_t i = 0; i < n_lanes; ++i) {
+            mg_carry_fill_lane(pin_mask, pin_rows, leaves, consts, prog_seed, seed, first_index, l,
+                               lane0 + i, n_lanes, i, out);
+            if (classes)
+                classes[(size_t)l * n_lanes + i] = mg_carry_pinned(pin_mask, l) ? 0xFFFFFFFFu :
+                    mg_carry_branch(leaves[l], mg_carry_class(seed, prog_seed, l,
+                                                              first_index + lane0 + i));
+        }
+    return MG_OK;
+}
+
+int mg_carry_plan_host(const uint32_t* n_leaves, uint32_t n_jobs, uint32_t lanes,
+                       uint32_t max_leaves, uint64_t* out_offsets, uint64_t* out_bytes,
+                       uint64_t* out_leaf_stride_w) {
+    return mg_carry_plan(n_leaves, n_jobs, lanes, max_leaves, out_offsets, out_bytes,
+                         out_leaf_stride_w) ? MG_OK : MG_E_ARG;
 }
 
 // Host only: lanes lane0 .. lane0 + n_lanes - 1 of round r of the lane

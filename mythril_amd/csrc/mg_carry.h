@@ -1,0 +1,228 @@
+/* mg_carry_batch: remembered witnesses evaluated on the
+ * programs of the groups that extend them, many jobs in one launch sequence.
+ * Host part, plain C++ with no HIP call: the candidate generator v9 restated
+ * for host and device (include/mythgpu.h states it above mg_leafgen,
+ * oracle/gen_ref.py is its specification), the lane function of the fill
+ * kernel, the checks of a batch's counts and the plan of its device buffer;
+ * the ABI (mg_carry_batch, mg_carry_fill_host, mg_carry_plan_host), the kernels
+ * of mg_carry.hip and the CPU suite run this code.
+ *
+ * Lane i of a job evaluates the candidate whose pinned leaves (bit l of the
+ * job's mask) are the job's pin rows and whose free leaves are the generator's
+ * values at candidate index first_index + i, each masked to the leaf's width.
+ *
+ * One device buffer holds the whole batch, every region 256-byte aligned, in
+ * this order:
+ *   descs                one mg_pdesc per job: the interpreter's table
+ *   jobs                 one mg_carry_dev_job per job
+ *   first                one u64 per job, preset all ones: the interpreter's
+ *                        first_sat (lane 0 has candidate index 0 there)
+ *   per job              its pin mask, its pin rows, its leaf generators
+ *     (up to here one upload from a host image of the same layout)
+ *   out                  n_jobs i64 (first, -1: none), then n_jobs x
+ *                        max_leaves x 8 words: one download
+ *   per job, its leaves  [leaf][limb][lanes] at a common stride: the largest
+ *                        n_leaves of the batch x 8 x lanes words, rounded up to
+ *                        256 bytes (the stride the interpreter's shell applies)
+ * offsets[]: MG_CY_SHARED shared regions, then MG_CY_JOB_REGIONS per job. */
+#ifndef MG_CARRY_H
+#define MG_CARRY_H
+
+#include <stdint.h>
+#include "mythgpu.h"
+#include "mythgpu_ir.h"
+#include "mg_device.h"
+#include "mg_repair.h"
+
+enum { MG_CY_DESCS, MG_CY_JOBS, MG_CY_FIRST, MG_CY_OUT, MG_CY_SHARED };
+enum { MG_CY_MASK, MG_CY_ROWS, MG_CY_GEN, MG_CY_LEAVES, MG_CY_JOB_REGIONS };
+#define MG_CY_OFF(g, k) ((size_t)MG_CY_SHARED + (size_t)(g) * MG_CY_JOB_REGIONS + (k))
+
+static_assert(MG_CARRY_SHARED == MG_CY_SHARED && MG_CARRY_JOB_REGIONS == MG_CY_JOB_REGIONS,
+              "include/mythgpu.h documents the length of the offset table");
+
+#define MG_CARRY_TILE 256u
+/* leaves of one fill launch along the grid's y; leaves beyond are strided */
+#define MG_CARRY_GRID_LEAVES 1024u
+
+#define MG_CARRY_FN MG_REPAIR_FN
+
+/* The job as the kernels read it: blockIdx.z (fill) / blockIdx.x (gather). */
+struct mg_carry_dev_job {
+    const uint32_t* mask;       /* [(n_leaves + 31) / 32] */
+    const uint32_t* rows;       /* [n_leaves][8] */
+    const mg_leafgen* gen;      /* [n_leaves], as loaded */
+    const uint32_t* consts;     /* the program's constant table */
+    uint32_t* leaves;           /* its leaf region [n_leaves][8][lanes] */
+    uint64_t prog_seed;
+    uint32_t n_leaves;
+    uint32_t pad;
+};
+
+#define MG_CARRY_GOLD 0x9E3779B97F4A7C15ull
+#define MG_CARRY_MIX1 0xBF58476D1CE4E5B9ull
+#define MG_CARRY_SALT_P 0xD1B54A32D192ED03ull
+#define MG_CARRY_SALT_L 0x8CB92BA72F3D8DD7ull
+#define MG_CARRY_CLS_MUL 0x2545F491u
+
+MG_CARRY_FN uint64_t mg_carry_salt(uint64_t prog_seed, uint32_t leaf) {
+    return (prog_seed * MG_CARRY_SALT_P) ^ (((uint64_t)leaf + 1) * MG_CARRY_SALT_L);
+}
+
+/* the class of leaf `leaf` for the 64 candidates around idx: 0 .. 99 */
+MG_CARRY_FN uint32_t mg_carry_class(uint64_t seed, uint64_t prog_seed, uint32_t leaf,
+                                    uint64_t idx) {
+    const uint64_t ss = seed ^ mg_carry_salt(prog_seed, leaf);
+    const uint32_t y = (((uint32_t)(idx >> 6) ^ (uint32_t)ss) * MG_CARRY_CLS_MUL) ^
+                       (uint32_t)(ss >> 32);
+    return mg_repair_mulhi(y, 100u);
+}
+
+/* which branch a class takes: 0 r0 (64 bits), 1 boundary, 2 pool, 3 uniform */
+MG_CARRY_FN uint32_t mg_carry_branch(const mg_leafgen& g, uint32_t cls) {
+    if (g.pct_uniform <= cls && cls < g.pct_small) return 0;
+    if (g.pct_small <= cls && cls < g.pct_boundary) return 1;
+    if (cls >= g.pct_boundary && g.pool_n > 0) return 2;
+    return 3;
+}
+
+/* Generator v9: the value of leaf `leaf` at candidate index idx, masked to the
+ * leaf's width, upper limbs zero.  consts: the program's constant table (read
+ * at pool_off .. pool_off + pool_n - 1 in the pool class only). */
+MG_CARRY_FN void mg_carry_gen(uint64_t seed, uint64_t prog_seed, uint32_t leaf, uint64_t idx,
+                              const mg_leafgen& g, const uint32_t* consts, uint32_t* v) {
+    uint64_t s = (seed ^ mg_carry_salt(prog_seed, leaf) ^ idx) + MG_CARRY_GOLD;
+    const uint64_t u = s ^ (s >> 32);
+    const uint64_t z = u * MG_CARRY_MIX1;
+    const uint64_t r0 = z ^ (z >> 32);
+    const uint32_t lo = (uint32_t)r0;
+    const uint32_t w = g.width;
+    const uint32_t br = mg_carry_branch(g, mg_carry_class(seed, prog_seed, leaf, idx));
+    for (uint32_t k = 0; k < 8; ++k) v[k] = 0;
+    if (br == 0) {
+        v[0] = lo;
+        v[1] = (uint32_t)(r0 >> 32);
+    } else if (br == 1) {
+        const uint32_t kind = mg_repair_mulhi(lo, 6u);
+        const uint32_t k = mg_repair_mulhi(lo * 0x9E3779B1u, w);
+        if (kind == 1) {
+            v[0] = 1;
+        } else if (kind == 2) {
+            mg_repair_addpow(v, w - 1, false);
+        } else if (kind == 3) {
+            for (uint32_t i = 0; i < 8; ++i) v[i] = 0xFFFFFFFFu;
+        } else if (kind == 4) {
+            mg_repair_addpow(v, k, false);
+            mg_repair_addpow(v, 0, false);
+        } else if (kind == 5) {
+            mg_repair_addpow(v, k, false);
+            mg_repair_addpow(v, 0, true);
+        }
+    } else if (br == 2) {
+        const uint32_t e = g.pool_off + mg_repair_mulhi(lo, g.pool_n);
+        const uint32_t delta = mg_repair_mulhi(lo * 0x85EBCA6Bu, 3u);
+        for (uint32_t k = 0; k < 8; ++k) v[k] = consts[(uint64_t)e * 8 + k];
+        if (delta != 1) mg_repair_addpow(v, 0, delta == 0);
+    } else {
+        const uint32_t x = lo ^ (uint32_t)(r0 >> 32);
+        const uint32_t c[3] = {0x85EBCA6Bu, 0xC2B2AE35u, 0x27D4EB2Fu};
+        v[0] = lo;
+        v[1] = (uint32_t)(r0 >> 32);
+        for (uint32_t k = 0; k < 3; ++k) {
+            const uint64_t p = (uint64_t)x * c[k] + r0;
+            v[2 * k + 2] = (uint32_t)p;
+            v[2 * k + 3] = (uint32_t)(p >> 32);
+        }
+    }
+    mg_repair_mask(v, w);
+}
+
+MG_CARRY_FN bool mg_carry_pinned(const uint32_t* mask, uint32_t leaf) {
+    return (mask[leaf >> 5] >> (leaf & 31)) & 1u;
+}
+
+/* The fill kernel's lane function: leaf `leaf` of lane `lane` of a job into
+ * column `col` of rows of `stride` words: out[(leaf * 8 + k) * stride + col]. */
+MG_CARRY_FN void mg_carry_fill_lane(const uint32_t* mask, const uint32_t* rows,
+                                    const mg_leafgen* gen, const uint32_t* consts,
+                                    uint64_t prog_seed, uint64_t seed, uint64_t first_index,
+                                    uint32_t leaf, uint32_t lane, uint64_t stride, uint64_t col,
+                                    uint32_t* out) {
+    uint32_t v[8];
+    if (mg_carry_pinned(mask, leaf)) {
+        for (uint32_t k = 0; k < 8; ++k) v[k] = rows[(uint64_t)leaf * 8 + k];
+        mg_repair_mask(v, gen[leaf].width);
+    } else {
+        mg_carry_gen(seed, prog_seed, leaf, first_index + lane, gen[leaf], consts, v);
+    }
+    for (uint32_t k = 0; k < 8; ++k) out[((uint64_t)leaf * 8 + k) * stride + col] = v[k];
+}
+
+/* the shared counts mg_carry_batch accepts */
+static inline bool mg_carry_shared_ok(uint32_t n_jobs, uint32_t lanes) {
+    return n_jobs >= 1 && n_jobs <= MG_CARRY_MAX_JOBS && lanes >= 1 &&
+           lanes <= MG_REPAIR_MAX_LANES;
+}
+
+/* what the generator reads of a leaf table is inside the constants */
+static inline bool mg_carry_gen_ok(const mg_leafgen* gen, uint32_t n_leaves, uint32_t n_consts) {
+    for (uint32_t l = 0; l < n_leaves; ++l) {
+        if (gen[l].width < 1 || gen[l].width > 256) return false;
+        if (gen[l].pool_n && (gen[l].pool_off > n_consts || gen[l].pool_n > n_consts - gen[l].pool_off))
+            return false;
+    }
+    return true;
+}
+
+/* a + round_up(count * unit, 256) into *a; false when 64 bits overflow */
+static inline bool mg_cy_add(uint64_t* a, uint64_t count, uint64_t unit) {
+    uint64_t b;
+    if (__builtin_mul_overflow(count, unit, &b)) return false;
+    if (__builtin_add_overflow(b, (uint64_t)255, &b)) return false;
+    b &= ~(uint64_t)255;
+    return !__builtin_add_overflow(*a, b, a);
+}
+
+/* Every offset of the batch's buffer and its size; false when the shared
+ * counts are out of range or 64 bits overflow.  n_leaves[g] need not be below
+ * max_leaves: sizes are computed with checked arithmetic.  *leaf_stride_w (u32
+ * words, may be NULL): the distance between two jobs' leaf regions. */
+static inline bool mg_carry_plan(const uint32_t* n_leaves, uint32_t n_jobs, uint32_t lanes,
+                                 uint32_t max_leaves, uint64_t* offsets, uint64_t* bytes,
+                                 uint64_t* leaf_stride_w) {
+    if (!n_leaves || !offsets || !bytes || !mg_carry_shared_ok(n_jobs, lanes)) return false;
+    uint64_t at = 0;
+    offsets[MG_CY_DESCS] = at;
+    if (!mg_cy_add(&at, n_jobs, sizeof(mg_pdesc))) return false;
+    offsets[MG_CY_JOBS] = at;
+    if (!mg_cy_add(&at, n_jobs, sizeof(mg_carry_dev_job))) return false;
+    offsets[MG_CY_FIRST] = at;
+    if (!mg_cy_add(&at, n_jobs, 8)) return false;
+    uint32_t most = 0;
+    for (uint32_t g = 0; g < n_jobs; ++g) {
+        const uint64_t n = n_leaves[g];
+        most = n_leaves[g] > most ? n_leaves[g] : most;
+        offsets[MG_CY_OFF(g, MG_CY_MASK)] = at;
+        if (!mg_cy_add(&at, (n + 31) / 32, 4)) return false;
+        offsets[MG_CY_OFF(g, MG_CY_ROWS)] = at;
+        if (!mg_cy_add(&at, n, 32)) return false;
+        offsets[MG_CY_OFF(g, MG_CY_GEN)] = at;
+        if (!mg_cy_add(&at, n, sizeof(mg_leafgen))) return false;
+    }
+    offsets[MG_CY_OUT] = at;
+    uint64_t out_b;
+    if (__builtin_mul_overflow((uint64_t)max_leaves * 32u + 8u, (uint64_t)n_jobs, &out_b))
+        return false;
+    if (!mg_cy_add(&at, out_b, 1)) return false;
+    uint64_t leaf_b = 0;
+    if (!mg_cy_add(&leaf_b, (uint64_t)most * 32u, lanes)) return false;
+    for (uint32_t g = 0; g < n_jobs; ++g) {
+        offsets[MG_CY_OFF(g, MG_CY_LEAVES)] = at;
+        if (__builtin_add_overflow(at, leaf_b, &at)) return false;
+    }
+    *bytes = at;
+    if (leaf_stride_w) *leaf_stride_w = leaf_b / 4;
+    return true;
+}
+
+#endif

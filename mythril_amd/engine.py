@@ -39,7 +39,8 @@ EXPORTS = ("mg_init", "mg_init_layout", "mg_layouts", "mg_free", "mg_last_error"
            "mg_walk_bound_mutate_host", "mg_walk_uf", "mg_walk_uf_resolve_host",
            "mg_walk_uf_mutate_host", "mg_walk_sum", "mg_walk_sum_mutate_host", "mg_walk_batch",
            "mg_walk_batch_plan_host", "mg_walk_batch_shape_ok_host", "mg_census_batch",
-           "mg_census_batch_plan_host", "mg_census_batch_blocks_host", "mg_batch_witness")
+           "mg_census_batch_plan_host", "mg_census_batch_blocks_host", "mg_batch_witness",
+           "mg_carry_batch", "mg_carry_fill_host", "mg_carry_plan_host")
 
 
 def layouts() -> Dict[int, Tuple[int, int]]:
@@ -115,7 +116,16 @@ class CensusShape(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("n_probes", "n_roots", "mask_probe0")]
 
 
+class CarryJob(C.Structure):
+    """mg_carry_job (include/mythgpu.h): one job of mg_carry_batch."""
+    _fields_ = [("prog", C.c_void_p), ("pin_rows", C.c_void_p), ("pin_mask", C.c_void_p)]
+
+
 # include/mythgpu.h
+CARRY_MAX_JOBS = 256
+CARRY_MAX_LANES = 1 << 20
+CARRY_SHARED = 4
+CARRY_JOB_REGIONS = 4
 CENSUS_BATCH_MAX_JOBS = 256
 CENSUS_BATCH_SHARED = 2
 CENSUS_BATCH_JOB_REGIONS = 2
@@ -205,6 +215,10 @@ def load_library(path: str = _LIB_PATH, check_digest: bool = True):
                                                   C.c_size_t]
         lib.mg_census_batch_blocks_host.argtypes = [u32, u64]
         lib.mg_batch_witness.argtypes = [p, C.POINTER(p), p, u32, u64, p, u32, p, u32]
+        lib.mg_carry_batch.argtypes = [p, C.POINTER(CarryJob), u32, C.POINTER(Gen), u32, p, p, u32,
+                                       p]
+        lib.mg_carry_fill_host.argtypes = [p, u32, p, u32, u64, p, p, u64, u64, u32, u32, u32, p, p]
+        lib.mg_carry_plan_host.argtypes = [p, u32, u32, u32, p, C.POINTER(u64), C.POINTER(u64)]
         lib.mg_batch_create.argtypes = [p, C.POINTER(p), u32, C.POINTER(p)]
         lib.mg_batch_free.argtypes = [p]
         lib.mg_batch_free.restype = None
@@ -446,6 +460,54 @@ class Engine:
                                   nfail_hist=hist[i, :r + 1].astype(np.int64),
                                   best_nfail=int(best_nfail[i]), best_index=int(best_index[i]),
                                   kernel_ms=ms))
+        return out
+
+    def carry_batch(self, jobs, seed: int, first_index: int, lanes: int, want_fill: bool = False):
+        """Remembered witnesses evaluated on eval-form programs, all jobs in
+        one launch sequence (mg_carry_batch).  ``jobs``: a
+        list of ``(lp, pin_rows, pin_mask)`` — a program loaded with its leaf
+        generators, rows ``(n_leaves, 8)`` uint32 and the words of the pin mask
+        (``carry.pins`` builds both).  Lane i of a job evaluates the pin rows
+        on the pinned leaves and the generator's candidate ``first_index + i``
+        on the free ones.  Returns per job ``(first, leaves)``: the lowest lane
+        on which every root holds (-1: none) and that lane's leaf rows
+        ``(n_leaves, 8)`` (None when there is none); with ``want_fill`` a third
+        element, the job's leaf region ``(n_leaves, 8, lanes)`` as the device
+        filled it.  More than ``CARRY_MAX_JOBS`` jobs run as consecutive
+        batches; jobs are independent, so the results do not depend on the
+        split."""
+        jobs = [(lp, np.ascontiguousarray(r, dtype=np.uint32).reshape(-1, 8),
+                 np.ascontiguousarray(m, dtype=np.uint32).reshape(-1)) for lp, r, m in jobs]
+        for lp, r, m in jobs:
+            n = len(lp.program.leaves)
+            if r.shape[0] != n or m.shape[0] != (n + 31) // 32:
+                raise ValueError("pin rows must be (n_leaves, 8) and the pin mask "
+                                 "(n_leaves + 31) // 32 words")
+        g = Gen(seed & (2**64 - 1), first_index)
+        out = []
+        for lo in range(0, len(jobs), CARRY_MAX_JOBS):
+            part = jobs[lo:lo + CARRY_MAX_JOBS]
+            n = len(part)
+            arr = (CarryJob * n)()
+            for i, (lp, r, m) in enumerate(part):
+                arr[i].prog, arr[i].pin_rows, arr[i].pin_mask = lp.handle, _ptr(r), _ptr(m)
+            counts = [len(lp.program.leaves) for lp, _, _ in part]
+            max_leaves = max(1, max(counts))
+            first = np.full(n, -1, dtype=np.int64)
+            wit = np.zeros((n, max_leaves, 8), dtype=np.uint32)
+            fill = None
+            if want_fill:
+                _, _, stride = carry_plan_host(counts, lanes, max_leaves)
+                fill = np.zeros((n, max(1, stride)), dtype=np.uint32)
+            rc = self.lib.mg_carry_batch(self._ctx, arr, n, C.byref(g), lanes, _ptr(first),
+                                         _ptr(wit), max_leaves, _ptr(fill))
+            self._check(rc, "mg_carry_batch")
+            for i, k in enumerate(counts):
+                f = int(first[i])
+                res = (f, wit[i, :k].copy() if f >= 0 else None)
+                if want_fill:
+                    res += (fill[i, :k * 8 * lanes].reshape(k, 8, lanes).copy(),)
+                out.append(res)
         return out
 
     def batch_witness(self, pairs, seed: int, want_probes: bool = True):
@@ -1107,6 +1169,56 @@ def census_batch_plan_host(shapes: Sequence[CensusShape], n_cand: int, chunk: in
         raise EngineError("census_batch: " + why.value.decode(errors="replace"))
     return (offs[:CENSUS_BATCH_SHARED + n * CENSUS_BATCH_JOB_REGIONS], int(total.value),
             int(got.value))
+
+
+def carry_plan_host(n_leaves: Sequence[int], lanes: int, max_leaves: int):
+    """Host-only: ``(offsets, bytes, leaf_stride_words)`` of the device buffer
+    mg_carry_batch uses for jobs of these leaf counts (mg_carry_plan_host:
+    ``CARRY_SHARED`` shared offsets, then ``CARRY_JOB_REGIONS`` per job — mask,
+    rows, generators, leaf region).  :class:`EngineError` where the library
+    refuses: counts out of range or sizes beyond 64 bits."""
+    lib = load_library(check_digest=False)
+    counts = np.ascontiguousarray(n_leaves, dtype=np.uint32)
+    n = counts.shape[0]
+    offs = np.zeros(CARRY_SHARED + max(1, n) * CARRY_JOB_REGIONS, dtype=np.uint64)
+    total, stride = C.c_uint64(0), C.c_uint64(0)
+    rc = lib.mg_carry_plan_host(_ptr(counts), n, lanes, max_leaves, _ptr(offs), C.byref(total),
+                                C.byref(stride))
+    if rc != 0:
+        raise EngineError("carry_batch: %d jobs at %d lanes: counts out of range or a buffer "
+                          "beyond 64 bits" % (n, lanes))
+    return offs[:CARRY_SHARED + n * CARRY_JOB_REGIONS], int(total.value), int(stride.value)
+
+
+def carry_fill_host(leafgen: Sequence[LeafGen], consts: np.ndarray, prog_seed: int,
+                    pin_rows: np.ndarray, pin_mask: np.ndarray, seed: int, first_index: int,
+                    lanes: int, lane0: int = 0, n_lanes: Optional[int] = None,
+                    want_classes: bool = False):
+    """Host-only: lanes ``lane0 .. lane0 + n_lanes - 1`` of one mg_carry_batch
+    job as the fill kernel writes them (mg_carry_fill_host, the kernel's own
+    lane function): ``(n_leaves, 8, n_lanes)`` uint32, and with
+    ``want_classes`` the generator branch of every free leaf and lane
+    (0 r0, 1 boundary, 2 pool, 3 uniform; 0xFFFFFFFF: pinned)."""
+    lib = load_library(check_digest=False)
+    gens = list(leafgen)
+    n = len(gens)
+    n_lanes = lanes - lane0 if n_lanes is None else n_lanes
+    garr = (LeafGen * max(1, n))(*gens)
+    consts = np.ascontiguousarray(consts, dtype=np.uint32).reshape(-1, 8)
+    rows = np.ascontiguousarray(pin_rows, dtype=np.uint32).reshape(-1, 8)
+    mask = np.ascontiguousarray(pin_mask, dtype=np.uint32).reshape(-1)
+    if rows.shape[0] != n or mask.shape[0] != (n + 31) // 32:
+        raise ValueError("pin rows must be (n_leaves, 8) and the pin mask (n_leaves + 31) // 32 "
+                         "words")
+    out = np.zeros((n, 8, max(0, n_lanes)), dtype=np.uint32)
+    cls = np.zeros((n, max(0, n_lanes)), dtype=np.uint32) if want_classes else None
+    rc = lib.mg_carry_fill_host(C.cast(garr, C.c_void_p), n, _ptr(consts), consts.shape[0],
+                                prog_seed & (2**64 - 1), _ptr(rows), _ptr(mask),
+                                seed & (2**64 - 1), first_index, lanes, lane0, max(0, n_lanes),
+                                _ptr(out), _ptr(cls))
+    if rc != 0:
+        raise EngineError("mg_carry_fill_host refused its arguments (%d)" % rc)
+    return (out, cls) if want_classes else out
 
 
 def census_batch_blocks_host(n_jobs: int, n: int) -> int:

@@ -120,6 +120,13 @@ class SolverStatistics:
         self.repair_attempts = 0        # missed groups handed to the local search (repair.py)
         self.repair_hits = 0            # ... that it turned into a witness
         self.repair_batches = 0         # repair.repair_groups calls of batch_is_possible
+        self.carry_exact = 0            # groups answered from the group-hit memo (carry.py)
+        self.carry_attempts = 0         # groups evaluated under a carried witness
+        self.carry_hits = 0             # ... on which every root held
+        self.carry_candidates = 0       # candidates those evaluations ran
+        self.kernel_calls = 0           # engine calls whose device time kernel_time sums
+        self.launches = 0               # kernel launches of those calls (_count_kernel)
+        self.carry_gated = 0            # extensions not carried: a carried table above the cap
         self.phase = {k: 0.0 for k in PHASES}
 
     def gpu_report(self) -> str:
@@ -127,7 +134,11 @@ class SolverStatistics:
             "\nGPU repair: attempts: {} hits: {}{}".format(
                 self.repair_attempts, self.repair_hits,
                 " batches: {}".format(self.repair_batches) if self.repair_batches else "")
-            if self.repair_attempts or self.repair_hits else "")
+            if self.repair_attempts or self.repair_hits else "") + (
+            "\nGPU carry: exact: {} attempts: {} hits: {} candidates: {}{}".format(
+                self.carry_exact, self.carry_attempts, self.carry_hits, self.carry_candidates,
+                " table-gated: {}".format(self.carry_gated) if self.carry_gated else "")
+            if self.carry_exact or self.carry_attempts or self.carry_gated else "")
 
     def _gpu_report(self) -> str:
         return ("GPU pre-filter: queries: {} hits: {} fallbacks: {} unsupported: {} errors: {} "
@@ -160,10 +171,28 @@ class _Phase:
         return False
 
 
-def _count_kernel(eng) -> None:
+SEARCH_LAUNCH = 1 << 26        # candidates per launch of mg_search / mg_batch_search
+
+
+def _search_launches(n_cand: int, hit=None) -> int:
+    """Kernel launches of one engine search over ``n_cand`` candidates: the
+    search launches, then the witness regeneration — always one for a batched
+    search (``hit`` None); for ``Engine.search`` one on a hit and one more when
+    a solve-mode witness is re-evaluated for its probes (``_witness``)."""
+    n = max(1, -(-n_cand // SEARCH_LAUNCH))
+    if hit is None:
+        return n + 1
+    idx, prog = hit
+    return n + (0 if idx < 0 else 2 if prog.solved else 1)
+
+
+def _count_kernel(eng, launches: int = 0) -> None:
     """Device time of the engine's last search (HIP events around its
-    launches inside libmythgpu, ``mg_last_kernel_ms``)."""
+    launches inside libmythgpu, ``mg_last_kernel_ms``) and the kernel launches
+    the call made."""
     ms = getattr(eng, "last_kernel_ms", None)
+    stats.kernel_calls += 1
+    stats.launches += launches
     if ms is not None:
         stats.kernel_time += ms() / 1000.0
 
@@ -209,6 +238,11 @@ REPAIR_WALKERS = 16
 # a batch_is_possible search missed go to ONE repair.repair_groups call, their
 # walks in one launch sequence; unset, nothing changes
 REPAIR_BATCH = False
+# opt-in (MYTHRIL_GPU_CARRY=1): a group that found a witness is remembered
+# (_group_hit); an exact repeat is answered from the memo and a group that
+# extends remembered groups is evaluated once under their witnesses before it
+# is compiled for a search (carry.py); unset, nothing changes
+CARRY = False
 SHAPE_MIN, SHAPE_FLOOR, SHAPE_PROBE = 4, 1.0 / 16, 8
 
 
@@ -231,9 +265,14 @@ def configure_from_env(env=None) -> None:
     through sums, differences, masks and shifts too;
     ``MYTHRIL_GPU_REPAIR_BATCH=1`` (off by default; with
     ``MYTHRIL_GPU_REPAIR`` 3..7) hands the groups a ``batch_is_possible``
-    search missed to one batched walk (``repair.repair_groups``)."""
+    search missed to one batched walk (``repair.repair_groups``);
+    ``MYTHRIL_GPU_CARRY=1`` (off by default) remembers the witnesses of groups
+    and evaluates them on the groups that extend them (``carry.py``),
+    ``MYTHRIL_GPU_CARRY_LANES`` the candidates of such an evaluation when the
+    extension has fresh symbols, ``MYTHRIL_GPU_CARRY_MAX_ENTRIES`` the largest
+    carried table an extension is evaluated with."""
     global GPU_ENABLED, DEVICES, SEARCH_CANDIDATES, SEARCH_BUDGET_MS, SHAPE_GATE, REFUTE, REPAIR
-    global REPAIR_SCORED, REPAIR_BATCH
+    global REPAIR_SCORED, REPAIR_BATCH, CARRY
     import os
     env = os.environ if env is None else env
     GPU_ENABLED = env.get("MYTHRIL_GPU", "1").strip().lower() not in ("0", "off", "false", "no")
@@ -255,6 +294,13 @@ def configure_from_env(env=None) -> None:
         "1", "on", "true", "yes")
     REPAIR_BATCH = env.get("MYTHRIL_GPU_REPAIR_BATCH", "0").strip().lower() in (
         "1", "on", "true", "yes")
+    CARRY = env.get("MYTHRIL_GPU_CARRY", "0").strip().lower() in ("1", "on", "true", "yes")
+    if env.get("MYTHRIL_GPU_CARRY_LANES"):
+        from . import carry
+        carry.CARRY_LANES = min(1 << 20, max(1, int(env["MYTHRIL_GPU_CARRY_LANES"])))
+    if env.get("MYTHRIL_GPU_CARRY_MAX_ENTRIES"):
+        from . import carry
+        carry.MAX_ENTRIES = max(0, int(env["MYTHRIL_GPU_CARRY_MAX_ENTRIES"]))
 
 
 configure_from_env()
@@ -587,7 +633,7 @@ def batch_search_devices(progs: Sequence[Program], n_cand: int):
             loaded = [eng.load(p, search_leafgen(p), prog_seed=0) for p in progs]
         with _Phase("search"):
             hits = eng.batch_search(loaded, SEARCH_SEED, n_cand, want_probes=True)
-            _count_kernel(eng)
+            _count_kernel(eng, _search_launches(n_cand))
             t0 = time.perf_counter()
             out = [(h[0], _witness(eng, lp, h) if h[0] >= 0 else None)
                    for lp, h in zip(loaded, hits)]
@@ -600,7 +646,7 @@ def batch_search_devices(progs: Sequence[Program], n_cand: int):
         eng = get_engine(*dev)
         loaded = [eng.load(progs[i], search_leafgen(progs[i]), prog_seed=0) for i in idx]
         hits = eng.batch_search(loaded, SEARCH_SEED, n_cand, want_probes=True)
-        _count_kernel(eng)
+        _count_kernel(eng, _search_launches(n_cand))
         for i, lp, h in zip(idx, loaded, hits):
             out[i] = (h[0], _witness(eng, lp, h) if h[0] >= 0 else None)
     with _Phase("search"):
@@ -645,7 +691,7 @@ def search_assignment_axis(prog: Program, n_cand: int, devices: Sequence[int]):
         lp = eng.load(prog, search_leafgen(prog), prog_seed=0)
         n = bounds[g + 1] - bounds[g]
         h = eng.search(lp, SEARCH_SEED, n, first_index=bounds[g]) if n else (-1, None)
-        _count_kernel(eng)
+        _count_kernel(eng, _search_launches(n, (h[0], prog)) if n else 0)
         res[g] = (h[0], _witness(eng, lp, h) if h[0] >= 0 else None)
     with _Phase("search"):
         _on_devices(run, list(enumerate(device_slots(devices))))
@@ -672,6 +718,70 @@ _miss_index: "Dict[int, List[frozenset]]" = {}
 # COMPILER=py) measured ~0.035 ms/node
 COMPILE_MS_PER_NODE = 0.004
 COMPILE_MS_PER_NODE_PY = 0.04
+
+
+# Group-hit memo (carry.py; filled only with CARRY on): the
+# witness of every group a search, a repair or a carry answered, bounded like
+# the miss memo and indexed by the key's minimum id the same way.
+from .carry import HitMemo  # noqa: E402
+
+_hit_memo = HitMemo(GROUP_MISS_SIZE)
+_group_hit = _hit_memo.hits
+_hit_index = _hit_memo.index
+
+
+def _note_hit(key, assignment, prog=None) -> None:
+    if CARRY and key is not None and assignment is not None:
+        _hit_memo.size = GROUP_MISS_SIZE
+        _hit_memo.note(key, assignment, prog)
+
+
+def _carry_groups(groups, eng=None):
+    """What the hit memo and the carry answer of ``groups``, a list of ``(key,
+    nodes)``: key -> (assignment, program).  Exact repeats come from the memo
+    with no launch (their program: the group's cached search program, else the
+    one that evidenced the hit); the groups that extend remembered groups go
+    into ONE ``Engine.carry_batch`` call on the first device, deduplicated by
+    key.  A group missing from the result goes on as before."""
+    from . import carry
+    out, jobs = {}, {}
+    cache = _SEARCH_CACHE or {}
+    for key, nodes in groups:
+        if key in out or key in jobs or not key:
+            continue
+        what = carry.plan(key, _hit_memo)
+        if what is None:
+            continue
+        if what[0] == "exact":
+            prog = cache.get((tuple(n.id for n in nodes), ())) or _hit_memo.progs.get(key)
+            if prog is None:
+                continue
+            stats.carry_exact += 1
+            out[key] = (what[1], prog)
+        elif max(carry.table_sizes(what[1]).values(), default=0) > carry.MAX_ENTRIES:
+            # the eval form reads a table entry by entry: a carried table of
+            # this size makes the compile dearer than the search it may save
+            stats.carry_gated += 1
+        else:
+            jobs[key] = (nodes, what[1])
+    if jobs:
+        eng = eng or get_engine((list(DEVICES) or [0])[0])
+        res = carry.run(eng, list(jobs.values()), SEARCH_SEED, search_leafgen, phase=_Phase)
+        ran = [r for r in res if r is not None]
+        if ran:
+            # fill (when any job has a leaf), interpreter, gather
+            _count_kernel(eng, 3 if any(len(p.leaves) for _, p, _ in ran) else 2)
+        for key, r in zip(jobs, res):
+            if r is None:                  # no eval form (Unsupported): nothing ran
+                continue
+            stats.carry_attempts += 1
+            asg, prog, n = r
+            stats.carry_candidates += n
+            if asg is not None:
+                stats.carry_hits += 1
+                _note_hit(key, asg, prog)
+                out[key] = (asg, prog)
+    return out
 
 
 def _group_key(nodes: Sequence[N.Node]) -> frozenset:
@@ -765,6 +875,9 @@ def clear_search_memos() -> None:
     _group_miss.clear()
     _miss_index.clear()
     _shape_stats.clear()
+    _hit_memo.clear()
+    from . import carry
+    carry.clear()
 
 
 def _compile_estimate_ms(buckets, sizes) -> float:
@@ -811,26 +924,33 @@ def gpu_search(nodes: Sequence[N.Node], budget_ms: float):
         stats.refuted += 1
         _note_miss(dead, GROUND_MISS)
         return None
+    # groups the hit memo or a carried witness answers (MYTHRIL_GPU_CARRY=1)
+    # are not compiled in solve mode and not searched
+    carried = _carry_groups(list(zip(keys, buckets))) if CARRY else {}
+    todo = [k for k, key in enumerate(keys) if key not in carried]
     shape = query_shape(nodes[-1]) if nodes else ""
+    if carried and not todo:
+        _shape_note(shape, True)
+        return _merge([carried[k][0] for k in keys]), [carried[k][1] for k in keys]
     if not _shape_gate(shape):
         stats.shape_skipped += 1
         return None
-    if _compile_estimate_ms(buckets, sizes) > budget_ms:
+    if _compile_estimate_ms([buckets[k] for k in todo], [sizes[k] for k in todo]) > budget_ms:
         stats.gated += 1
         return None
     with _Phase("compile"):
-        progs = [_compile_search(b) for b in buckets]
+        progs = [_compile_search(buckets[k]) for k in todo]
     n_cand = _n_cand(progs, budget_ms)
-    if any(_known_miss(k, n_cand) for k in keys):
+    if any(_known_miss(keys[k], n_cand) for k in todo):
         stats.memo_misses += 1
         return None
     devices = list(DEVICES) or [0]
     ground = [_ground_value(p) for p in progs]
     if any(g is False for g in ground):
         stats.ground_false += 1
-        for k, g in zip(keys, ground):
+        for k, g in zip(todo, ground):
             if g is False:
-                _note_miss(k, GROUND_MISS)
+                _note_miss(keys[k], GROUND_MISS)
         return None
     if len(progs) > 1 or len(devices) > 1 or ground[0] is not None:
         hits = search_groups(progs, n_cand)
@@ -840,18 +960,24 @@ def gpu_search(nodes: Sequence[N.Node], budget_ms: float):
             lp = eng.load(progs[0], search_leafgen(progs[0]), prog_seed=0)
         with _Phase("search"):
             h = eng.search(lp, SEARCH_SEED, n_cand)
-            _count_kernel(eng)
+            _count_kernel(eng, _search_launches(n_cand, (h[0], progs[0])))
             hits = [(h[0], _witness(eng, lp, h) if h[0] >= 0 else None)]
     stats.gpu_candidates += sum(n_cand if i < 0 else i + 1 for i, _ in hits)
     if REPAIR and any(i < 0 for i, _ in hits):
-        hits = _repair_misses(buckets, hits, budget_ms, t_start)
-    for k, (i, _) in zip(keys, hits):
+        hits = _repair_misses([buckets[k] for k in todo], hits, budget_ms, t_start)
+    for k, p, g, (i, a) in zip(todo, progs, ground, hits):
         if i < 0:
-            _note_miss(k, n_cand)
+            _note_miss(keys[k], n_cand)
+        elif g is None:
+            _note_hit(keys[k], a, p)
     _shape_note(shape, all(i >= 0 for i, _ in hits))
     if any(i < 0 for i, _ in hits):
         return None
-    return _merge([a for _, a in hits]), progs
+    if not carried:
+        return _merge([a for _, a in hits]), progs
+    found = dict(zip(todo, zip((a for _, a in hits), progs)))
+    parts = [found[k] if k in found else carried[keys[k]] for k in range(len(keys))]
+    return _merge([a for a, _ in parts]), [p for _, p in parts]
 
 
 def _repair_misses(buckets, hits, budget_ms: float, t_start: float):
@@ -1108,6 +1234,7 @@ def batch_is_possible(constraint_sets, enforce_execution_time=True) -> List[bool
     if enforce_execution_time:
         timeout = min(timeout, time_handler.time_remaining() - 500)
     pending = []                          # (set, bucket programs)
+    sets_open = []                        # CARRY: (set, buckets) before the carry
     if timeout > 0 and _engine_failed is None and GPU_ENABLED:
         for cs in sets:
             if any(type(c) == bool and not c for c in cs):
@@ -1125,6 +1252,9 @@ def batch_is_possible(constraint_sets, enforce_execution_time=True) -> List[bool
                     _note_miss(dead, GROUND_MISS)
                     _remember(_gpu_missed, cs, True)
                     continue
+                if CARRY:                     # compiled below, after the carry
+                    sets_open.append((cs, buckets))
+                    continue
                 with _Phase("compile"):
                     progs = [_compile_search(b) for b in buckets]
             except Unsupported as e:
@@ -1136,6 +1266,38 @@ def batch_is_possible(constraint_sets, enforce_execution_time=True) -> List[bool
                 log.debug("GPU pre-filter failed on a set: %s", e)
                 continue
             pending.append((cs, progs, buckets))
+    # MYTHRIL_GPU_CARRY=1: all carry jobs of all sets in ONE Engine.carry_batch
+    # call; only the groups still open are compiled and searched (pending then
+    # holds each set's open groups, done its answered ones)
+    done = {}
+    if sets_open:
+        t0 = time.perf_counter()
+        try:
+            carried = _carry_groups([(_group_key(b), b) for _, bs in sets_open for b in bs])
+        except EngineUnavailable as e:
+            _engine_failed = _engine_failure(e, _engine_failed)
+            log.debug("GPU pre-filter unavailable: %s", e)
+            carried, sets_open = {}, []
+        except Exception as e:  # noqa: BLE001
+            stats.errors += 1
+            log.debug("GPU carry failed (%s: %s)", type(e).__name__, e)
+            carried = {}
+        stats.gpu_time += time.perf_counter() - t0
+        for cs, bs in sets_open:
+            rest = [b for b in bs if _group_key(b) not in carried]
+            try:
+                with _Phase("compile"):
+                    progs = [_compile_search(b) for b in rest]
+            except Unsupported as e:
+                stats.unsupported += 1
+                log.debug("GPU pre-filter: unsupported (%s)", e)
+                continue
+            except Exception as e:  # noqa: BLE001
+                stats.errors += 1
+                log.debug("GPU pre-filter failed on a set: %s", e)
+                continue
+            done[cs] = [carried[_group_key(b)] for b in bs if _group_key(b) in carried]
+            pending.append((cs, progs, rest))
     if pending:
         try:
             t0 = time.perf_counter()
@@ -1159,12 +1321,14 @@ def batch_is_possible(constraint_sets, enforce_execution_time=True) -> List[bool
                 found = [(0, repaired[p.group_key]) if k < 0 and h == SEARCHED and
                          p.group_key in repaired else (k, w)
                          for p, (k, w), h in zip(progs, found, how)]
-                for p, (k, _), h in zip(progs, found, how):
+                for p, (k, w), h in zip(progs, found, how):
                     # only a group that was launched (or folded to false)
                     # missed; a group skipped for a false sibling was not
                     # searched, and its key must not block later queries
                     if k < 0 and p.group_key is not None and h in (SEARCHED, GROUND_FALSE):
                         _note_miss(p.group_key, GROUND_MISS if h == GROUND_FALSE else n_cand)
+                    elif k >= 0 and h == SEARCHED:
+                        _note_hit(p.group_key, w, p)
                 if any(k < 0 for k, _ in found):
                     # the set goes straight to z3 only when the batch searched
                     # it as far as get_model alone would have; otherwise
@@ -1172,8 +1336,9 @@ def batch_is_possible(constraint_sets, enforce_execution_time=True) -> List[bool
                     if n_cand >= _n_cand(progs, min(timeout, SEARCH_BUDGET_MS)):
                         _remember(_gpu_missed, cs, True)
                 else:
-                    a = _merge([w for _, w in found])
-                    _remember(_batch_witness, cs, (a, progs))
+                    a = _merge([w for _, w in found] + [w for w, _ in done.get(cs, ())])
+                    _remember(_batch_witness, cs,
+                              (a, list(progs) + [p for _, p in done.get(cs, ())]))
         except EngineUnavailable as e:
             _engine_failed = _engine_failure(e, _engine_failed)
             log.debug("GPU pre-filter unavailable: %s", e)

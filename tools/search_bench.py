@@ -137,7 +137,19 @@ def shape_lines(eng, n_queries, n_sample=48):
                     "mean_ms": statistics.mean(lat),
                     "max_ms": max(lat), "gpu_misses": misses,
                     "memo_misses": M.stats.memo_misses, "shape_skipped": M.stats.shape_skipped,
-                    "gated": M.stats.gated, "kernel_ms_per_query":
+                    "gated": M.stats.gated,
+                    # MYTHRIL_GPU_CARRY=1: groups answered from
+                    # the hit memo, evaluated under a carried witness, and hit there
+                    "carry": {"on": M.CARRY, "exact": M.stats.carry_exact,
+                              "attempts": M.stats.carry_attempts, "hits": M.stats.carry_hits,
+                              "candidates": M.stats.carry_candidates,
+                              "table_gated": M.stats.carry_gated},
+                    # kernel launches per query (a search: its launches and the
+                    # witness regeneration; a carry: fill, interpreter, gather)
+                    # and the engine calls that made them
+                    "launches_per_query": M.stats.launches / len(lat),
+                    "launch_calls_per_query": M.stats.kernel_calls / len(lat),
+                    "kernel_ms_per_query":
                         M.stats.kernel_time * 1000.0 / len(lat),
                     "witness_ms_per_query": M.stats.witness_time * 1000.0 / len(lat),
                     "phase_ms_per_query": {k: v * 1000.0 / len(lat)
@@ -170,6 +182,8 @@ def main():
     ap.add_argument("--dags", type=int, default=1024)
     ap.add_argument("--chunks", type=int, default=8, help="2^20-candidate chunks (unsat query)")
     ap.add_argument("--shape-queries", type=int, default=64)
+    ap.add_argument("--stream-queries", type=int, default=48,
+                    help="distinct queries of a shape's get_model stream")
     ap.add_argument("--skip-corpus", action="store_true")
     args = ap.parse_args()
 
@@ -202,7 +216,7 @@ def main():
     out["unsat_query"] = {"ir_instructions": int(len(prog.code)), "candidates": args.chunks * chunk,
                           "ms_per_2^20_chunk": dt * 1000.0 / args.chunks}
 
-    out["shapes"] = shape_lines(eng, args.shape_queries)
+    out["shapes"] = shape_lines(eng, args.shape_queries, args.stream_queries)
     print(json.dumps({"shapes": out["shapes"]}), flush=True)
     if args.skip_corpus:
         print(json.dumps(out), flush=True)
