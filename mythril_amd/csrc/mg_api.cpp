@@ -1222,60 +1222,52 @@ static bool walk_table_ok(const uint32_t* table, uint32_t n_roots, uint32_t n_re
     return true;
 }
 
-// what scores a walk's neighbours: the residual table of mg_walk (no atoms, no
-// code) or the tree tables of mg_walk_tree (table: its root entries); aim: the
-// round of mg_walk_aim with its aim table (tree scoring); bound: the round of
-// mg_walk_sum.hip, whose entries have 5 words and a fixed value each; uf: with
-// the UF tables uft (host pointers; else empty); sum: with the lin words (else
-// null: all 0) and n_srows side rows between the residual probes and the U
-// rows (else 0).  bound, uf and sum also say which rung's checks and messages
-// walk_check applies.
-struct walk_scoring {
-    const uint32_t* table;
-    const uint32_t* atoms;
-    uint32_t n_atoms;
-    const uint32_t* code;
-    uint32_t n_code;
-    bool tree;
-    bool aim;
-    const uint32_t* entries;
-    uint32_t n_entries;
-    const uint32_t* pieces;
-    uint32_t n_pieces;
-    bool bound;
-    const uint32_t* fixed;
-    bool uf;
-    mg_uf_tables uft;
-    bool sum;
-    const uint32_t* lin;
-    uint32_t n_srows;
-};
+// A walk is one mg_walk_job (include/mythgpu.h) and the rung of the ladder that
+// runs it.  The rung says which of the job's tables are read, which checks and
+// messages walk_check applies and which kernels walk_run launches; the fields
+// a rung does not read are zero.  TABLE: roots is the residual table of
+// mg_walk (no atoms, no code); TREE: the tree tables of mg_walk_tree; AIM: the
+// round of mg_walk_aim with its aim table of 3-word entries; BOUND: the round
+// of mg_walk_sum.hip, whose entries have 5 words and a fixed value each; UF:
+// with the UF tables; SUM: with the lin words (below SUM: all 0) and n_srows
+// side rows between the residual probes and the U rows.
+enum walk_rung { TABLE, TREE, AIM, BOUND, UF, SUM };
+static bool walk_tree(walk_rung g) { return g >= TREE; }
+static bool walk_aim(walk_rung g) { return g >= AIM; }
+static bool walk_bound(walk_rung g) { return g >= BOUND; }
+static bool walk_uf(walk_rung g) { return g >= UF; }
+static bool walk_sum(walk_rung g) { return g == SUM; }
+
+// the job's UF tables (host pointers) as mg_walk_uf_ok and the kernels take them
+static mg_uf_tables walk_uf_tables(const mg_walk_job& j) {
+    return {j.slots, j.n_slots, j.funcs, j.n_funcs, j.cands, j.n_cands, j.ukeys, j.n_ukeys,
+            j.n_urows};
+}
 
 // What every walk refuses before it uploads or launches anything (the
 // message in ctx); mg_walk_batch asks the same of each of its jobs.
-static int walk_check(mg_ctx* ctx, const mg_prog* prog, const uint32_t* starts, uint32_t walkers,
-                      uint32_t n_roots, uint32_t mask_probe0, const walk_scoring& sc,
-                      uint32_t n_resid, uint32_t lanes, uint32_t max_rounds,
-                      const uint32_t* out_leaves, const uint32_t* out_nfail,
-                      const uint32_t* out_cost, const uint32_t* out_rounds,
-                      const uint32_t* out_winner) {
-    const uint32_t* table = sc.table;
-    if (!ctx || !prog || !starts || !table || !out_leaves || !out_nfail || !out_cost ||
-        !out_rounds || !out_winner || (sc.n_atoms && !sc.atoms) || (sc.n_code && !sc.code) ||
-        (sc.n_entries && !sc.entries) || (sc.n_pieces && !sc.pieces))
+static int walk_check(mg_ctx* ctx, const mg_walk_job& j, walk_rung rung, uint32_t walkers,
+                      uint32_t lanes, uint32_t max_rounds) {
+    const mg_prog* prog = j.prog;
+    const uint32_t* table = j.roots;
+    const uint32_t n_roots = j.n_roots, mask_probe0 = j.mask_probe0, n_resid = j.n_resid;
+    const mg_uf_tables uft = walk_uf_tables(j);
+    if (!ctx || !prog || !j.starts || !table || !j.out_leaves || !j.out_nfail || !j.out_cost ||
+        !j.out_rounds || !j.out_winner || (j.n_atoms && !j.atoms) || (j.n_code && !j.code) ||
+        (j.n_entries && !j.entries) || (j.n_pieces && !j.pieces))
         return fail(ctx, MG_E_ARG, "null argument");
-    if (sc.bound && sc.n_entries && !sc.fixed)
-        return fail(ctx, MG_E_ARG, "walk_bound: null fixed values with %u entries", sc.n_entries);
+    if (walk_bound(rung) && j.n_entries && !j.fixed)
+        return fail(ctx, MG_E_ARG, "walk_bound: null fixed values with %u entries", j.n_entries);
     if (prog->n_leaves == 0) return fail(ctx, MG_E_ARG, "walk: the program has no leaves");
     if (walkers < 1 || walkers > MG_WALK_MAX_WALKERS)
         return fail(ctx, MG_E_ARG, "walk: %u walkers outside 1..%u", walkers, MG_WALK_MAX_WALKERS);
     if (n_roots < 1 || n_roots > MG_CENSUS_MAX_ROOTS)
         return fail(ctx, MG_E_ARG, "walk: n_roots %u outside 1..%u", n_roots, MG_CENSUS_MAX_ROOTS);
-    if (sc.n_atoms > MG_WT_MAX_ATOMS)
-        return fail(ctx, MG_E_ARG, "walk_tree: %u atoms (at most %u)", sc.n_atoms,
+    if (j.n_atoms > MG_WT_MAX_ATOMS)
+        return fail(ctx, MG_E_ARG, "walk_tree: %u atoms (at most %u)", j.n_atoms,
                     MG_WT_MAX_ATOMS);
     // the root mask, then the atom mask (tree scoring), then the residuals
-    const uint32_t n_mask = (n_roots + 255) / 256, n_amask = (sc.n_atoms + 255) / 256;
+    const uint32_t n_mask = (n_roots + 255) / 256, n_amask = (j.n_atoms + 255) / 256;
     if (mask_probe0 >= prog->n_probes || n_mask > prog->n_probes - mask_probe0 ||
         n_amask > prog->n_probes - mask_probe0 - n_mask ||
         n_resid > prog->n_probes - mask_probe0 - n_mask - n_amask)
@@ -1287,36 +1279,36 @@ static int walk_check(mg_ctx* ctx, const mg_prog* prog, const uint32_t* starts, 
     if (max_rounds < 1 || max_rounds > MG_REPAIR_MAX_ROUNDS)
         return fail(ctx, MG_E_ARG, "walk: %u rounds outside 1..%u", max_rounds,
                     MG_REPAIR_MAX_ROUNDS);
-    if (sc.tree) {
-        if (!mg_walk_tree_ok(table, n_roots, sc.atoms, sc.n_atoms, sc.code, sc.n_code, n_resid))
+    if (walk_tree(rung)) {
+        if (!mg_walk_tree_ok(table, n_roots, j.atoms, j.n_atoms, j.code, j.n_code, n_resid))
             return fail(ctx, MG_E_ARG, "walk_tree: malformed tables (mg_walk_tree_ok: kinds, "
                         "atom and residual indices, offsets, stack depth, limits per root)");
     } else if (!walk_table_ok(table, n_roots, n_resid)) {
         return fail(ctx, MG_E_ARG, "walk: a table entry names an unknown kind or a residual "
                     "probe at or above %u", n_resid);
     }
-    if (sc.sum) {
+    if (walk_sum(rung)) {
         const uint32_t room = prog->n_probes - mask_probe0 - n_mask - n_amask - n_resid;
-        if (sc.n_srows > MG_SUM_MAX_ROWS || sc.n_srows > room || sc.uft.n_urows > room - sc.n_srows)
+        if (j.n_srows > MG_SUM_MAX_ROWS || j.n_srows > room || uft.n_urows > room - j.n_srows)
             return fail(ctx, MG_E_ARG, "walk_sum: %u side rows (at most %u) and %u U rows after "
-                        "%u residual probes outside the program's %u probes", sc.n_srows,
-                        MG_SUM_MAX_ROWS, sc.uft.n_urows, n_resid, prog->n_probes);
-        if (sc.n_entries && !sc.lin)
-            return fail(ctx, MG_E_ARG, "walk_sum: null lin words with %u entries", sc.n_entries);
-        if (!mg_walk_sum_ok(sc.entries, sc.n_entries, sc.pieces, sc.n_pieces, sc.fixed, sc.lin,
-                            sc.n_srows, prog->leafgen.data(), prog->n_leaves, n_resid, n_roots,
-                            sc.n_atoms, sc.uft))
+                        "%u residual probes outside the program's %u probes", j.n_srows,
+                        MG_SUM_MAX_ROWS, uft.n_urows, n_resid, prog->n_probes);
+        if (j.n_entries && !j.lin)
+            return fail(ctx, MG_E_ARG, "walk_sum: null lin words with %u entries", j.n_entries);
+        if (!mg_walk_sum_ok(j.entries, j.n_entries, j.pieces, j.n_pieces, j.fixed, j.lin,
+                            j.n_srows, prog->leafgen.data(), prog->n_leaves, n_resid, n_roots,
+                            j.n_atoms, uft))
             return fail(ctx, MG_E_ARG, "walk_sum: malformed tables (mg_walk_sum_ok: what "
                         "mg_walk_uf_ok checks; an unknown lin word, the side row of a linear XOR "
                         "entry at or above %u, a side row in a linear order entry, a slot piece "
-                        "in a linear entry, null tables)", sc.n_srows);
-    } else if (sc.uf) {
-        if (sc.uft.n_urows > prog->n_probes - mask_probe0 - n_mask - n_amask - n_resid)
+                        "in a linear entry, null tables)", j.n_srows);
+    } else if (walk_uf(rung)) {
+        if (uft.n_urows > prog->n_probes - mask_probe0 - n_mask - n_amask - n_resid)
             return fail(ctx, MG_E_ARG, "walk_uf: %u U rows after %u residual probes outside the "
-                        "program's %u probes", sc.uft.n_urows, n_resid, prog->n_probes);
-        if (!mg_walk_uf_ok(sc.entries, sc.n_entries, sc.pieces, sc.n_pieces, sc.fixed,
-                           prog->leafgen.data(), prog->n_leaves, n_resid, n_roots, sc.n_atoms,
-                           sc.uft))
+                        "program's %u probes", uft.n_urows, n_resid, prog->n_probes);
+        if (!mg_walk_uf_ok(j.entries, j.n_entries, j.pieces, j.n_pieces, j.fixed,
+                           prog->leafgen.data(), prog->n_leaves, n_resid, n_roots, j.n_atoms,
+                           uft))
             return fail(ctx, MG_E_ARG, "walk_uf: malformed tables (mg_walk_uf_ok: what "
                         "mg_walk_bound_ok checks for leaf pieces; at most %u slots, %u candidates "
                         "and %u U rows, null tables, slot, function, candidate, key and U-row "
@@ -1324,15 +1316,15 @@ static int walk_check(mg_ctx* ctx, const mg_prog* prog, const uint32_t* starts, 
                         "slot piece outside it)", MG_UF_MAX_SLOTS, MG_UF_MAX_CANDS,
                         MG_UF_MAX_ROWS, MG_UF_MAX_CHUNKS);
     }
-    if (sc.bound && !sc.uf && !mg_walk_bound_ok(sc.entries, sc.n_entries, sc.pieces, sc.n_pieces, sc.fixed,
-                                      prog->leafgen.data(), prog->n_leaves, n_resid, n_roots,
-                                      sc.n_atoms))
+    if (rung == BOUND && !mg_walk_bound_ok(j.entries, j.n_entries, j.pieces, j.n_pieces, j.fixed,
+                                           prog->leafgen.data(), prog->n_leaves, n_resid, n_roots,
+                                           j.n_atoms))
         return fail(ctx, MG_E_ARG, "walk_bound: malformed aim table (mg_walk_bound_ok: what "
                     "mg_walk_aim_ok checks, a mode above %u, a truth index outside the %u atoms "
                     "or %u roots, an XOR entry with a truth or fixed word)", MG_BOUND_HIGH_STRICT,
-                    sc.n_atoms, n_roots);
-    if (sc.aim && !sc.bound && !mg_walk_aim_ok(sc.entries, sc.n_entries, sc.pieces, sc.n_pieces,
-                                  prog->leafgen.data(), prog->n_leaves, n_resid))
+                    j.n_atoms, n_roots);
+    if (rung == AIM && !mg_walk_aim_ok(j.entries, j.n_entries, j.pieces, j.n_pieces,
+                                       prog->leafgen.data(), prog->n_leaves, n_resid))
         return fail(ctx, MG_E_ARG, "walk_aim: malformed aim table (mg_walk_aim_ok: at most %u "
                     "entries of 1..%u pieces inside the piece array, residual and leaf indices, "
                     "bit ranges inside the leaf and the residual)", MG_AIM_MAX_ENTRIES,
@@ -1346,132 +1338,101 @@ static int walk_check(mg_ctx* ctx, const mg_prog* prog, const uint32_t* starts, 
     return MG_OK;
 }
 
+// One region of walk_run's workspace: filled from src when there is one, else
+// with the byte fill (NO_FILL: left as it is); the pointer at dev, of whatever
+// type, gets the region's device address.
+struct walk_region {
+    size_t bytes;
+    const void* src;
+    int fill;
+    void* dev;
+    size_t off;
+};
+enum { NO_FILL = -1 };
+
 // The scored walk.  Rounds are queued back to back;
 // after every sync_every rounds the host reads the walkers' states (16 bytes
 // each) and stops once one of them has no failing root.
-static int walk_run(mg_ctx* ctx, const mg_prog* prog, const uint32_t* starts, uint32_t walkers,
-                    uint32_t n_roots, uint32_t mask_probe0, const walk_scoring& sc,
-                    uint32_t n_resid, uint64_t seed, uint32_t lanes, uint32_t max_rounds,
-                    uint32_t sync_every, uint32_t* out_leaves, uint32_t* out_nfail,
-                    uint32_t* out_cost, uint32_t* out_rounds, uint32_t* trace,
-                    uint32_t* out_winner) {
-    int ok = walk_check(ctx, prog, starts, walkers, n_roots, mask_probe0, sc, n_resid, lanes,
-                        max_rounds, out_leaves, out_nfail, out_cost, out_rounds, out_winner);
+static int walk_run(mg_ctx* ctx, const mg_walk_job& j, walk_rung rung, uint32_t walkers,
+                    uint32_t lanes, uint32_t max_rounds, uint32_t sync_every) {
+    int ok = walk_check(ctx, j, rung, walkers, lanes, max_rounds);
     if (ok != MG_OK) return ok;
-    const uint32_t* table = sc.table;
-    const uint32_t n_mask = (n_roots + 255) / 256, n_amask = (sc.n_atoms + 255) / 256;
+    const mg_prog* prog = j.prog;
+    const uint32_t n_roots = j.n_roots, mask_probe0 = j.mask_probe0, n_resid = j.n_resid,
+                   n_atoms = j.n_atoms, n_entries = j.n_entries, n_srows = j.n_srows;
+    const uint64_t seed = j.seed;
+    const bool tree = walk_tree(rung), aim = walk_aim(rung), bound = walk_bound(rung);
+    const uint32_t n_mask = (n_roots + 255) / 256, n_amask = (n_atoms + 255) / 256;
     const uint64_t total = (uint64_t)walkers * lanes;
     if (sync_every == 0) sync_every = 8;
     HIPCHECK(ctx, hipSetDevice(ctx->device));
-    auto align = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const uint32_t n_leaves = prog->n_leaves;
     const uint64_t words = (total + 63) / 64;
-    const size_t state_b = (size_t)walkers * sizeof(mg_walk_state),
-                 base_b = (size_t)walkers * n_leaves * 32,
-                 gen_b = (size_t)n_leaves * sizeof(mg_leafgen), table_b = (size_t)n_roots * 4,
-                 trace_b = (size_t)walkers * max_rounds * 8, root_b = words * 8,
-                 leaf_b = (size_t)n_leaves * 8 * total * 4,
-                 probe_b = (size_t)prog->n_probes * 8 * total * 4,
-                 atom_b = (size_t)sc.n_atoms * 4, code_b = (size_t)sc.n_code * 4,
-                 entry_b = (size_t)sc.n_entries * (sc.bound ? 20 : 12), piece_b = (size_t)sc.n_pieces * 16,
-                 rstate_b = sc.aim ? (size_t)walkers * n_resid * 32 : 0,
-                 live_b = sc.aim ? (size_t)walkers * MG_AIM_LIVE_WORDS * 4 : 0,
-                 fixed_b = sc.bound ? (size_t)sc.n_entries * 32 : 0,
-                 mstate_b = sc.bound ? (size_t)walkers * 4 * (MG_BOUND_MASK_WORDS(n_roots) +
-                                                              MG_BOUND_MASK_WORDS(sc.n_atoms)) : 0,
-                 slot_b = (size_t)sc.uft.n_slots * 8, func_b = (size_t)sc.uft.n_funcs * 12,
-                 cand_b = (size_t)sc.uft.n_cands * 24, ukey_b = (size_t)sc.uft.n_ukeys * 32,
-                 ustate_b = (size_t)walkers * sc.uft.n_urows * 32,
-                 dest_b = (size_t)walkers * sc.uft.n_slots * 4,
-                 lin_b = sc.bound ? (size_t)sc.n_entries * 4 : 0,
-                 sstate_b = (size_t)walkers * sc.n_srows * 32;
-    const size_t off_base = align(state_b), off_gen = off_base + align(base_b),
-                 off_table = off_gen + align(gen_b), off_trace = off_table + align(table_b),
-                 off_root = off_trace + align(trace_b), off_leaf = off_root + align(root_b),
-                 off_probe = off_leaf + align(leaf_b), off_atom = off_probe + align(probe_b),
-                 off_code = off_atom + align(atom_b), off_entry = off_code + align(code_b),
-                 off_piece = off_entry + align(entry_b), off_rstate = off_piece + align(piece_b),
-                 off_live = off_rstate + align(rstate_b), off_fixed = off_live + align(live_b),
-                 off_mstate = off_fixed + align(fixed_b), off_slot = off_mstate + align(mstate_b),
-                 off_func = off_slot + align(slot_b), off_cand = off_func + align(func_b),
-                 off_ukey = off_cand + align(cand_b), off_ustate = off_ukey + align(ukey_b),
-                 off_dest = off_ustate + align(ustate_b), off_lin = off_dest + align(dest_b),
-                 off_sstate = off_lin + align(lin_b), bytes = off_sstate + align(sstate_b);
+    const size_t w32 = (size_t)walkers * 32, state_b = (size_t)walkers * sizeof(mg_walk_state),
+                 base_b = w32 * n_leaves, trace_b = (size_t)walkers * max_rounds * 8;
+    mg_walk_state* d_state;
+    mg_leafgen* d_gen;
+    uint64_t* d_root;
+    uint32_t *d_bases, *d_table, *d_trace, *d_leaves, *d_probes, *d_atoms, *d_code, *d_entries,
+             *d_pieces, *d_rstate, *d_lives, *d_fixed, *d_mstate, *d_ustate, *d_dests, *d_lin,
+             *d_sstate;
+    // the UF tables as the kernels read them: device pointers, host counts
+    mg_uf_tables d_uf = walk_uf_tables(j);
+    // The workspace in address order, every region 256-byte aligned.  The rung
+    // decides the entry stride and which of the sum round's regions exist; a
+    // rung below SUM has no lin words, so its lin region is zero: no entry is
+    // linear.
+    walk_region reg[] = {
+        {state_b, nullptr, 0xFF, &d_state},
+        {base_b, j.starts, NO_FILL, &d_bases},
+        {(size_t)n_leaves * sizeof(mg_leafgen), prog->leafgen.data(), NO_FILL, &d_gen},
+        {(size_t)n_roots * 4, j.roots, NO_FILL, &d_table},
+        {trace_b, nullptr, 0, &d_trace},
+        {words * 8, nullptr, NO_FILL, &d_root},
+        {(size_t)n_leaves * 8 * total * 4, nullptr, NO_FILL, &d_leaves},
+        {(size_t)prog->n_probes * 8 * total * 4, nullptr, NO_FILL, &d_probes},
+        {(size_t)n_atoms * 4, j.atoms, NO_FILL, &d_atoms},
+        {(size_t)j.n_code * 4, j.code, NO_FILL, &d_code},
+        {(size_t)n_entries * (bound ? 20 : 12), j.entries, NO_FILL, &d_entries},
+        {(size_t)j.n_pieces * 16, j.pieces, NO_FILL, &d_pieces},
+        {aim ? w32 * n_resid : 0, nullptr, 0, &d_rstate},
+        {aim ? (size_t)walkers * MG_AIM_LIVE_WORDS * 4 : 0, nullptr, 0, &d_lives},
+        {bound ? (size_t)n_entries * 32 : 0, j.fixed, NO_FILL, &d_fixed},
+        {bound ? (size_t)walkers * 4 * (MG_BOUND_MASK_WORDS(n_roots) +
+                                        MG_BOUND_MASK_WORDS(n_atoms)) : 0, nullptr, 0, &d_mstate},
+        {(size_t)j.n_slots * 8, j.slots, NO_FILL, &d_uf.slots},
+        {(size_t)j.n_funcs * 12, j.funcs, NO_FILL, &d_uf.funcs},
+        {(size_t)j.n_cands * 24, j.cands, NO_FILL, &d_uf.cands},
+        {(size_t)j.n_ukeys * 32, j.ukeys, NO_FILL, &d_uf.ukeys},
+        {w32 * j.n_urows, nullptr, 0, &d_ustate},
+        {(size_t)walkers * j.n_slots * 4, nullptr, 0xFF, &d_dests},
+        {bound ? (size_t)n_entries * 4 : 0, j.lin, 0, &d_lin},
+        {w32 * n_srows, nullptr, 0, &d_sstate},
+    };
+    const size_t n_reg = sizeof reg / sizeof reg[0];
+    size_t bytes = 0;
+    for (walk_region& g : reg) {
+        g.off = bytes;
+        bytes += (g.bytes + 255) & ~(size_t)255;
+    }
     void* ws;
     int rc = workspace(ctx, bytes + 256, &ws);
     if (rc) return rc;
     uint8_t* w = (uint8_t*)ws;
-    mg_walk_state* d_state = (mg_walk_state*)w;
-    uint32_t* d_bases = (uint32_t*)(w + off_base);
-    mg_leafgen* d_gen = (mg_leafgen*)(w + off_gen);
-    uint32_t* d_table = (uint32_t*)(w + off_table);
-    uint32_t* d_trace = (uint32_t*)(w + off_trace);
-    uint32_t* d_leaves = (uint32_t*)(w + off_leaf);
-    uint32_t* d_probes = (uint32_t*)(w + off_probe);
-    uint32_t* d_atoms = (uint32_t*)(w + off_atom);
-    uint32_t* d_code = (uint32_t*)(w + off_code);
-    uint32_t* d_entries = (uint32_t*)(w + off_entry);
-    uint32_t* d_pieces = (uint32_t*)(w + off_piece);
-    uint32_t* d_rstate = (uint32_t*)(w + off_rstate);
-    uint32_t* d_lives = (uint32_t*)(w + off_live);
-    uint32_t* d_fixed = (uint32_t*)(w + off_fixed);
-    uint32_t* d_mstate = (uint32_t*)(w + off_mstate);
-    uint32_t* d_ustate = (uint32_t*)(w + off_ustate);
-    uint32_t* d_dests = (uint32_t*)(w + off_dest);
-    uint32_t* d_lin = (uint32_t*)(w + off_lin);
-    uint32_t* d_sstate = (uint32_t*)(w + off_sstate);
-    // the UF tables as the kernels read them: device pointers, host counts
-    mg_uf_tables d_uf = sc.uft;
-    d_uf.slots = (const uint32_t*)(w + off_slot);
-    d_uf.funcs = (const uint32_t*)(w + off_func);
-    d_uf.cands = (const uint32_t*)(w + off_cand);
-    d_uf.ukeys = (const uint32_t*)(w + off_ukey);
-    HIPCHECK(ctx, hipMemsetAsync(d_state, 0xFF, state_b, ctx->stream));
-    HIPCHECK(ctx, hipMemsetAsync(d_trace, 0, trace_b, ctx->stream));
-    HIPCHECK(ctx, hipMemcpyAsync(d_bases, starts, base_b, hipMemcpyHostToDevice, ctx->stream));
-    HIPCHECK(ctx, hipMemcpyAsync(d_gen, prog->leafgen.data(), gen_b, hipMemcpyHostToDevice,
-                                 ctx->stream));
-    HIPCHECK(ctx, hipMemcpyAsync(d_table, table, table_b, hipMemcpyHostToDevice, ctx->stream));
-    if (atom_b)
-        HIPCHECK(ctx, hipMemcpyAsync(d_atoms, sc.atoms, atom_b, hipMemcpyHostToDevice,
-                                     ctx->stream));
-    if (code_b)
-        HIPCHECK(ctx, hipMemcpyAsync(d_code, sc.code, code_b, hipMemcpyHostToDevice,
-                                     ctx->stream));
-    if (entry_b)
-        HIPCHECK(ctx, hipMemcpyAsync(d_entries, sc.entries, entry_b, hipMemcpyHostToDevice,
-                                     ctx->stream));
-    if (piece_b)
-        HIPCHECK(ctx, hipMemcpyAsync(d_pieces, sc.pieces, piece_b, hipMemcpyHostToDevice,
-                                     ctx->stream));
-    if (rstate_b) HIPCHECK(ctx, hipMemsetAsync(d_rstate, 0, rstate_b, ctx->stream));
-    if (live_b) HIPCHECK(ctx, hipMemsetAsync(d_lives, 0, live_b, ctx->stream));
-    if (fixed_b)
-        HIPCHECK(ctx, hipMemcpyAsync(d_fixed, sc.fixed, fixed_b, hipMemcpyHostToDevice,
-                                     ctx->stream));
-    if (mstate_b) HIPCHECK(ctx, hipMemsetAsync(d_mstate, 0, mstate_b, ctx->stream));
-    if (slot_b)
-        HIPCHECK(ctx, hipMemcpyAsync(w + off_slot, sc.uft.slots, slot_b, hipMemcpyHostToDevice,
-                                     ctx->stream));
-    if (func_b)
-        HIPCHECK(ctx, hipMemcpyAsync(w + off_func, sc.uft.funcs, func_b, hipMemcpyHostToDevice,
-                                     ctx->stream));
-    if (cand_b)
-        HIPCHECK(ctx, hipMemcpyAsync(w + off_cand, sc.uft.cands, cand_b, hipMemcpyHostToDevice,
-                                     ctx->stream));
-    if (ukey_b)
-        HIPCHECK(ctx, hipMemcpyAsync(w + off_ukey, sc.uft.ukeys, ukey_b, hipMemcpyHostToDevice,
-                                     ctx->stream));
-    if (ustate_b) HIPCHECK(ctx, hipMemsetAsync(d_ustate, 0, ustate_b, ctx->stream));
-    if (dest_b) HIPCHECK(ctx, hipMemsetAsync(d_dests, 0xFF, dest_b, ctx->stream));
-    if (lin_b && sc.lin)
-        HIPCHECK(ctx, hipMemcpyAsync(d_lin, sc.lin, lin_b, hipMemcpyHostToDevice, ctx->stream));
-    else if (lin_b)                                       // a lower rung: no entry is linear
-        HIPCHECK(ctx, hipMemsetAsync(d_lin, 0, lin_b, ctx->stream));
-    if (sstate_b) HIPCHECK(ctx, hipMemsetAsync(d_sstate, 0, sstate_b, ctx->stream));
+    // queued in address order, but for the trace's fill, which follows the state's
+    static const uint8_t first[] = {0, 4, 1, 2, 3};
+    for (size_t k = 0; k < n_reg; ++k) {
+        const walk_region& g = reg[k < sizeof first ? first[k] : k];
+        uint8_t* d = w + g.off;
+        memcpy(g.dev, &d, sizeof d);
+        if (g.bytes && g.src)
+            HIPCHECK(ctx, hipMemcpyAsync(d, g.src, g.bytes, hipMemcpyHostToDevice, ctx->stream));
+        else if (g.bytes && g.fill != NO_FILL)
+            HIPCHECK(ctx, hipMemsetAsync(d, g.fill, g.bytes, ctx->stream));
+    }
     mg_run run = empty_run();
     run.leaves = d_leaves;
-    run.root_bits = (uint64_t*)(w + off_root);
+    run.root_bits = d_root;
     run.probes = d_probes;
     run.stride = total;
     run.n_assign = total;
@@ -1479,7 +1440,6 @@ static int walk_run(mg_ctx* ctx, const mg_prog* prog, const uint32_t* starts, ui
     const uint32_t* d_masks = d_probes + (size_t)mask_probe0 * 8 * total;
     const uint32_t* d_amasks = d_masks + (size_t)n_mask * 8 * total;
     const uint32_t* d_resid = d_amasks + (size_t)n_amask * 8 * total;
-    const uint32_t n_srows = sc.n_srows;
     const uint32_t* d_srows = d_resid + (size_t)n_resid * 8 * total;
     const uint32_t* d_urows = d_srows + (size_t)n_srows * 8 * total;
     const uint32_t* d_consts = prog->h_desc.consts;       // the first n_consts entries: as loaded
@@ -1490,38 +1450,38 @@ static int walk_run(mg_ctx* ctx, const mg_prog* prog, const uint32_t* starts, ui
     while (r < max_rounds && !done) {
         const uint32_t stop = max_rounds - r < sync_every ? max_rounds : r + sync_every;
         for (; r < stop; ++r) {
-            if (sc.bound)                      // mg_walk_bound, mg_walk_uf, mg_walk_sum
+            if (bound)                      // mg_walk_bound, mg_walk_uf, mg_walk_sum
                 HIPCHECK(ctx, mg_launch_walk_sum_round(d_bases, d_gen, d_consts, n_leaves, seed,
-                                                       r, lanes, walkers, d_entries, sc.n_entries,
+                                                       r, lanes, walkers, d_entries, n_entries,
                                                        d_pieces, d_fixed, d_lin, d_rstate, n_resid,
                                                        d_sstate, n_srows, d_lives, d_dests,
                                                        d_uf.n_slots, d_leaves, ctx->stream));
-            else if (sc.aim)
+            else if (aim)
                 HIPCHECK(ctx, mg_launch_walk_aim_round(d_bases, d_gen, d_consts, n_leaves, seed, r,
-                                                       lanes, walkers, d_entries, sc.n_entries,
+                                                       lanes, walkers, d_entries, n_entries,
                                                        d_pieces, d_rstate, n_resid, d_lives,
                                                        d_leaves, ctx->stream));
             else
                 HIPCHECK(ctx, mg_launch_walk_round(d_bases, d_gen, d_consts, n_leaves, seed, r,
                                                    lanes, walkers, d_leaves, ctx->stream));
             HIPCHECK(ctx, launch(ctx, 0, prog->d_desc, 1, run, prog->n_lds, ctx->stream));
-            if (sc.bound)
+            if (bound)
                 HIPCHECK(ctx, mg_launch_walk_sum_pick(d_masks, d_amasks, d_resid, d_srows, n_srows,
                                                       d_urows, d_table, d_atoms, d_code, lanes,
-                                                      walkers, n_roots, sc.n_atoms, d_bases, d_gen,
+                                                      walkers, n_roots, n_atoms, d_bases, d_gen,
                                                       d_consts, n_leaves, seed, r, max_rounds,
-                                                      d_entries, sc.n_entries, d_pieces, d_fixed,
+                                                      d_entries, n_entries, d_pieces, d_fixed,
                                                       d_lin, n_resid, d_uf, d_rstate, d_mstate,
                                                       d_sstate, d_ustate, d_dests, d_lives,
                                                       d_state, d_trace, ctx->stream));
-            else if (sc.aim)
+            else if (aim)
                 HIPCHECK(ctx, mg_launch_walk_aim_pick(d_masks, d_amasks, d_resid, d_table, d_atoms,
                                                       d_code, lanes, walkers, n_roots, d_bases,
                                                       d_gen, d_consts, n_leaves, seed, r,
-                                                      max_rounds, d_entries, sc.n_entries,
+                                                      max_rounds, d_entries, n_entries,
                                                       d_pieces, n_resid, d_rstate, d_lives,
                                                       d_state, d_trace, ctx->stream));
-            else if (sc.tree)
+            else if (tree)
                 HIPCHECK(ctx, mg_launch_walk_tree_pick(d_masks, d_amasks, d_resid, d_table,
                                                        d_atoms, d_code, lanes, walkers, n_roots,
                                                        d_bases, d_gen, d_consts, n_leaves, seed,
@@ -1540,32 +1500,39 @@ static int walk_run(mg_ctx* ctx, const mg_prog* prog, const uint32_t* starts, ui
         for (uint32_t k = 0; k < walkers; ++k) done = done || h_state[k].nfail == 0;
     }
     timing_read(ctx);
-    HIPCHECK(ctx, hipMemcpyAsync(out_leaves, d_bases, base_b, hipMemcpyDeviceToHost, ctx->stream));
-    if (trace)
-        HIPCHECK(ctx, hipMemcpyAsync(trace, d_trace, trace_b, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHECK(ctx, hipMemcpyAsync(j.out_leaves, d_bases, base_b, hipMemcpyDeviceToHost, ctx->stream));
+    if (j.trace)
+        HIPCHECK(ctx, hipMemcpyAsync(j.trace, d_trace, trace_b, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
     uint32_t win = 0;
     for (uint32_t k = 0; k < walkers; ++k) {
-        out_nfail[k] = h_state[k].nfail;
-        out_cost[k] = h_state[k].cost;
+        j.out_nfail[k] = h_state[k].nfail;
+        j.out_cost[k] = h_state[k].cost;
         if (h_state[k].nfail < h_state[win].nfail ||
             (h_state[k].nfail == h_state[win].nfail && h_state[k].cost < h_state[win].cost))
             win = k;
     }
-    *out_rounds = r;
-    *out_winner = win;
+    *j.out_rounds = r;
+    *j.out_winner = win;
     return MG_OK;
 }
+
+// A zeroed job j with the fields that every walk entry takes, under the job's
+// own names; the entry adds its rung's tables.
+#define WALK_JOB(j)                                                                         \
+    mg_walk_job j = {};                                                                     \
+    j.prog = prog, j.starts = starts, j.n_roots = n_roots, j.mask_probe0 = mask_probe0;     \
+    j.n_resid = n_resid, j.seed = seed, j.out_leaves = out_leaves, j.out_nfail = out_nfail; \
+    j.out_cost = out_cost, j.out_rounds = out_rounds, j.trace = trace, j.out_winner = out_winner
 
 int mg_walk(mg_ctx* ctx, const mg_prog* prog, const uint32_t* starts, uint32_t walkers,
             uint32_t n_roots, uint32_t mask_probe0, const uint32_t* table, uint32_t n_resid,
             uint64_t seed, uint32_t lanes, uint32_t max_rounds, uint32_t sync_every,
             uint32_t* out_leaves, uint32_t* out_nfail, uint32_t* out_cost, uint32_t* out_rounds,
             uint32_t* trace, uint32_t* out_winner) {
-    const walk_scoring sc = {table, nullptr, 0, nullptr, 0, false};
-    return walk_run(ctx, prog, starts, walkers, n_roots, mask_probe0, sc, n_resid, seed, lanes,
-                    max_rounds, sync_every, out_leaves, out_nfail, out_cost, out_rounds, trace,
-                    out_winner);
+    WALK_JOB(j);
+    j.roots = table;
+    return walk_run(ctx, j, TABLE, walkers, lanes, max_rounds, sync_every);
 }
 
 // The scored walk with tree distances: mg_walk with the
@@ -1576,10 +1543,9 @@ int mg_walk_tree(mg_ctx* ctx, const mg_prog* prog, const uint32_t* starts, uint3
                  uint64_t seed, uint32_t lanes, uint32_t max_rounds, uint32_t sync_every,
                  uint32_t* out_leaves, uint32_t* out_nfail, uint32_t* out_cost,
                  uint32_t* out_rounds, uint32_t* trace, uint32_t* out_winner) {
-    const walk_scoring sc = {roots, atoms, n_atoms, code, n_code, true};
-    return walk_run(ctx, prog, starts, walkers, n_roots, mask_probe0, sc, n_resid, seed, lanes,
-                    max_rounds, sync_every, out_leaves, out_nfail, out_cost, out_rounds, trace,
-                    out_winner);
+    WALK_JOB(j);
+    j.roots = roots, j.atoms = atoms, j.n_atoms = n_atoms, j.code = code, j.n_code = n_code;
+    return walk_run(ctx, j, TREE, walkers, lanes, max_rounds, sync_every);
 }
 
 // The tree-scored walk with aimed moves: mg_walk_tree with
@@ -1591,11 +1557,10 @@ int mg_walk_aim(mg_ctx* ctx, const mg_prog* prog, const uint32_t* starts, uint32
                 uint32_t n_pieces, uint64_t seed, uint32_t lanes, uint32_t max_rounds,
                 uint32_t sync_every, uint32_t* out_leaves, uint32_t* out_nfail,
                 uint32_t* out_cost, uint32_t* out_rounds, uint32_t* trace, uint32_t* out_winner) {
-    const walk_scoring sc = {roots, atoms, n_atoms, code, n_code, true, true,
-                             entries, n_entries, pieces, n_pieces};
-    return walk_run(ctx, prog, starts, walkers, n_roots, mask_probe0, sc, n_resid, seed, lanes,
-                    max_rounds, sync_every, out_leaves, out_nfail, out_cost, out_rounds, trace,
-                    out_winner);
+    WALK_JOB(j);
+    j.roots = roots, j.atoms = atoms, j.n_atoms = n_atoms, j.code = code, j.n_code = n_code;
+    j.entries = entries, j.n_entries = n_entries, j.pieces = pieces, j.n_pieces = n_pieces;
+    return walk_run(ctx, j, AIM, walkers, lanes, max_rounds, sync_every);
 }
 
 // The tree-scored walk with moves aimed by equalities and orders (DESIGN.md
@@ -1609,11 +1574,11 @@ int mg_walk_bound(mg_ctx* ctx, const mg_prog* prog, const uint32_t* starts, uint
                   uint32_t max_rounds, uint32_t sync_every, uint32_t* out_leaves,
                   uint32_t* out_nfail, uint32_t* out_cost, uint32_t* out_rounds, uint32_t* trace,
                   uint32_t* out_winner) {
-    const walk_scoring sc = {roots, atoms, n_atoms, code, n_code, true, true,
-                             entries, n_entries, pieces, n_pieces, true, fixed};
-    return walk_run(ctx, prog, starts, walkers, n_roots, mask_probe0, sc, n_resid, seed, lanes,
-                    max_rounds, sync_every, out_leaves, out_nfail, out_cost, out_rounds, trace,
-                    out_winner);
+    WALK_JOB(j);
+    j.roots = roots, j.atoms = atoms, j.n_atoms = n_atoms, j.code = code, j.n_code = n_code;
+    j.entries = entries, j.n_entries = n_entries, j.pieces = pieces, j.n_pieces = n_pieces;
+    j.fixed = fixed;
+    return walk_run(ctx, j, BOUND, walkers, lanes, max_rounds, sync_every);
 }
 
 // The same with aims that write the table entry a UF application reads
@@ -1630,13 +1595,13 @@ int mg_walk_uf(mg_ctx* ctx, const mg_prog* prog, const uint32_t* starts, uint32_
                uint32_t* out_nfail, uint32_t* out_cost, uint32_t* out_rounds, uint32_t* trace,
                uint32_t* out_winner) {
     if (ctx) HIPCHECK(ctx, hipSetDevice(ctx->device));
-    const walk_scoring sc = {roots, atoms, n_atoms, code, n_code, true, true,
-                             entries, n_entries, pieces, n_pieces, true, fixed, true,
-                             {slots, n_slots, funcs, n_funcs, cands, n_cands, ukeys, n_ukeys,
-                              n_urows}};
-    return walk_run(ctx, prog, starts, walkers, n_roots, mask_probe0, sc, n_resid, seed, lanes,
-                    max_rounds, sync_every, out_leaves, out_nfail, out_cost, out_rounds, trace,
-                    out_winner);
+    WALK_JOB(j);
+    j.roots = roots, j.atoms = atoms, j.n_atoms = n_atoms, j.code = code, j.n_code = n_code;
+    j.entries = entries, j.n_entries = n_entries, j.pieces = pieces, j.n_pieces = n_pieces;
+    j.fixed = fixed, j.n_urows = n_urows;
+    j.slots = slots, j.n_slots = n_slots, j.funcs = funcs, j.n_funcs = n_funcs;
+    j.cands = cands, j.n_cands = n_cands, j.ukeys = ukeys, j.n_ukeys = n_ukeys;
+    return walk_run(ctx, j, UF, walkers, lanes, max_rounds, sync_every);
 }
 
 // The same with aims through sums, differences, masks and shifts (DESIGN.md
@@ -1653,13 +1618,13 @@ int mg_walk_sum(mg_ctx* ctx, const mg_prog* prog, const uint32_t* starts, uint32
                 uint32_t sync_every, uint32_t* out_leaves, uint32_t* out_nfail,
                 uint32_t* out_cost, uint32_t* out_rounds, uint32_t* trace, uint32_t* out_winner) {
     if (ctx) HIPCHECK(ctx, hipSetDevice(ctx->device));
-    const walk_scoring sc = {roots, atoms, n_atoms, code, n_code, true, true,
-                             entries, n_entries, pieces, n_pieces, true, fixed, true,
-                             {slots, n_slots, funcs, n_funcs, cands, n_cands, ukeys, n_ukeys,
-                              n_urows}, true, lin, n_srows};
-    return walk_run(ctx, prog, starts, walkers, n_roots, mask_probe0, sc, n_resid, seed, lanes,
-                    max_rounds, sync_every, out_leaves, out_nfail, out_cost, out_rounds, trace,
-                    out_winner);
+    WALK_JOB(j);
+    j.roots = roots, j.atoms = atoms, j.n_atoms = n_atoms, j.code = code, j.n_code = n_code;
+    j.entries = entries, j.n_entries = n_entries, j.pieces = pieces, j.n_pieces = n_pieces;
+    j.fixed = fixed, j.lin = lin, j.n_srows = n_srows, j.n_urows = n_urows;
+    j.slots = slots, j.n_slots = n_slots, j.funcs = funcs, j.n_funcs = n_funcs;
+    j.cands = cands, j.n_cands = n_cands, j.ukeys = ukeys, j.n_ukeys = n_ukeys;
+    return walk_run(ctx, j, SUM, walkers, lanes, max_rounds, sync_every);
 }
 
 // The walks of several groups in one launch sequence (DESIGN.md §3.16,
@@ -1710,13 +1675,7 @@ int mg_walk_batch(mg_ctx* ctx, const mg_walk_job* jobs, uint32_t n_jobs, uint32_
                         "output pointer", g);
         if (j.prog->ctx != ctx)
             return fail(ctx, MG_E_ARG, "walk_batch: job %u: a program of another context", g);
-        const walk_scoring sc = {j.roots, j.atoms, j.n_atoms, j.code, j.n_code, true, true,
-                                 j.entries, j.n_entries, j.pieces, j.n_pieces, true, j.fixed, true,
-                                 {j.slots, j.n_slots, j.funcs, j.n_funcs, j.cands, j.n_cands,
-                                  j.ukeys, j.n_ukeys, j.n_urows}, true, j.lin, j.n_srows};
-        if (walk_check(ctx, j.prog, j.starts, walkers, j.n_roots, j.mask_probe0, sc, j.n_resid,
-                       lanes, max_rounds, j.out_leaves, j.out_nfail, j.out_cost, j.out_rounds,
-                       j.out_winner) != MG_OK) {
+        if (walk_check(ctx, j, SUM, walkers, lanes, max_rounds) != MG_OK) {
             const std::string why = ctx->err;
             return fail(ctx, MG_E_ARG, "walk_batch: job %u: %s", g, why.c_str());
         }

@@ -91,6 +91,10 @@ _WALK_COUNTS = ("n_roots", "mask_probe0", "n_atoms", "n_code", "n_resid", "n_ent
                 "n_srows", "n_slots", "n_funcs", "n_cands", "n_ukeys", "n_urows")
 
 
+_WALK_TABLES = ("starts", "roots", "atoms", "code", "entries", "pieces", "fixed", "lin", "slots",
+                "funcs", "cands", "ukeys")
+
+
 class WalkJob(C.Structure):
     """mg_walk_job (include/mythgpu.h): one job of mg_walk_batch."""
     _fields_ = [(n, C.c_void_p) for n in (
@@ -566,7 +570,6 @@ class Engine:
         its verdict mask as probes ``mask_probe0``.. and ``n_resid`` residual
         probes right after it (``repair.residuals``, whose ``table`` says
         which root reads which): a :class:`mythril_amd.repair.WalkResult`."""
-        from .repair import WalkResult
         n_leaves = len(lp.program.leaves)
         starts = np.ascontiguousarray(starts, dtype=np.uint32)
         if starts.ndim != 3 or starts.shape[1:] != (n_leaves, 8):
@@ -575,11 +578,8 @@ class Engine:
         table = np.ascontiguousarray(table, dtype=np.uint32)
         if table.shape != (max(0, int(n_roots)),) and 1 <= int(n_roots) <= 1024:
             raise ValueError("table must have n_roots entries")
-        w1, r1 = max(1, min(walkers, 64)), max(1, min(int(max_rounds), 1 << 16))
-        out = np.zeros((w1, max(1, n_leaves), 8), dtype=np.uint32)
-        nfail, cost = np.zeros(w1, dtype=np.uint32), np.zeros(w1, dtype=np.uint32)
-        trace = np.zeros((w1, r1, 2), dtype=np.uint32)
-        rounds, winner = C.c_uint32(0), C.c_uint32(0)
+        bufs = out, nfail, cost, trace, rounds, winner = _walk_outputs(walkers, n_leaves,
+                                                                       max_rounds)
         rc = self.lib.mg_walk(self._ctx, lp.handle, _ptr(starts) if starts.size else _ptr(out),
                               walkers, max(0, int(n_roots)), mask_probe0,
                               _ptr(table) if table.size else _ptr(nfail), max(0, int(n_resid)),
@@ -587,8 +587,7 @@ class Engine:
                               _ptr(nfail), _ptr(cost), C.byref(rounds), _ptr(trace),
                               C.byref(winner))
         self._check(rc, "mg_walk")
-        return WalkResult(out[:, :n_leaves], nfail.astype(np.int64), cost.astype(np.int64),
-                          int(rounds.value), trace, int(winner.value), self.last_kernel_ms())
+        return _walk_result(bufs, n_leaves, self.last_kernel_ms())
 
     def walk_tree(self, lp: LoadedProgram, starts: np.ndarray, n_roots: int, trees, seed: int,
                   lanes: int = 4096, max_rounds: int = 64, sync_every: int = 8,
@@ -599,35 +598,8 @@ class Engine:
         (``repair.distance_trees``; ``n_resid``: how many residual probes the
         program has, by default the trees'): a
         :class:`mythril_amd.repair.WalkResult`."""
-        from .repair import WalkResult
-        n_leaves = len(lp.program.leaves)
-        starts = np.ascontiguousarray(starts, dtype=np.uint32)
-        if starts.ndim != 3 or starts.shape[1:] != (n_leaves, 8):
-            raise ValueError("starts must be (walkers, n_leaves, 8)")
-        walkers = starts.shape[0]
-        roots = np.ascontiguousarray(trees.roots, dtype=np.uint32)
-        atoms = np.ascontiguousarray(trees.atoms, dtype=np.uint32)
-        code = np.ascontiguousarray(trees.code, dtype=np.uint32)
-        if roots.shape != (max(0, int(n_roots)),) and 1 <= int(n_roots) <= 1024:
-            raise ValueError("trees.roots must have n_roots entries")
-        n_resid = len(trees.probes) if n_resid is None else n_resid
-        w1, r1 = max(1, min(walkers, 64)), max(1, min(int(max_rounds), 1 << 16))
-        out = np.zeros((w1, max(1, n_leaves), 8), dtype=np.uint32)
-        nfail, cost = np.zeros(w1, dtype=np.uint32), np.zeros(w1, dtype=np.uint32)
-        trace = np.zeros((w1, r1, 2), dtype=np.uint32)
-        rounds, winner = C.c_uint32(0), C.c_uint32(0)
-        rc = self.lib.mg_walk_tree(self._ctx, lp.handle,
-                                   _ptr(starts) if starts.size else _ptr(out), walkers,
-                                   max(0, int(n_roots)), mask_probe0,
-                                   _ptr(roots) if roots.size else _ptr(nfail), atoms.size,
-                                   _ptr(atoms) if atoms.size else None,
-                                   _ptr(code) if code.size else None, code.size,
-                                   max(0, int(n_resid)), seed & (2**64 - 1), lanes, max_rounds,
-                                   sync_every, _ptr(out), _ptr(nfail), _ptr(cost),
-                                   C.byref(rounds), _ptr(trace), C.byref(winner))
-        self._check(rc, "mg_walk_tree")
-        return WalkResult(out[:, :n_leaves], nfail.astype(np.int64), cost.astype(np.int64),
-                          int(rounds.value), trace, int(winner.value), self.last_kernel_ms())
+        q = _pack_walk(lp, starts, n_roots, trees, mask_probe0=mask_probe0, n_resid=n_resid)
+        return self._walk_rung("mg_walk_tree", lp, q, seed, lanes, max_rounds, sync_every)
 
     def walk_aim(self, lp: LoadedProgram, starts: np.ndarray, n_roots: int, trees, aims, seed: int,
                  lanes: int = 4096, max_rounds: int = 64, sync_every: int = 8,
@@ -636,93 +608,40 @@ class Engine:
         :meth:`walk_tree` with the aim table ``aims`` (``repair.aim_table``:
         ``entries`` (n, 3) and ``pieces`` (m, 4) u32); with no entry it is
         :meth:`walk_tree` bit for bit."""
-        from .repair import WalkResult
-        n_leaves = len(lp.program.leaves)
-        starts = np.ascontiguousarray(starts, dtype=np.uint32)
-        if starts.ndim != 3 or starts.shape[1:] != (n_leaves, 8):
-            raise ValueError("starts must be (walkers, n_leaves, 8)")
-        walkers = starts.shape[0]
-        roots = np.ascontiguousarray(trees.roots, dtype=np.uint32)
-        atoms = np.ascontiguousarray(trees.atoms, dtype=np.uint32)
-        code = np.ascontiguousarray(trees.code, dtype=np.uint32)
-        if roots.shape != (max(0, int(n_roots)),) and 1 <= int(n_roots) <= 1024:
-            raise ValueError("trees.roots must have n_roots entries")
-        entries = np.ascontiguousarray(aims.entries, dtype=np.uint32)
-        pieces = np.ascontiguousarray(aims.pieces, dtype=np.uint32)
-        if entries.shape[1:] != (3,) or pieces.shape[1:] != (4,):
-            raise ValueError("aims.entries must be (n, 3), aims.pieces (m, 4)")
-        n_resid = len(trees.probes) if n_resid is None else n_resid
-        w1, r1 = max(1, min(walkers, 64)), max(1, min(int(max_rounds), 1 << 16))
-        out = np.zeros((w1, max(1, n_leaves), 8), dtype=np.uint32)
-        nfail, cost = np.zeros(w1, dtype=np.uint32), np.zeros(w1, dtype=np.uint32)
-        trace = np.zeros((w1, r1, 2), dtype=np.uint32)
-        rounds, winner = C.c_uint32(0), C.c_uint32(0)
-        rc = self.lib.mg_walk_aim(self._ctx, lp.handle,
-                                  _ptr(starts) if starts.size else _ptr(out), walkers,
-                                  max(0, int(n_roots)), mask_probe0,
-                                  _ptr(roots) if roots.size else _ptr(nfail), atoms.size,
-                                  _ptr(atoms) if atoms.size else None,
-                                  _ptr(code) if code.size else None, code.size,
-                                  max(0, int(n_resid)),
-                                  _ptr(entries) if entries.size else None, entries.shape[0],
-                                  _ptr(pieces) if pieces.size else None, pieces.shape[0],
-                                  seed & (2**64 - 1), lanes, max_rounds, sync_every, _ptr(out),
-                                  _ptr(nfail), _ptr(cost), C.byref(rounds), _ptr(trace),
-                                  C.byref(winner))
-        self._check(rc, "mg_walk_aim")
-        return WalkResult(out[:, :n_leaves], nfail.astype(np.int64), cost.astype(np.int64),
-                          int(rounds.value), trace, int(winner.value), self.last_kernel_ms())
+        q = _pack_walk(lp, starts, n_roots, trees, aims=aims, mask_probe0=mask_probe0,
+                       n_resid=n_resid)
+        return self._walk_rung("mg_walk_aim", lp, q, seed, lanes, max_rounds, sync_every)
 
-    def _walk_rung(self, name: str, lp: LoadedProgram, starts: np.ndarray, n_roots: int, trees,
-                   bounds, ufs, sums, seed: int, lanes: int, max_rounds: int, sync_every: int,
-                   mask_probe0: int, n_resid: Optional[int]):
-        """What :meth:`walk_bound`, :meth:`walk_uf` and :meth:`walk_sum` share:
-        the arrays, the result buffers and the call of the C entry ``name``,
-        whose argument list has the lin words and side rows when ``sums`` is
-        given and the UF tables and U rows when ``ufs`` is."""
-        from .repair import WalkResult
-        n_leaves = len(lp.program.leaves)
-        starts = np.ascontiguousarray(starts, dtype=np.uint32)
-        if starts.ndim != 3 or starts.shape[1:] != (n_leaves, 8):
-            raise ValueError("starts must be (walkers, n_leaves, 8)")
-        walkers = starts.shape[0]
-        roots = np.ascontiguousarray(trees.roots, dtype=np.uint32)
-        atoms = np.ascontiguousarray(trees.atoms, dtype=np.uint32)
-        code = np.ascontiguousarray(trees.code, dtype=np.uint32)
-        if roots.shape != (max(0, int(n_roots)),) and 1 <= int(n_roots) <= 1024:
-            raise ValueError("trees.roots must have n_roots entries")
-        entries = np.ascontiguousarray(bounds.entries, dtype=np.uint32)
-        pieces = np.ascontiguousarray(bounds.pieces, dtype=np.uint32)
-        fixed = np.ascontiguousarray(bounds.fixed, dtype=np.uint32)
-        lin = None if sums is None else np.ascontiguousarray(sums.lin, dtype=np.uint32)
-        if entries.shape[1:] != (5,) or pieces.shape[1:] != (4,) or \
-                fixed.shape != (entries.shape[0], 8) or \
-                (lin is not None and lin.shape != (entries.shape[0],)):
-            raise ValueError("bounds.entries must be (n, 5), bounds.pieces (m, 4), "
-                             "bounds.fixed (n, 8)" + ("" if sums is None else ", sums.lin (n,)"))
-        tabs = None if ufs is None else _uf_arrays(ufs)
-        n_resid = len(trees.probes) if n_resid is None else n_resid
-        w1, r1 = max(1, min(walkers, 64)), max(1, min(int(max_rounds), 1 << 16))
-        out = np.zeros((w1, max(1, n_leaves), 8), dtype=np.uint32)
-        nfail, cost = np.zeros(w1, dtype=np.uint32), np.zeros(w1, dtype=np.uint32)
-        trace = np.zeros((w1, r1, 2), dtype=np.uint32)
-        rounds, winner = C.c_uint32(0), C.c_uint32(0)
-        args = [self._ctx, lp.handle, _ptr(starts) if starts.size else _ptr(out), walkers,
-                max(0, int(n_roots)), mask_probe0, _ptr(roots) if roots.size else _ptr(nfail),
-                atoms.size, _ptr(atoms) if atoms.size else None,
-                _ptr(code) if code.size else None, code.size, max(0, int(n_resid)),
-                _ptr(entries) if entries.size else None, entries.shape[0],
-                _ptr(pieces) if pieces.size else None, pieces.shape[0],
-                _ptr(fixed) if fixed.size else None]
-        if sums is not None:
-            args += [_ptr(lin) if lin.size else None, max(0, int(sums.n_srows))]
-        if ufs is not None:
-            args += [*_uf_args(tabs), max(0, int(ufs.n_urows))]
+    def _walk_rung(self, name: str, lp: LoadedProgram, q: dict, seed: int, lanes: int,
+                   max_rounds: int, sync_every: int):
+        """What the tree-scored walks share: the result buffers and the call of
+        the C entry ``name`` on the arrays ``q`` of :func:`_pack_walk`.  The
+        entry's argument list has the tables that were packed: the aim or
+        bound table, the fixed values, the lin words with the side rows, the
+        UF tables with the U rows."""
+        s = q["shape"]
+        walkers = q["starts"].shape[0]
+        bufs = out, nfail, cost, trace, rounds, winner = _walk_outputs(walkers, s.n_leaves,
+                                                                       max_rounds)
+
+        def ptr(name, empty=None):
+            return _ptr(q[name]) if q[name].size else empty
+
+        args = [self._ctx, lp.handle, ptr("starts", _ptr(out)), walkers, s.n_roots, s.mask_probe0,
+                ptr("roots", _ptr(nfail)), s.n_atoms, ptr("atoms"), ptr("code"), s.n_code,
+                s.n_resid]
+        if q["entries"] is not None:
+            args += [ptr("entries"), s.n_entries, ptr("pieces"), s.n_pieces]
+        if q["fixed"] is not None:
+            args += [ptr("fixed")]
+        if q["lin"] is not None:
+            args += [ptr("lin"), s.n_srows]
+        if q["slots"] is not None:
+            args += [*_uf_args([q[k] for k in ("slots", "funcs", "cands", "ukeys")]), s.n_urows]
         args += [seed & (2**64 - 1), lanes, max_rounds, sync_every, _ptr(out), _ptr(nfail),
                  _ptr(cost), C.byref(rounds), _ptr(trace), C.byref(winner)]
         self._check(getattr(self.lib, name)(*args), name)
-        return WalkResult(out[:, :n_leaves], nfail.astype(np.int64), cost.astype(np.int64),
-                          int(rounds.value), trace, int(winner.value), self.last_kernel_ms())
+        return _walk_result(bufs, s.n_leaves, self.last_kernel_ms())
 
     def walk_bound(self, lp: LoadedProgram, starts: np.ndarray, n_roots: int, trees, bounds,
                    seed: int, lanes: int = 4096, max_rounds: int = 64, sync_every: int = 8,
@@ -732,8 +651,9 @@ class Engine:
         ``bounds`` (``repair.bound_table``: ``entries`` (n, 5), ``pieces``
         (m, 4) and ``fixed`` (n, 8) u32); with XOR entries only it is
         :meth:`walk_aim` bit for bit."""
-        return self._walk_rung("mg_walk_bound", lp, starts, n_roots, trees, bounds, None, None,
-                               seed, lanes, max_rounds, sync_every, mask_probe0, n_resid)
+        q = _pack_walk(lp, starts, n_roots, trees, bounds, mask_probe0=mask_probe0,
+                       n_resid=n_resid)
+        return self._walk_rung("mg_walk_bound", lp, q, seed, lanes, max_rounds, sync_every)
 
     def walk_uf(self, lp: LoadedProgram, starts: np.ndarray, n_roots: int, trees, bounds, ufs,
                 seed: int, lanes: int = 4096, max_rounds: int = 64, sync_every: int = 8,
@@ -744,8 +664,9 @@ class Engine:
         program writes ``ufs.n_urows`` U rows after the residual probes
         (``repair.uf_view``).  With no slot piece it is :meth:`walk_bound` bit
         for bit."""
-        return self._walk_rung("mg_walk_uf", lp, starts, n_roots, trees, bounds, ufs, None, seed,
-                               lanes, max_rounds, sync_every, mask_probe0, n_resid)
+        q = _pack_walk(lp, starts, n_roots, trees, bounds, ufs, mask_probe0=mask_probe0,
+                       n_resid=n_resid)
+        return self._walk_rung("mg_walk_uf", lp, q, seed, lanes, max_rounds, sync_every)
 
     def walk_sum(self, lp: LoadedProgram, starts: np.ndarray, n_roots: int, trees, bounds, ufs,
                  sums, seed: int, lanes: int = 4096, max_rounds: int = 64, sync_every: int = 8,
@@ -756,8 +677,9 @@ class Engine:
         ``bounds.entries``); the program writes ``sums.n_srows`` side rows
         after the residual probes and before the U rows.  With no linear entry
         it is :meth:`walk_uf` bit for bit."""
-        return self._walk_rung("mg_walk_sum", lp, starts, n_roots, trees, bounds, ufs, sums, seed,
-                               lanes, max_rounds, sync_every, mask_probe0, n_resid)
+        q = _pack_walk(lp, starts, n_roots, trees, bounds, ufs, sums, mask_probe0=mask_probe0,
+                       n_resid=n_resid)
+        return self._walk_rung("mg_walk_sum", lp, q, seed, lanes, max_rounds, sync_every)
 
     def walk_batch(self, jobs, lanes: int = 4096, max_rounds: int = 64, sync_every: int = 8,
                    max_bytes: Optional[int] = None):
@@ -772,7 +694,6 @@ class Engine:
         there are more jobs than one batch takes, consecutive sub-batches that
         fit are run; jobs are independent, so the results do not depend on the
         split.  A single job that does not fit raises :class:`EngineError`."""
-        from .repair import WalkResult
         jobs = [tuple(j) for j in jobs]
         if not jobs:
             return []
@@ -787,22 +708,17 @@ class Engine:
             parts = split_walk_jobs(shapes, walkers, lanes, max_rounds, cap)
         else:                                   # the library says what is wrong
             parts = [(0, min(len(jobs), WALK_BATCH_MAX_JOBS))]
-        w1, r1 = max(1, min(walkers, 64)), max(1, min(int(max_rounds), 1 << 16))
         results = []
         for lo, hi in parts:
             arr = (WalkJob * (hi - lo))()
             outs = []
-            for i, q in enumerate(packed[lo:hi]):
+            for j, q in zip(arr, packed[lo:hi]):
                 n_leaves = q["shape"].n_leaves
-                out = np.zeros((w1, max(1, n_leaves), 8), dtype=np.uint32)
-                nfail, cost = np.zeros(w1, dtype=np.uint32), np.zeros(w1, dtype=np.uint32)
-                trace = np.zeros((w1, r1, 2), dtype=np.uint32)
-                rw = np.zeros(2, dtype=np.uint32)            # rounds, winner
-                outs.append((out, nfail, cost, trace, rw, n_leaves))
-                j = arr[i]
+                bufs = out, nfail, cost, trace, rounds, winner = _walk_outputs(walkers, n_leaves,
+                                                                               max_rounds)
+                outs.append((bufs, n_leaves))
                 j.prog = q["lp"].handle
-                for name in ("starts", "roots", "atoms", "code", "entries", "pieces", "fixed",
-                             "lin", "slots", "funcs", "cands", "ukeys"):
+                for name in _WALK_TABLES:
                     a = q[name]
                     setattr(j, name, a.ctypes.data if a.size else None)
                 if not q["starts"].size:
@@ -811,7 +727,7 @@ class Engine:
                     j.roots = nfail.ctypes.data
                 j.out_leaves, j.out_nfail, j.out_cost = (out.ctypes.data, nfail.ctypes.data,
                                                          cost.ctypes.data)
-                j.out_rounds, j.out_winner = rw.ctypes.data, rw.ctypes.data + 4
+                j.out_rounds, j.out_winner = C.addressof(rounds), C.addressof(winner)
                 j.trace = trace.ctypes.data
                 j.seed = q["seed"] & (2**64 - 1)
                 for name in _WALK_COUNTS:
@@ -820,10 +736,7 @@ class Engine:
                                         sync_every, cap)
             self._check(rc, "mg_walk_batch")
             ms = self.last_kernel_ms()
-            for out, nfail, cost, trace, rw, n_leaves in outs:
-                results.append(WalkResult(out[:, :n_leaves], nfail.astype(np.int64),
-                                          cost.astype(np.int64), int(rw[0]), trace, int(rw[1]),
-                                          ms))
+            results += [_walk_result(bufs, n_leaves, ms) for bufs, n_leaves in outs]
         return results
 
     def witness(self, lp: LoadedProgram, seed: int, index: int):
@@ -1028,14 +941,13 @@ def walk_aim_mutate_host(leafgen: Sequence[LeafGen], consts: np.ndarray, base: n
     return out[:len(gens), :, :n_lanes], moves[:n_lanes]
 
 
-def walk_bound_mutate_host(leafgen: Sequence[LeafGen], consts: np.ndarray, base: np.ndarray,
-                           state, bounds, seed: int, r: int, lanes: int, lane0: int = 0,
-                           n_lanes: Optional[int] = None, n_resid: Optional[int] = None):
-    """Host-only (no GPU): :func:`walk_aim_mutate_host` for the lane function
-    of mg_walk_bound (mg_walk_bound_mutate_host; ``repair.bound_mutate_ref`` is
-    its specification).  ``state``: what the walker knows of its base, ``(rvals
-    (n_resid, 8) u32, root bits (n_roots,) bool, atom bits (n_atoms,) bool)``,
-    None in round 0."""
+def _walk_mutate_host(name: str, leafgen, consts, base, state, bounds, ufs, sums, seed, r, lanes,
+                      lane0, n_lanes, n_resid):
+    """What :func:`walk_bound_mutate_host`, :func:`walk_uf_mutate_host` and
+    :func:`walk_sum_mutate_host` share: ``state`` and the tables as arrays and
+    the call of the C entry ``name``, whose argument list has the lin words and
+    side rows when ``sums`` is given and the UF tables, U rows and slot
+    destinations when ``ufs`` is."""
     from .repair import bound_mask_words
     lib = load_library()
     gens = list(leafgen)
@@ -1045,68 +957,136 @@ def walk_bound_mutate_host(leafgen: Sequence[LeafGen], consts: np.ndarray, base:
     entries = np.ascontiguousarray(bounds.entries, dtype=np.uint32).reshape(-1, 5)
     pieces = np.ascontiguousarray(bounds.pieces, dtype=np.uint32).reshape(-1, 4)
     fixed = np.ascontiguousarray(bounds.fixed, dtype=np.uint32).reshape(-1, 8)
-    rvals = mvals = None
+    rvals = mvals = svals = None
     n_roots, n_atoms = bounds.n_roots, bounds.n_atoms
+    if sums is not None:
+        lin = np.ascontiguousarray(sums.lin, dtype=np.uint32).reshape(-1)
+    if ufs is not None:
+        tabs = _uf_arrays(ufs)
+        dest = np.full(max(1, tabs[0].shape[0]), 0xFFFFFFFF, dtype=np.uint32)
     if state is not None:
         rvals = np.ascontiguousarray(state[0], dtype=np.uint32).reshape(-1, 8)
         n_roots, n_atoms = len(state[1]), len(state[2])
         mvals = np.concatenate([bound_mask_words(state[1]), bound_mask_words(state[2]),
                                 np.zeros(1, dtype=np.uint32)])
+        if ufs is not None:
+            dest[:tabs[0].shape[0]] = np.asarray(state[3], dtype=np.uint32)
+        if sums is not None:
+            svals = np.ascontiguousarray(state[4], dtype=np.uint32).reshape(-1, 8)
+            if svals.shape[0] < sums.n_srows:
+                raise EngineError("%s: srows shorter than n_srows" % name)
     if n_resid is None:
         n_resid = rvals.shape[0] if rvals is not None else \
             (int(entries[:, 0].max()) + 1 if entries.size else 0)
     if rvals is not None and rvals.shape[0] < n_resid:
-        raise EngineError("mg_walk_bound_mutate_host: rvals shorter than n_resid")
+        raise EngineError("%s: rvals shorter than n_resid" % name)
     n_lanes = lanes - lane0 if n_lanes is None else n_lanes
     out = np.zeros((max(1, len(gens)), 8, max(1, n_lanes)), dtype=np.uint32)
     moves = np.zeros((max(1, n_lanes), 5), dtype=np.uint32)
-    rc = lib.mg_walk_bound_mutate_host(
-        C.cast(garr, C.c_void_p), len(gens), _ptr(consts), consts.shape[0], _ptr(base),
-        _ptr(rvals) if rvals is not None and rvals.size else None, n_resid,
-        _ptr(mvals) if mvals is not None else None, n_roots, n_atoms,
-        _ptr(entries) if entries.size else None, entries.shape[0],
-        _ptr(pieces) if pieces.size else None, pieces.shape[0],
-        _ptr(fixed) if fixed.size else None, seed & (2**64 - 1), r, lanes, lane0, n_lanes,
-        _ptr(out), _ptr(moves))
+    args = [C.cast(garr, C.c_void_p), len(gens), _ptr(consts), consts.shape[0], _ptr(base),
+            _ptr(rvals) if rvals is not None and rvals.size else None, n_resid,
+            _ptr(mvals) if mvals is not None else None, n_roots, n_atoms,
+            _ptr(entries) if entries.size else None, entries.shape[0],
+            _ptr(pieces) if pieces.size else None, pieces.shape[0],
+            _ptr(fixed) if fixed.size else None]
+    if sums is not None:
+        args += [_ptr(lin) if lin.size else None,
+                 _ptr(svals) if svals is not None and svals.size else None, int(sums.n_srows)]
+    if ufs is not None:
+        args += [*_uf_args(tabs), int(ufs.n_urows), _ptr(dest)]
+    args += [seed & (2**64 - 1), r, lanes, lane0, n_lanes, _ptr(out), _ptr(moves)]
+    rc = getattr(lib, name)(*args)
     if rc != 0:
-        raise EngineError("mg_walk_bound_mutate_host failed (%d)" % rc)
+        raise EngineError("%s failed (%d)" % (name, rc))
     return out[:len(gens), :, :n_lanes], moves[:n_lanes]
 
 
-def _pack_walk_job(job):
-    """One job of :meth:`Engine.walk_batch` as contiguous arrays and its
-    :class:`WalkShape`; the shapes :meth:`Engine.walk_sum` checks."""
-    lp, starts, n_roots, trees, bounds, ufs, sums, seed = job[:8]
-    mask_probe0 = job[8] if len(job) > 8 else 0
-    n_resid = job[9] if len(job) > 9 and job[9] is not None else len(trees.probes)
+def walk_bound_mutate_host(leafgen: Sequence[LeafGen], consts: np.ndarray, base: np.ndarray,
+                           state, bounds, seed: int, r: int, lanes: int, lane0: int = 0,
+                           n_lanes: Optional[int] = None, n_resid: Optional[int] = None):
+    """Host-only (no GPU): :func:`walk_aim_mutate_host` for the lane function
+    of mg_walk_bound (mg_walk_bound_mutate_host; ``repair.bound_mutate_ref`` is
+    its specification).  ``state``: what the walker knows of its base, ``(rvals
+    (n_resid, 8) u32, root bits (n_roots,) bool, atom bits (n_atoms,) bool)``,
+    None in round 0."""
+    return _walk_mutate_host("mg_walk_bound_mutate_host", leafgen, consts, base, state, bounds,
+                             None, None, seed, r, lanes, lane0, n_lanes, n_resid)
+
+
+def _pack_walk(lp, starts, n_roots, trees, bounds=None, ufs=None, sums=None, aims=None,
+               mask_probe0=0, n_resid=None):
+    """One tree-scored walk as the library takes it: the contiguous u32 array
+    of every table in ``_WALK_TABLES`` (None for a table of a rung that was not
+    given) and, as ``shape``, its :class:`WalkShape`.  ``aims`` (3-word
+    entries) or ``bounds`` (5-word entries and fixed values) is the aim table.
+    Only the arrays' shapes are checked here; the library refuses the rest."""
+    def u32(a):
+        return np.ascontiguousarray(a, dtype=np.uint32)
+
     n_leaves = len(lp.program.leaves)
-    starts = np.ascontiguousarray(starts, dtype=np.uint32)
-    if starts.ndim != 3 or starts.shape[1:] != (n_leaves, 8):
+    q = dict.fromkeys(_WALK_TABLES)
+    q["starts"] = u32(starts)
+    if q["starts"].ndim != 3 or q["starts"].shape[1:] != (n_leaves, 8):
         raise ValueError("starts must be (walkers, n_leaves, 8)")
-    q = dict(lp=lp, starts=starts, seed=int(seed),
-             roots=np.ascontiguousarray(trees.roots, dtype=np.uint32),
-             atoms=np.ascontiguousarray(trees.atoms, dtype=np.uint32),
-             code=np.ascontiguousarray(trees.code, dtype=np.uint32),
-             entries=np.ascontiguousarray(bounds.entries, dtype=np.uint32),
-             pieces=np.ascontiguousarray(bounds.pieces, dtype=np.uint32),
-             fixed=np.ascontiguousarray(bounds.fixed, dtype=np.uint32),
-             lin=np.ascontiguousarray(sums.lin, dtype=np.uint32))
+    q["roots"], q["atoms"], q["code"] = u32(trees.roots), u32(trees.atoms), u32(trees.code)
     if q["roots"].shape != (max(0, int(n_roots)),) and 1 <= int(n_roots) <= 1024:
         raise ValueError("trees.roots must have n_roots entries")
-    n = q["entries"].shape[0]
-    if q["entries"].shape[1:] != (5,) or q["pieces"].shape[1:] != (4,) or \
-            q["fixed"].shape != (n, 8) or q["lin"].shape != (n,):
-        raise ValueError("bounds.entries must be (n, 5), bounds.pieces (m, 4), "
-                         "bounds.fixed (n, 8), sums.lin (n,)")
-    q["slots"], q["funcs"], q["cands"], q["ukeys"] = _uf_arrays(ufs)
+    n = n_pieces = 0
+    if aims is not None:
+        q["entries"], q["pieces"] = u32(aims.entries), u32(aims.pieces)
+        if q["entries"].shape[1:] != (3,) or q["pieces"].shape[1:] != (4,):
+            raise ValueError("aims.entries must be (n, 3), aims.pieces (m, 4)")
+    if bounds is not None:
+        q["entries"], q["pieces"], q["fixed"] = (u32(bounds.entries), u32(bounds.pieces),
+                                                 u32(bounds.fixed))
+        n = q["entries"].shape[0]
+        if sums is not None:
+            q["lin"] = u32(sums.lin)
+        if q["entries"].shape[1:] != (5,) or q["pieces"].shape[1:] != (4,) or \
+                q["fixed"].shape != (n, 8) or (sums is not None and q["lin"].shape != (n,)):
+            raise ValueError("bounds.entries must be (n, 5), bounds.pieces (m, 4), "
+                             "bounds.fixed (n, 8)" + ("" if sums is None else ", sums.lin (n,)"))
+    if q["entries"] is not None:
+        n, n_pieces = q["entries"].shape[0], q["pieces"].shape[0]
+    if ufs is not None:
+        q["slots"], q["funcs"], q["cands"], q["ukeys"] = _uf_arrays(ufs)
+    n_resid = len(trees.probes) if n_resid is None else n_resid
     q["shape"] = WalkShape(
         n_leaves=n_leaves, n_probes=lp.program.n_probes, n_roots=max(0, int(n_roots)),
         mask_probe0=mask_probe0, n_atoms=q["atoms"].size, n_code=q["code"].size,
-        n_resid=max(0, int(n_resid)), n_entries=n, n_pieces=q["pieces"].shape[0],
-        n_srows=max(0, int(sums.n_srows)), n_slots=q["slots"].shape[0],
-        n_funcs=q["funcs"].shape[0], n_cands=q["cands"].shape[0], n_ukeys=q["ukeys"].shape[0],
-        n_urows=max(0, int(ufs.n_urows)))
+        n_resid=max(0, int(n_resid)), n_entries=n, n_pieces=n_pieces,
+        n_srows=0 if sums is None else max(0, int(sums.n_srows)),
+        n_urows=0 if ufs is None else max(0, int(ufs.n_urows)),
+        **{"n_" + k: 0 if q[k] is None else q[k].shape[0]
+           for k in ("slots", "funcs", "cands", "ukeys")})
     return q
+
+
+def _pack_walk_job(job):
+    """One job tuple of :meth:`Engine.walk_batch` through :func:`_pack_walk`,
+    with its ``lp`` and ``seed``."""
+    q = _pack_walk(*job[:7], **dict(zip(("mask_probe0", "n_resid"), job[8:10])))
+    q["lp"], q["seed"] = job[0], int(job[7])
+    return q
+
+
+def _walk_outputs(walkers: int, n_leaves: int, max_rounds: int):
+    """The buffers one walk writes, ``(out, nfail, cost, trace, rounds,
+    winner)``, never empty and never larger than the library's limits: a count
+    out of range is for the library to refuse."""
+    w1, r1 = max(1, min(walkers, 64)), max(1, min(int(max_rounds), 1 << 16))
+    return (np.zeros((w1, max(1, n_leaves), 8), dtype=np.uint32), np.zeros(w1, dtype=np.uint32),
+            np.zeros(w1, dtype=np.uint32), np.zeros((w1, r1, 2), dtype=np.uint32),
+            C.c_uint32(0), C.c_uint32(0))
+
+
+def _walk_result(bufs, n_leaves: int, kernel_ms: float):
+    """The :class:`mythril_amd.repair.WalkResult` of the buffers of
+    :func:`_walk_outputs` after the walk."""
+    from .repair import WalkResult
+    out, nfail, cost, trace, rounds, winner = bufs
+    return WalkResult(out[:, :n_leaves], nfail.astype(np.int64), cost.astype(np.int64),
+                      int(rounds.value), trace, int(winner.value), kernel_ms)
 
 
 def walk_batch_plan_host(shapes: Sequence[WalkShape], walkers: int, lanes: int, max_rounds: int):
@@ -1300,44 +1280,8 @@ def walk_uf_mutate_host(leafgen: Sequence[LeafGen], consts: np.ndarray, base: np
     of mg_walk_uf (mg_walk_uf_mutate_host; ``repair.uf_mutate_ref`` is its
     specification).  ``state``: ``(rvals, root bits, atom bits, dest (n_slots,)
     u32)``, None in round 0."""
-    from .repair import bound_mask_words
-    lib = load_library()
-    gens = list(leafgen)
-    garr = (LeafGen * max(1, len(gens)))(*gens)
-    consts = np.ascontiguousarray(consts, dtype=np.uint32).reshape(-1, 8)
-    base = np.ascontiguousarray(base, dtype=np.uint32)
-    entries = np.ascontiguousarray(bounds.entries, dtype=np.uint32).reshape(-1, 5)
-    pieces = np.ascontiguousarray(bounds.pieces, dtype=np.uint32).reshape(-1, 4)
-    fixed = np.ascontiguousarray(bounds.fixed, dtype=np.uint32).reshape(-1, 8)
-    tabs = _uf_arrays(ufs)
-    rvals = mvals = None
-    n_roots, n_atoms = bounds.n_roots, bounds.n_atoms
-    dest = np.full(max(1, tabs[0].shape[0]), 0xFFFFFFFF, dtype=np.uint32)
-    if state is not None:
-        rvals = np.ascontiguousarray(state[0], dtype=np.uint32).reshape(-1, 8)
-        n_roots, n_atoms = len(state[1]), len(state[2])
-        mvals = np.concatenate([bound_mask_words(state[1]), bound_mask_words(state[2]),
-                                np.zeros(1, dtype=np.uint32)])
-        dest[:tabs[0].shape[0]] = np.asarray(state[3], dtype=np.uint32)
-    if n_resid is None:
-        n_resid = rvals.shape[0] if rvals is not None else \
-            (int(entries[:, 0].max()) + 1 if entries.size else 0)
-    if rvals is not None and rvals.shape[0] < n_resid:
-        raise EngineError("mg_walk_uf_mutate_host: rvals shorter than n_resid")
-    n_lanes = lanes - lane0 if n_lanes is None else n_lanes
-    out = np.zeros((max(1, len(gens)), 8, max(1, n_lanes)), dtype=np.uint32)
-    moves = np.zeros((max(1, n_lanes), 5), dtype=np.uint32)
-    rc = lib.mg_walk_uf_mutate_host(
-        C.cast(garr, C.c_void_p), len(gens), _ptr(consts), consts.shape[0], _ptr(base),
-        _ptr(rvals) if rvals is not None and rvals.size else None, n_resid,
-        _ptr(mvals) if mvals is not None else None, n_roots, n_atoms,
-        _ptr(entries) if entries.size else None, entries.shape[0],
-        _ptr(pieces) if pieces.size else None, pieces.shape[0],
-        _ptr(fixed) if fixed.size else None, *_uf_args(tabs), int(ufs.n_urows), _ptr(dest),
-        seed & (2**64 - 1), r, lanes, lane0, n_lanes, _ptr(out), _ptr(moves))
-    if rc != 0:
-        raise EngineError("mg_walk_uf_mutate_host failed (%d)" % rc)
-    return out[:len(gens), :, :n_lanes], moves[:n_lanes]
+    return _walk_mutate_host("mg_walk_uf_mutate_host", leafgen, consts, base, state, bounds, ufs,
+                             None, seed, r, lanes, lane0, n_lanes, n_resid)
 
 
 def walk_sum_mutate_host(leafgen: Sequence[LeafGen], consts: np.ndarray, base: np.ndarray,
@@ -1347,50 +1291,8 @@ def walk_sum_mutate_host(leafgen: Sequence[LeafGen], consts: np.ndarray, base: n
     of mg_walk_sum (mg_walk_sum_mutate_host; ``repair.sum_mutate_ref`` is its
     specification).  ``state``: ``(rvals, root bits, atom bits, dest (n_slots,)
     u32, srows (n_srows, 8) u32)``, None in round 0."""
-    from .repair import bound_mask_words
-    lib = load_library()
-    gens = list(leafgen)
-    garr = (LeafGen * max(1, len(gens)))(*gens)
-    consts = np.ascontiguousarray(consts, dtype=np.uint32).reshape(-1, 8)
-    base = np.ascontiguousarray(base, dtype=np.uint32)
-    entries = np.ascontiguousarray(bounds.entries, dtype=np.uint32).reshape(-1, 5)
-    pieces = np.ascontiguousarray(bounds.pieces, dtype=np.uint32).reshape(-1, 4)
-    fixed = np.ascontiguousarray(bounds.fixed, dtype=np.uint32).reshape(-1, 8)
-    lin = np.ascontiguousarray(sums.lin, dtype=np.uint32).reshape(-1)
-    tabs = _uf_arrays(ufs)
-    rvals = mvals = svals = None
-    n_roots, n_atoms = bounds.n_roots, bounds.n_atoms
-    dest = np.full(max(1, tabs[0].shape[0]), 0xFFFFFFFF, dtype=np.uint32)
-    if state is not None:
-        rvals = np.ascontiguousarray(state[0], dtype=np.uint32).reshape(-1, 8)
-        n_roots, n_atoms = len(state[1]), len(state[2])
-        mvals = np.concatenate([bound_mask_words(state[1]), bound_mask_words(state[2]),
-                                np.zeros(1, dtype=np.uint32)])
-        dest[:tabs[0].shape[0]] = np.asarray(state[3], dtype=np.uint32)
-        svals = np.ascontiguousarray(state[4], dtype=np.uint32).reshape(-1, 8)
-        if svals.shape[0] < sums.n_srows:
-            raise EngineError("mg_walk_sum_mutate_host: srows shorter than n_srows")
-    if n_resid is None:
-        n_resid = rvals.shape[0] if rvals is not None else \
-            (int(entries[:, 0].max()) + 1 if entries.size else 0)
-    if rvals is not None and rvals.shape[0] < n_resid:
-        raise EngineError("mg_walk_sum_mutate_host: rvals shorter than n_resid")
-    n_lanes = lanes - lane0 if n_lanes is None else n_lanes
-    out = np.zeros((max(1, len(gens)), 8, max(1, n_lanes)), dtype=np.uint32)
-    moves = np.zeros((max(1, n_lanes), 5), dtype=np.uint32)
-    rc = lib.mg_walk_sum_mutate_host(
-        C.cast(garr, C.c_void_p), len(gens), _ptr(consts), consts.shape[0], _ptr(base),
-        _ptr(rvals) if rvals is not None and rvals.size else None, n_resid,
-        _ptr(mvals) if mvals is not None else None, n_roots, n_atoms,
-        _ptr(entries) if entries.size else None, entries.shape[0],
-        _ptr(pieces) if pieces.size else None, pieces.shape[0],
-        _ptr(fixed) if fixed.size else None, _ptr(lin) if lin.size else None,
-        _ptr(svals) if svals is not None and svals.size else None, int(sums.n_srows),
-        *_uf_args(tabs), int(ufs.n_urows), _ptr(dest),
-        seed & (2**64 - 1), r, lanes, lane0, n_lanes, _ptr(out), _ptr(moves))
-    if rc != 0:
-        raise EngineError("mg_walk_sum_mutate_host failed (%d)" % rc)
-    return out[:len(gens), :, :n_lanes], moves[:n_lanes]
+    return _walk_mutate_host("mg_walk_sum_mutate_host", leafgen, consts, base, state, bounds, ufs,
+                             sums, seed, r, lanes, lane0, n_lanes, n_resid)
 
 
 def walk_score_host(masks: np.ndarray, resid: Optional[np.ndarray], table: np.ndarray,

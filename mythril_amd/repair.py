@@ -2065,15 +2065,25 @@ class _WitnessJob:
 
 class _TreeWalk:
     """Where :func:`_repair_steps` hands a tree-scored walk to its driver:
-    ``single()`` runs it as :func:`repair_group` always has; ``job`` is the same
-    walk as a job of ``Engine.walk_batch`` on ``eng`` (mg_walk_sum's arguments:
-    a kind without a table gets the empty one, which by §3.12 - §3.15 is that
-    kind bit for bit)."""
+    ``job`` is the walk as a job of ``Engine.walk_batch`` on ``eng``
+    (mg_walk_sum's arguments: a kind without a table gets the empty one, which
+    by §3.12 - §3.15 is that kind bit for bit); ``single()`` runs it as
+    :func:`repair_group` always has, with the entry of its own ``rung``
+    (``Engine.walk_<rung>``) on the tables of the job that the entry takes."""
 
     stage = 2
 
-    def __init__(self, eng, job, single):
-        self.eng, self.job, self.single = eng, job, single
+    def __init__(self, eng, rung, job, lanes, max_rounds, sync_every):
+        self.eng, self.rung, self.job = eng, rung, job
+        self.how = (lanes, max_rounds, sync_every)
+
+    def single(self):
+        wide, starts, n, trees, bounds, ufs, sums, seed = self.job
+        tables = {"tree": (), "bound": (bounds,), "uf": (bounds, ufs), "sum": (bounds, ufs, sums),
+                  # the job's XOR entries are the aim table's with two zero words each
+                  "aim": (Aims(bounds.entries[:, :3], bounds.pieces, bounds.sides),)}[self.rung]
+        return getattr(self.eng, "walk_" + self.rung)(wide, starts, n, trees, *tables, seed,
+                                                      *self.how)
 
 
 def _repair_steps(nodes, n_cand, form, lanes, max_rounds, device, seed, sync_every, scored,
@@ -2245,32 +2255,24 @@ def _repair_steps(nodes, n_cand, form, lanes, max_rounds, device, seed, sync_eve
             # arguments, then the kept keys
             wide = eng.load(uf_view(masked, n_mask + n_amask + len(resid) + len(sprobes) +
                                     ufs.n_arg_rows, ufs.keep), gens, prog_seed=0)
-            job = (wide, starts, n, trees, bounds, ufs, sums, seed)
-            single = lambda: eng.walk_sum(wide, starts, n, trees, bounds, ufs, sums, seed, lanes,
-                                          max_rounds, sync_every)
+            rung, job = "sum", (wide, starts, n, trees, bounds, ufs, sums, seed)
         elif trees is not None and ufs is not None:
             # the U rows after the residuals: the arguments, then the kept keys
             wide = eng.load(uf_view(masked, n_mask + n_amask + len(resid) + ufs.n_arg_rows,
                                     ufs.keep), gens, prog_seed=0)
-            job = (wide, starts, n, trees, bounds, ufs, no_sums(len(bounds)), seed)
-            single = lambda: eng.walk_uf(wide, starts, n, trees, bounds, ufs, seed, lanes,
-                                         max_rounds, sync_every)
+            rung, job = "uf", (wide, starts, n, trees, bounds, ufs, no_sums(len(bounds)), seed)
         elif trees is not None and bounds is not None:
-            job = (wide, starts, n, trees, bounds, no_ufs(), no_sums(len(bounds)), seed)
-            single = lambda: eng.walk_bound(wide, starts, n, trees, bounds, seed, lanes,
-                                            max_rounds, sync_every)
+            rung, job = "bound", (wide, starts, n, trees, bounds, no_ufs(),
+                                  no_sums(len(bounds)), seed)
         elif trees is not None and aims is not None and len(aims):
             xor = bounds_of_aims(aims, n, trees.n_atoms)
-            job = (wide, starts, n, trees, xor, no_ufs(), no_sums(len(xor)), seed)
-            single = lambda: eng.walk_aim(wide, starts, n, trees, aims, seed, lanes, max_rounds,
-                                          sync_every)
+            rung, job = "aim", (wide, starts, n, trees, xor, no_ufs(), no_sums(len(xor)), seed)
         elif trees is not None:
-            job = (wide, starts, n, trees, bounds_of_aims(no_aims(), n, trees.n_atoms), no_ufs(),
-                   no_sums(0), seed)
-            single = lambda: eng.walk_tree(wide, starts, n, trees, seed, lanes, max_rounds,
-                                           sync_every)
+            rung, job = "tree", (wide, starts, n, trees,
+                                 bounds_of_aims(no_aims(), n, trees.n_atoms), no_ufs(),
+                                 no_sums(0), seed)
         if trees is not None:
-            res = yield _TreeWalk(eng, job, single)
+            res = yield _TreeWalk(eng, rung, job, lanes, max_rounds, sync_every)
             out["trees"] = trees
         else:
             res = eng.walk(wide, starts, len(nodes), table, len(resid), seed, lanes, max_rounds,
