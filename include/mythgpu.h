@@ -725,6 +725,72 @@ int mg_carry_plan_host(const uint32_t* n_leaves /*[n_jobs]*/, uint32_t n_jobs, u
                        uint32_t max_leaves, uint64_t* out_offsets, uint64_t* out_bytes,
                        uint64_t* out_leaf_stride_w);
 
+/* The pin ladder of the witness carry (csrc/mg_carry.h,
+ * mg_carry_ladder.hip): several pin sets of a job tried in one launch
+ * sequence.  A job names an eval-form program (loaded with its leaf
+ * generators), ONE set of pin rows and n_rungs pin masks, strictest first,
+ * mask r at pin_masks + r * ((n_leaves + 31) / 32).  A call has `lanes`
+ * candidates per rung; with R the batch's largest n_rungs every job has
+ * C = R x lanes columns.  Column c of job j lies on rung
+ * r = min(c / lanes, n_rungs - 1) and holds candidate i = c % lanes: leaf l is
+ * the pin row where bit l of mask r is set, else generator v9's value for
+ * (gen->seed, the program's prog_seed, l, gen->first_index + i), every value
+ * masked to the leaf's width — what lane i of mg_carry_batch holds under mask
+ * r.  Every rung so replays the same candidates, and a job with fewer rungs
+ * than R repeats its last one in the surplus columns.
+ * first[j]: the lowest column of 0 .. C - 1 on which every root of job j
+ * holds, or -1; rung[j]: that column's rung, or -1 — the strictest rung with
+ * a hit, since rungs lie in column order; leaves[j]: that column's leaf rows,
+ * zero where there is none and past the program's leaves.  fill_out (may be
+ * NULL): the jobs' leaf regions as the fill kernel wrote them,
+ * [n_jobs][leaf_stride_w] words with job j's [n_leaves][8][C] at the front
+ * (mg_carry_ladder_plan_host gives the stride).
+ * The sequence is mg_carry_batch's: one upload, the rung fill launch, one
+ * eval-mode interpreter launch over the job axis at C candidates, the gather
+ * launch, one download; mg_last_kernel_ms covers the three launches.  With
+ * one rung per job the results are those of mg_carry_batch under that mask.
+ * Refused with MG_E_ARG before any upload or launch, the message beginning
+ * "carry_ladder:": whatever mg_carry_batch refuses; n_rungs outside
+ * 1..MG_CARRY_MAX_RUNGS; R x lanes above 2^20; a null mask pointer. */
+#define MG_CARRY_MAX_RUNGS 8u
+typedef struct mg_carry_ladder_job {
+    const mg_prog* prog;        /* eval-form program, loaded with its leaf generators */
+    const uint32_t* pin_rows;   /* [n_leaves][8]; rows of leaves no rung pins ignored  */
+    const uint32_t* pin_masks;  /* [n_rungs][(n_leaves + 31) / 32], strictest first    */
+    uint32_t n_rungs;           /* 1..MG_CARRY_MAX_RUNGS                               */
+    uint32_t pad;
+} mg_carry_ladder_job;
+int mg_carry_ladder(mg_ctx* ctx, const mg_carry_ladder_job* jobs, uint32_t n_jobs,
+                    const mg_gen* gen, uint32_t lanes, int64_t* first /*[n_jobs], -1: none*/,
+                    int64_t* rung /*[n_jobs], -1: none*/,
+                    uint32_t* leaves /*[n_jobs][max_leaves][8]*/, uint32_t max_leaves,
+                    uint32_t* fill_out /*NULL, or every job's leaf region copied back*/);
+/* Host-only (no GPU): columns col0 .. col0 + n_cols - 1 of one job of
+ * mg_carry_ladder as the rung fill kernel writes them, from the same lane
+ * function: out [n_leaves][8][n_cols].  cols: the columns of the job, a
+ * multiple of lanes in the call (n_rungs x lanes or more: the surplus repeats
+ * the last rung).  MG_E_ARG as mg_carry_fill_host, and for n_rungs outside
+ * 1..MG_CARRY_MAX_RUNGS, cols below lanes or above 2^20 and a column range
+ * outside cols. */
+int mg_carry_fill_rungs_host(const mg_leafgen* leaves, uint32_t n_leaves, const uint32_t* consts,
+                             uint32_t n_consts, uint64_t prog_seed,
+                             const uint32_t* pin_rows /*[n_leaves][8]*/,
+                             const uint32_t* pin_masks /*[n_rungs][(n_leaves + 31) / 32]*/,
+                             uint32_t n_rungs, uint64_t seed, uint64_t first_index,
+                             uint32_t lanes, uint32_t cols, uint32_t col0, uint32_t n_cols,
+                             uint32_t* out);
+/* Host-only (no GPU): the plan of the device buffer mg_carry_ladder uses: the
+ * regions of mg_carry_plan_host in the same order and under the same indices,
+ * job j's mask region holding its n_rungs[j] masks, the output block first,
+ * rung and rows, and every leaf region the batch's largest n_leaves x 8 x C
+ * words rounded up to 256 bytes (*out_leaf_stride_w).  MG_E_ARG for a null
+ * pointer, n_jobs, lanes or an n_rungs out of range, R x lanes above 2^20 and
+ * sizes beyond 64 bits. */
+int mg_carry_ladder_plan_host(const uint32_t* n_leaves /*[n_jobs]*/,
+                              const uint32_t* n_rungs /*[n_jobs]*/, uint32_t n_jobs,
+                              uint32_t lanes, uint32_t max_leaves, uint64_t* out_offsets,
+                              uint64_t* out_bytes, uint64_t* out_leaf_stride_w);
+
 /* Corpus batches: many programs, one launch.  Device-pointer API for
  * resident benchmarking; stream is a hipStream_t (NULL = the context's own
  * stream, which the synchronous calls also use).

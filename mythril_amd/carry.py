@@ -15,6 +15,12 @@ whole ``batch_is_possible`` call — in one launch sequence.
 The carry never concludes UNSAT: a group it misses is searched as before, and a
 carried witness is accepted by the same rule as any other (``model._accept``).
 Opt-in: ``MYTHRIL_GPU_CARRY=1``.
+
+``MYTHRIL_GPU_CARRY=2`` runs the pin ladder instead: the
+extended group is compiled in eval form WITH constant keys
+(:func:`compile_eval_ck`), several pin sets — all, read, new (:func:`rungs`) —
+are tried strictest first, and ``Engine.carry_ladder`` evaluates every rung of
+every job in the same three launches (:func:`run_ladder`).
 """
 
 from __future__ import annotations
@@ -25,7 +31,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from .assign import Assignment, leaf_values, unpack
-from .ir import Program, compile_constraints
+from .ir import Program, compile_constraints, scan_const_keys
 
 # candidates of a job with at least one free leaf (MYTHRIL_GPU_CARRY_LANES);
 # a job with no free leaf runs one.  256 is one block of the interpreter and
@@ -209,6 +215,169 @@ def pins(program: Program, asg: Assignment) -> Tuple[np.ndarray, np.ndarray]:
 def n_free(program: Program, mask: np.ndarray) -> int:
     n = len(program.leaves)
     return n - sum(bin(int(w)).count("1") for w in mask)
+
+
+# ---------------------------------------------------------------------------
+# The pin ladder (MYTHRIL_GPU_CARRY=2): the eval form with
+# constant keys and several pin sets per job, strictest first
+# ---------------------------------------------------------------------------
+
+MAX_RUNGS = 8                  # include/mythgpu.h MG_CARRY_MAX_RUNGS
+RUNG_NAMES = ("all", "read", "new")
+
+
+def table_sizes_ck(nodes, asg: Assignment, default: int = DEFAULT_ENTRIES) -> Dict[str, int]:
+    """``table_sizes`` for the constant-keyed eval form of ``nodes`` evaluated
+    under ``asg``: per carried table the maximum of the default and the number
+    of its entries whose key is not a constant key the nodes read the table at
+    (``scan_const_keys``) — the entries ``assign.leaf_values`` leaves in the
+    leaf-keyed part; those at constant keys are served by ``cval`` leaves.  A
+    table the nodes read at constant keys only has no leaf-keyed part at all —
+    every read is a ``cval`` leaf, no ``key`` or ``val`` leaf exists and no
+    other entry of the witness can be met — so it keeps the default whatever
+    the witness holds (a calldata witness of 68 entries read at bytes 0..4)."""
+    sym: Dict[str, int] = {}
+    ck = scan_const_keys(nodes, sym_counts=sym)
+    out = {}
+    for name, (entries, _) in list(asg.arrays.items()) + list(asg.funcs.items()):
+        keys = set(ck.get(name, ()))
+        rest = sum(1 for k, _ in entries if k not in keys) if sym.get(name) else 0
+        out[name] = max(default, rest)
+    return out
+
+
+def compile_eval_ck(nodes, asg: Assignment, sizes: Optional[Dict[str, int]] = None) -> Program:
+    """:func:`compile_eval` with constant keys: every numeral-keyed read is a
+    ``cval`` leaf of its own, so a carried table costs its remaining entries
+    only (``sizes``: :func:`table_sizes_ck`, computed when not given).  Cached
+    with the plain form, under a key that names the form."""
+    sizes = table_sizes_ck(nodes, asg) if sizes is None else sizes
+    key = ("ck", tuple(n.id for n in nodes), tuple(sorted(sizes.items())))
+    prog = _EVAL_CACHE.get(key)
+    if prog is not None:
+        _EVAL_CACHE.move_to_end(key)
+        return prog
+    prog = compile_constraints(nodes, solve=False, leaf_pools=True, const_keys=True,
+                               table_sizes=sizes or None)
+    _EVAL_CACHE[key] = prog
+    if len(_EVAL_CACHE) > EVAL_CACHE_SIZE:
+        _EVAL_CACHE.popitem(last=False)
+    return prog
+
+
+def _symbol_names(nodes) -> set:
+    from .smt.node import topo_order
+    return {n.params[0] for n in topo_order(list(nodes)) if n.op in ("var", "array", "apply")}
+
+
+def rung_masks(program: Program, asg: Assignment, parent_nodes, new_nodes):
+    """``(rows, ladder)`` of one ladder job: ``rows`` ((n_leaves, 8) uint32) as
+    :func:`pins` gives them — every leaf the strictest rung pins holds its
+    carried value, so one row set serves all rungs — and ``ladder``
+    ((len(RUNG_NAMES), (n_leaves + 31) // 32) uint32), the mask of every rung
+    of ``RUNG_NAMES``, strictest first:
+
+    * "all": the rule of :func:`pins`, every leaf whose source ``asg``
+      interprets.
+    * "read": as "all", but a ``cval`` leaf at a key the parent never read its
+      table at (``scan_const_keys(parent_nodes)``) is free: that entry of the
+      witness was a don't-care.  ``key``, ``val`` and ``else`` leaves and vars
+      stay pinned, and a table the parent reads at a symbolic key without
+      ``scan_const_keys`` listing it (no numeral key, or too many symbolic
+      links) frees nothing: any entry may have been what that read met.
+    * "new": as "read", and every leaf whose source occurs in ``new_nodes``
+      is free.
+
+    ``parent_nodes``: the group's nodes of the remembered subsets the pin set
+    was taken from (``plan``'s keys); ``new_nodes``: the rest."""
+    n = len(program.leaves)
+    words = (n + 31) // 32
+    rows = np.zeros((n, 8), dtype=np.uint32)
+    ladder = np.zeros((len(RUNG_NAMES), words), dtype=np.uint32)
+    sym: Dict[str, int] = {}
+    read = scan_const_keys(parent_nodes, sym_counts=sym)
+    closed = {name for name, k in sym.items() if k and name not in read}
+    fresh = _symbol_names(new_nodes)
+    vals = leaf_values(program, asg) if n else []
+    for l, (leaf, v) in enumerate(zip(program.leaves, vals)):
+        if not pinned(leaf, asg):
+            continue
+        rows[l] = np.frombuffer(int(v).to_bytes(32, "little"), dtype="<u4")
+        keep = [True, True, True]
+        if leaf.kind == "cval" and leaf.source not in closed:
+            key = program.table_ckeys[leaf.source][leaf.entry]
+            keep[1] = key in read.get(leaf.source, ())
+        keep[2] = keep[1] and leaf.source not in fresh
+        for r in range(len(RUNG_NAMES)):
+            if keep[r]:
+                ladder[r, l >> 5] |= np.uint32(1 << (l & 31))
+    return rows, ladder
+
+
+def distinct(ladder: np.ndarray) -> List[int]:
+    """The rows of ``ladder`` that differ from every row before them, in
+    order, ``MAX_RUNGS`` at the most."""
+    kept: List[int] = []
+    for r in range(ladder.shape[0]):
+        if not any(np.array_equal(ladder[r], ladder[k]) for k in kept):
+            kept.append(r)
+    return kept[:MAX_RUNGS]
+
+
+def rungs(program: Program, asg: Assignment, parent_nodes, new_nodes):
+    """``(rows, masks)`` of one ladder job: the rows and the distinct masks of
+    :func:`rung_masks`, strictest first."""
+    rows, ladder = rung_masks(program, asg, parent_nodes, new_nodes)
+    return rows, ladder[distinct(ladder)]
+
+
+def split_nodes(nodes, taken_keys):
+    """``(parent_nodes, new_nodes)`` of a group: the nodes whose ids lie in the
+    subset keys :func:`plan` reports as taken, and the rest."""
+    ids = set().union(*taken_keys) if taken_keys else set()
+    return [n for n in nodes if n.id in ids], [n for n in nodes if n.id not in ids]
+
+
+def run_ladder(eng, items, seed: int, leafgen, lanes: Optional[int] = None, phase=None):
+    """:func:`run` on the pin ladder: one ``Engine.carry_ladder`` call for
+    ``items``, a list of ``(nodes, assignment, taken_keys)`` (``plan``'s third
+    element).  Per item ``(assignment, program, candidates, rung)`` — the
+    witness (None on a miss), the constant-keyed eval form, the candidates the
+    job ran over all its rungs and the index in ``RUNG_NAMES`` of the rung
+    that hit (-1 on a miss) — or None where the group has no eval form.  A
+    rung without a free leaf is one candidate; a batch none of whose rungs has
+    one runs one lane."""
+    import contextlib
+    from .ir import Unsupported
+    phase = phase or (lambda name: contextlib.nullcontext())
+    lanes = CARRY_LANES if lanes is None else lanes
+    jobs, progs, free, kept, where = [], [], [], [], []
+    with phase("compile"):
+        for k, (nodes, asg, taken) in enumerate(items):
+            try:
+                prog = compile_eval_ck(nodes, asg)
+                rows, ladder = rung_masks(prog, asg, *split_nodes(nodes, taken))
+            except (Unsupported, ValueError):
+                continue
+            keep = distinct(ladder)
+            progs.append(prog)
+            kept.append(keep)
+            free.append([n_free(prog, ladder[r]) for r in keep])
+            jobs.append((prog, rows, ladder[keep]))
+            where.append(k)
+    out: List = [None] * len(items)
+    if not jobs:
+        return out
+    width = max(1, int(lanes)) if any(any(f) for f in free) else 1
+    width = min(width, (1 << 20) // max(len(keep) for keep in kept))   # the call's column cap
+    with phase("load"):
+        loaded = [(eng.load(p, leafgen(p), prog_seed=0), r, m) for p, r, m in jobs]
+    with phase("search"):
+        res = eng.carry_ladder(loaded, seed, 0, width)
+        for k, prog, f, keep, (first, rung, leaves) in zip(where, progs, free, kept, res):
+            out[k] = (unpack(prog, leaves) if first >= 0 else None, prog,
+                      sum(width if x else 1 for x in f), keep[rung] if first >= 0 else -1)
+    return out
 
 
 def run(eng, items, seed: int, leafgen, lanes: Optional[int] = None, phase=None):

@@ -163,6 +163,15 @@ hipError_t mg_launch_carry_gather(const mg_carry_dev_job* d_jobs, uint32_t n_job
                                   const unsigned long long* d_first, uint32_t lanes,
                                   uint32_t max_leaves, long long* d_out_first,
                                   uint32_t* d_out_leaves, hipStream_t stream);
+// the two around mg_carry_ladder's (mg_carry_ladder.hip)
+hipError_t mg_launch_carry_fill_rungs(const mg_carry_dev_job* d_jobs, uint32_t n_jobs,
+                                      uint32_t most_leaves, uint64_t seed, uint64_t first_index,
+                                      uint32_t lanes, uint32_t cols, hipStream_t stream);
+hipError_t mg_launch_carry_gather_rungs(const mg_carry_dev_job* d_jobs, uint32_t n_jobs,
+                                        const unsigned long long* d_first, uint32_t lanes,
+                                        uint32_t cols, uint32_t max_leaves,
+                                        long long* d_out_first, long long* d_out_rung,
+                                        uint32_t* d_out_leaves, hipStream_t stream);
 
 struct mg_ctx {
     int device = 0;
@@ -1939,7 +1948,7 @@ int mg_carry_batch(mg_ctx* ctx, const mg_carry_job* jobs, uint32_t n_jobs, const
         d.leaves = (uint32_t*)(w + at(MG_CY_LEAVES));
         d.prog_seed = j.prog->h_desc.prog_seed;
         d.n_leaves = n;
-        d.pad = 0;
+        d.n_rungs = 0;
     }
     const mg_pdesc* d_descs = (const mg_pdesc*)(w + off[MG_CY_DESCS]);
     const mg_carry_dev_job* d_jobs = (const mg_carry_dev_job*)(w + off[MG_CY_JOBS]);
@@ -2001,6 +2010,157 @@ int mg_carry_plan_host(const uint32_t* n_leaves, uint32_t n_jobs, uint32_t lanes
                        uint64_t* out_leaf_stride_w) {
     return mg_carry_plan(n_leaves, n_jobs, lanes, max_leaves, out_offsets, out_bytes,
                          out_leaf_stride_w) ? MG_OK : MG_E_ARG;
+}
+
+// The pin ladder (include/mythgpu.h mg_carry_ladder, DESIGN.md §3.19;
+// csrc/mg_carry.h, mg_carry_ladder.hip): mg_carry_batch's sequence with
+// n_rungs masks per job and the largest n_rungs x lanes columns.
+int mg_carry_ladder(mg_ctx* ctx, const mg_carry_ladder_job* jobs, uint32_t n_jobs,
+                    const mg_gen* gen, uint32_t lanes, int64_t* first, int64_t* rung,
+                    uint32_t* leaves, uint32_t max_leaves, uint32_t* fill_out) {
+    if (!ctx) return MG_E_ARG;
+    if (!jobs || !gen || !first || !rung || !leaves)
+        return fail(ctx, MG_E_ARG, "carry_ladder: null argument");
+    if (n_jobs < 1 || n_jobs > MG_CARRY_MAX_JOBS)
+        return fail(ctx, MG_E_ARG, "carry_ladder: %u jobs outside 1..%u", n_jobs,
+                    MG_CARRY_MAX_JOBS);
+    if (lanes < 1 || lanes > MG_REPAIR_MAX_LANES)
+        return fail(ctx, MG_E_ARG, "carry_ladder: %u lanes outside 1..%u", lanes,
+                    MG_REPAIR_MAX_LANES);
+    if (max_leaves > MG_CARRY_MAX_LEAVES)
+        return fail(ctx, MG_E_ARG, "carry_ladder: max_leaves %u above %u", max_leaves,
+                    MG_CARRY_MAX_LEAVES);
+    std::vector<uint32_t> n_leaves(n_jobs), n_rungs(n_jobs);
+    uint32_t most = 0, max_lds = 0, top = 0;
+    for (uint32_t g = 0; g < n_jobs; ++g) {
+        const mg_carry_ladder_job& j = jobs[g];
+        if (!j.prog) return fail(ctx, MG_E_ARG, "carry_ladder: job %u: null program", g);
+        if (j.prog->ctx != ctx)
+            return fail(ctx, MG_E_ARG, "carry_ladder: job %u: a program of another context", g);
+        if (j.prog->n_leaves > max_leaves)
+            return fail(ctx, MG_E_ARG, "carry_ladder: job %u: %u leaves above max_leaves %u", g,
+                        j.prog->n_leaves, max_leaves);
+        if (j.n_rungs < 1 || j.n_rungs > MG_CARRY_MAX_RUNGS)
+            return fail(ctx, MG_E_ARG, "carry_ladder: job %u: %u rungs outside 1..%u", g,
+                        j.n_rungs, MG_CARRY_MAX_RUNGS);
+        if (j.prog->n_leaves && (!j.pin_rows || !j.pin_masks))
+            return fail(ctx, MG_E_ARG, "carry_ladder: job %u: null pin rows or pin masks", g);
+        if (j.prog->leafgen.size() != j.prog->n_leaves ||
+            !mg_carry_gen_ok(j.prog->leafgen.data(), j.prog->n_leaves, j.prog->n_consts))
+            return fail(ctx, MG_E_ARG, "carry_ladder: job %u: the program's leaf generators are "
+                        "not loaded", g);
+        n_leaves[g] = j.prog->n_leaves;
+        n_rungs[g] = j.n_rungs;
+        most = n_leaves[g] > most ? n_leaves[g] : most;
+        top = j.n_rungs > top ? j.n_rungs : top;
+        max_lds = j.prog->n_lds > max_lds ? j.prog->n_lds : max_lds;
+    }
+    uint32_t cols = 0;
+    if (!mg_carry_ladder_ok(n_rungs.data(), n_jobs, lanes, &cols))
+        return fail(ctx, MG_E_ARG, "carry_ladder: %u rungs of %u lanes above %u columns", top,
+                    lanes, MG_REPAIR_MAX_LANES);
+    std::vector<uint64_t> off(MG_CY_SHARED + (size_t)n_jobs * MG_CY_JOB_REGIONS);
+    uint64_t bytes = 0, leaf_w = 0;
+    if (!mg_carry_ladder_plan(n_leaves.data(), n_rungs.data(), n_jobs, lanes, max_leaves,
+                              off.data(), &bytes, &leaf_w))
+        return fail(ctx, MG_E_ARG, "carry_ladder: the batch's buffer exceeds 64 bits");
+    if (bytes > MG_WALK_BATCH_DEFAULT_BYTES)
+        return fail(ctx, MG_E_ARG, "carry_ladder: %llu bytes needed for %u jobs at %u columns, "
+                    "at most %llu; pass fewer jobs, rungs or lanes", (unsigned long long)bytes,
+                    n_jobs, cols, (unsigned long long)MG_WALK_BATCH_DEFAULT_BYTES);
+    HIPCHECK(ctx, hipSetDevice(ctx->device));
+    void* ws;
+    int rc = workspace(ctx, (size_t)bytes + 256, &ws);
+    if (rc) return rc;
+    uint8_t* w = (uint8_t*)ws;
+    // the host image of everything uploaded, at the offsets of the plan
+    const size_t up_b = (size_t)off[MG_CY_OUT];
+    std::vector<uint8_t> img(up_b, 0);
+    mg_pdesc* h_descs = (mg_pdesc*)(img.data() + off[MG_CY_DESCS]);
+    mg_carry_dev_job* h_jobs = (mg_carry_dev_job*)(img.data() + off[MG_CY_JOBS]);
+    memset(img.data() + off[MG_CY_FIRST], 0xFF, (size_t)n_jobs * 8);
+    for (uint32_t g = 0; g < n_jobs; ++g) {
+        const mg_carry_ladder_job& j = jobs[g];
+        const uint32_t n = n_leaves[g];
+        auto at = [&](uint32_t k) { return off[MG_CY_OFF(g, k)]; };
+        if (n) {
+            memcpy(img.data() + at(MG_CY_MASK), j.pin_masks,
+                   (size_t)((n + 31) / 32) * 4 * j.n_rungs);
+            memcpy(img.data() + at(MG_CY_ROWS), j.pin_rows, (size_t)n * 32);
+            memcpy(img.data() + at(MG_CY_GEN), j.prog->leafgen.data(), (size_t)n * sizeof(mg_leafgen));
+        }
+        h_descs[g] = j.prog->h_desc;
+        mg_carry_dev_job& d = h_jobs[g];
+        d.mask = (const uint32_t*)(w + at(MG_CY_MASK));
+        d.rows = (const uint32_t*)(w + at(MG_CY_ROWS));
+        d.gen = (const mg_leafgen*)(w + at(MG_CY_GEN));
+        d.consts = j.prog->h_desc.consts;              // the first n_consts entries: as loaded
+        d.leaves = (uint32_t*)(w + at(MG_CY_LEAVES));
+        d.prog_seed = j.prog->h_desc.prog_seed;
+        d.n_leaves = n;
+        d.n_rungs = j.n_rungs;
+    }
+    const mg_pdesc* d_descs = (const mg_pdesc*)(w + off[MG_CY_DESCS]);
+    const mg_carry_dev_job* d_jobs = (const mg_carry_dev_job*)(w + off[MG_CY_JOBS]);
+    unsigned long long* d_first = (unsigned long long*)(w + off[MG_CY_FIRST]);
+    long long* d_out_first = (long long*)(w + off[MG_CY_OUT]);
+    long long* d_out_rung = d_out_first + n_jobs;
+    uint32_t* d_out_leaves = (uint32_t*)(w + off[MG_CY_OUT] + (size_t)n_jobs * 16);
+    HIPCHECK(ctx, hipMemcpyAsync(w, img.data(), up_b, hipMemcpyHostToDevice, ctx->stream));
+    mg_run run = empty_run();
+    run.leaves = (const uint32_t*)(w + off[MG_CY_OFF(0, MG_CY_LEAVES)]);
+    run.leaves_prog_words = leaf_w;
+    run.first_sat = d_first;                           // first_index 0: the column itself
+    run.stride = cols;
+    run.n_assign = cols;
+    timing_begin(ctx);
+    HIPCHECK(ctx, mg_launch_carry_fill_rungs(d_jobs, n_jobs, most, gen->seed, gen->first_index,
+                                             lanes, cols, ctx->stream));
+    HIPCHECK(ctx, launch(ctx, 0, d_descs, n_jobs, run, max_lds, ctx->stream));
+    HIPCHECK(ctx, mg_launch_carry_gather_rungs(d_jobs, n_jobs, d_first, lanes, cols, max_leaves,
+                                               d_out_first, d_out_rung, d_out_leaves,
+                                               ctx->stream));
+    timing_end(ctx);
+    const size_t out_b = (size_t)n_jobs * 16 + (size_t)n_jobs * max_leaves * 32;
+    std::vector<uint8_t> h_out(out_b);
+    HIPCHECK(ctx, hipMemcpyAsync(h_out.data(), d_out_first, out_b, hipMemcpyDeviceToHost,
+                                 ctx->stream));
+    if (fill_out && leaf_w)
+        HIPCHECK(ctx, hipMemcpyAsync(fill_out, run.leaves, (size_t)n_jobs * leaf_w * 4,
+                                     hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
+    timing_read(ctx);
+    memcpy(first, h_out.data(), (size_t)n_jobs * 8);
+    memcpy(rung, h_out.data() + (size_t)n_jobs * 8, (size_t)n_jobs * 8);
+    memcpy(leaves, h_out.data() + (size_t)n_jobs * 16, (size_t)n_jobs * max_leaves * 32);
+    return MG_OK;
+}
+
+int mg_carry_fill_rungs_host(const mg_leafgen* leaves, uint32_t n_leaves, const uint32_t* consts,
+                             uint32_t n_consts, uint64_t prog_seed, const uint32_t* pin_rows,
+                             const uint32_t* pin_masks, uint32_t n_rungs, uint64_t seed,
+                             uint64_t first_index, uint32_t lanes, uint32_t cols, uint32_t col0,
+                             uint32_t n_cols, uint32_t* out) {
+    if (n_rungs < 1 || n_rungs > MG_CARRY_MAX_RUNGS) return MG_E_ARG;
+    if (lanes < 1 || cols < lanes || cols > MG_REPAIR_MAX_LANES || col0 > cols ||
+        n_cols > cols - col0)
+        return MG_E_ARG;
+    if (n_leaves == 0 || n_cols == 0) return MG_OK;
+    if (!leaves || !pin_rows || !pin_masks || !out || (n_consts && !consts)) return MG_E_ARG;
+    if (!mg_carry_gen_ok(leaves, n_leaves, n_consts)) return MG_E_ARG;
+    const uint32_t words = (n_leaves + 31) / 32;
+    for (uint32_t l = 0; l < n_leaves; ++l)
+        for (uint32_t i = 0; i < n_cols; ++i)
+            mg_carry_fill_rung_lane(pin_masks, words, n_rungs, pin_rows, leaves, consts, prog_seed,
+                                    seed, first_index, l, col0 + i, lanes, n_cols, i, out);
+    return MG_OK;
+}
+
+int mg_carry_ladder_plan_host(const uint32_t* n_leaves, const uint32_t* n_rungs, uint32_t n_jobs,
+                              uint32_t lanes, uint32_t max_leaves, uint64_t* out_offsets,
+                              uint64_t* out_bytes, uint64_t* out_leaf_stride_w) {
+    return mg_carry_ladder_plan(n_leaves, n_rungs, n_jobs, lanes, max_leaves, out_offsets,
+                                out_bytes, out_leaf_stride_w) ? MG_OK : MG_E_ARG;
 }
 
 // Host only: lanes lane0 .. lane0 + n_lanes - 1 of round r of the lane

@@ -24,7 +24,15 @@
  *   per job, its leaves  [leaf][limb][lanes] at a common stride: the largest
  *                        n_leaves of the batch x 8 x lanes words, rounded up to
  *                        256 bytes (the stride the interpreter's shell applies)
- * offsets[]: MG_CY_SHARED shared regions, then MG_CY_JOB_REGIONS per job. */
+ * offsets[]: MG_CY_SHARED shared regions, then MG_CY_JOB_REGIONS per job.
+ *
+ * mg_carry_ladder runs the same sequence with n_rungs pin
+ * masks per job, strictest first: with R the batch's largest n_rungs a job has
+ * C = R x lanes columns, column c on rung min(c / lanes, n_rungs - 1) and
+ * candidate c % lanes (mg_carry_rung, mg_carry_fill_rung_lane).  Its buffer is
+ * the one above with a job's mask region holding its n_rungs masks one after
+ * the other, the output block n_jobs i64 first, n_jobs i64 rung and the rows,
+ * and leaf regions of C columns (mg_carry_ladder_plan). */
 #ifndef MG_CARRY_H
 #define MG_CARRY_H
 
@@ -56,7 +64,7 @@ struct mg_carry_dev_job {
     uint32_t* leaves;           /* its leaf region [n_leaves][8][lanes] */
     uint64_t prog_seed;
     uint32_t n_leaves;
-    uint32_t pad;
+    uint32_t n_rungs;           /* mg_carry_ladder: the masks at `mask`; else 0 */
 };
 
 #define MG_CARRY_GOLD 0x9E3779B97F4A7C15ull
@@ -158,6 +166,28 @@ MG_CARRY_FN void mg_carry_fill_lane(const uint32_t* mask, const uint32_t* rows,
     for (uint32_t k = 0; k < 8; ++k) out[((uint64_t)leaf * 8 + k) * stride + col] = v[k];
 }
 
+/* the rung of column col of a job of n_rungs masks at `lanes` candidates per
+ * rung: a job with fewer rungs than the batch repeats its last one */
+MG_CARRY_FN uint32_t mg_carry_rung(uint32_t col, uint32_t lanes, uint32_t n_rungs) {
+    const uint32_t r = col / lanes;
+    return r < n_rungs ? r : n_rungs - 1;
+}
+
+/* The rung fill kernel's lane function: leaf `leaf` of column `col` of a job
+ * whose n_rungs masks of `words` words each lie one after the other at
+ * `masks`: mg_carry_fill_lane under the mask of the column's rung, at
+ * candidate col % lanes, into out[(leaf * 8 + k) * stride + out_col]. */
+MG_CARRY_FN void mg_carry_fill_rung_lane(const uint32_t* masks, uint32_t words, uint32_t n_rungs,
+                                         const uint32_t* rows, const mg_leafgen* gen,
+                                         const uint32_t* consts, uint64_t prog_seed,
+                                         uint64_t seed, uint64_t first_index, uint32_t leaf,
+                                         uint32_t col, uint32_t lanes, uint64_t stride,
+                                         uint64_t out_col, uint32_t* out) {
+    const uint32_t r = mg_carry_rung(col, lanes, n_rungs);
+    mg_carry_fill_lane(masks + (uint64_t)r * words, rows, gen, consts, prog_seed, seed,
+                       first_index, leaf, col % lanes, stride, out_col, out);
+}
+
 /* the shared counts mg_carry_batch accepts */
 static inline bool mg_carry_shared_ok(uint32_t n_jobs, uint32_t lanes) {
     return n_jobs >= 1 && n_jobs <= MG_CARRY_MAX_JOBS && lanes >= 1 &&
@@ -183,14 +213,12 @@ static inline bool mg_cy_add(uint64_t* a, uint64_t count, uint64_t unit) {
     return !__builtin_add_overflow(*a, b, a);
 }
 
-/* Every offset of the batch's buffer and its size; false when the shared
- * counts are out of range or 64 bits overflow.  n_leaves[g] need not be below
- * max_leaves: sizes are computed with checked arithmetic.  *leaf_stride_w (u32
- * words, may be NULL): the distance between two jobs' leaf regions. */
-static inline bool mg_carry_plan(const uint32_t* n_leaves, uint32_t n_jobs, uint32_t lanes,
-                                 uint32_t max_leaves, uint64_t* offsets, uint64_t* bytes,
-                                 uint64_t* leaf_stride_w) {
-    if (!n_leaves || !offsets || !bytes || !mg_carry_shared_ok(n_jobs, lanes)) return false;
+/* The layout both calls share: job g has n_rungs[g] masks (NULL: one each),
+ * the output block out_fixed bytes per job before its rows, a leaf region
+ * `cols` columns. */
+static inline bool mg_cy_plan(const uint32_t* n_leaves, const uint32_t* n_rungs, uint32_t n_jobs,
+                              uint64_t cols, uint32_t out_fixed, uint32_t max_leaves,
+                              uint64_t* offsets, uint64_t* bytes, uint64_t* leaf_stride_w) {
     uint64_t at = 0;
     offsets[MG_CY_DESCS] = at;
     if (!mg_cy_add(&at, n_jobs, sizeof(mg_pdesc))) return false;
@@ -203,7 +231,7 @@ static inline bool mg_carry_plan(const uint32_t* n_leaves, uint32_t n_jobs, uint
         const uint64_t n = n_leaves[g];
         most = n_leaves[g] > most ? n_leaves[g] : most;
         offsets[MG_CY_OFF(g, MG_CY_MASK)] = at;
-        if (!mg_cy_add(&at, (n + 31) / 32, 4)) return false;
+        if (!mg_cy_add(&at, (n + 31) / 32 * (n_rungs ? n_rungs[g] : 1u), 4)) return false;
         offsets[MG_CY_OFF(g, MG_CY_ROWS)] = at;
         if (!mg_cy_add(&at, n, 32)) return false;
         offsets[MG_CY_OFF(g, MG_CY_GEN)] = at;
@@ -211,11 +239,11 @@ static inline bool mg_carry_plan(const uint32_t* n_leaves, uint32_t n_jobs, uint
     }
     offsets[MG_CY_OUT] = at;
     uint64_t out_b;
-    if (__builtin_mul_overflow((uint64_t)max_leaves * 32u + 8u, (uint64_t)n_jobs, &out_b))
+    if (__builtin_mul_overflow((uint64_t)max_leaves * 32u + out_fixed, (uint64_t)n_jobs, &out_b))
         return false;
     if (!mg_cy_add(&at, out_b, 1)) return false;
     uint64_t leaf_b = 0;
-    if (!mg_cy_add(&leaf_b, (uint64_t)most * 32u, lanes)) return false;
+    if (!mg_cy_add(&leaf_b, (uint64_t)most * 32u, cols)) return false;
     for (uint32_t g = 0; g < n_jobs; ++g) {
         offsets[MG_CY_OFF(g, MG_CY_LEAVES)] = at;
         if (__builtin_add_overflow(at, leaf_b, &at)) return false;
@@ -223,6 +251,47 @@ static inline bool mg_carry_plan(const uint32_t* n_leaves, uint32_t n_jobs, uint
     *bytes = at;
     if (leaf_stride_w) *leaf_stride_w = leaf_b / 4;
     return true;
+}
+
+/* Every offset of the batch's buffer and its size; false when the shared
+ * counts are out of range or 64 bits overflow.  n_leaves[g] need not be below
+ * max_leaves: sizes are computed with checked arithmetic.  *leaf_stride_w (u32
+ * words, may be NULL): the distance between two jobs' leaf regions. */
+static inline bool mg_carry_plan(const uint32_t* n_leaves, uint32_t n_jobs, uint32_t lanes,
+                                 uint32_t max_leaves, uint64_t* offsets, uint64_t* bytes,
+                                 uint64_t* leaf_stride_w) {
+    if (!n_leaves || !offsets || !bytes || !mg_carry_shared_ok(n_jobs, lanes)) return false;
+    return mg_cy_plan(n_leaves, nullptr, n_jobs, lanes, 8, max_leaves, offsets, bytes,
+                      leaf_stride_w);
+}
+
+/* the shared counts mg_carry_ladder accepts; *cols (may be NULL): the columns
+ * of a job, the batch's largest n_rungs x lanes */
+static inline bool mg_carry_ladder_ok(const uint32_t* n_rungs, uint32_t n_jobs, uint32_t lanes,
+                                      uint32_t* cols) {
+    if (!n_rungs || !mg_carry_shared_ok(n_jobs, lanes)) return false;
+    uint32_t most = 0;
+    for (uint32_t g = 0; g < n_jobs; ++g) {
+        if (n_rungs[g] < 1 || n_rungs[g] > MG_CARRY_MAX_RUNGS) return false;
+        most = n_rungs[g] > most ? n_rungs[g] : most;
+    }
+    if ((uint64_t)most * lanes > MG_REPAIR_MAX_LANES) return false;
+    if (cols) *cols = most * lanes;
+    return true;
+}
+
+/* mg_carry_plan for mg_carry_ladder: masks of n_rungs[g] x words, an output
+ * block of first, rung and rows, leaf regions of the batch's largest n_leaves
+ * x 8 x C words. */
+static inline bool mg_carry_ladder_plan(const uint32_t* n_leaves, const uint32_t* n_rungs,
+                                        uint32_t n_jobs, uint32_t lanes, uint32_t max_leaves,
+                                        uint64_t* offsets, uint64_t* bytes,
+                                        uint64_t* leaf_stride_w) {
+    uint32_t cols = 0;
+    if (!n_leaves || !offsets || !bytes || !mg_carry_ladder_ok(n_rungs, n_jobs, lanes, &cols))
+        return false;
+    return mg_cy_plan(n_leaves, n_rungs, n_jobs, cols, 16, max_leaves, offsets, bytes,
+                      leaf_stride_w);
 }
 
 #endif

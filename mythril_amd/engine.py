@@ -40,7 +40,8 @@ EXPORTS = ("mg_init", "mg_init_layout", "mg_layouts", "mg_free", "mg_last_error"
            "mg_walk_uf_mutate_host", "mg_walk_sum", "mg_walk_sum_mutate_host", "mg_walk_batch",
            "mg_walk_batch_plan_host", "mg_walk_batch_shape_ok_host", "mg_census_batch",
            "mg_census_batch_plan_host", "mg_census_batch_blocks_host", "mg_batch_witness",
-           "mg_carry_batch", "mg_carry_fill_host", "mg_carry_plan_host")
+           "mg_carry_batch", "mg_carry_fill_host", "mg_carry_plan_host", "mg_carry_ladder",
+           "mg_carry_fill_rungs_host", "mg_carry_ladder_plan_host")
 
 
 def layouts() -> Dict[int, Tuple[int, int]]:
@@ -125,8 +126,15 @@ class CarryJob(C.Structure):
     _fields_ = [("prog", C.c_void_p), ("pin_rows", C.c_void_p), ("pin_mask", C.c_void_p)]
 
 
+class CarryLadderJob(C.Structure):
+    """mg_carry_ladder_job (include/mythgpu.h): one job of mg_carry_ladder."""
+    _fields_ = [("prog", C.c_void_p), ("pin_rows", C.c_void_p), ("pin_masks", C.c_void_p),
+                ("n_rungs", C.c_uint32), ("pad", C.c_uint32)]
+
+
 # include/mythgpu.h
 CARRY_MAX_JOBS = 256
+CARRY_MAX_RUNGS = 8
 CARRY_MAX_LANES = 1 << 20
 CARRY_SHARED = 4
 CARRY_JOB_REGIONS = 4
@@ -223,6 +231,12 @@ def load_library(path: str = _LIB_PATH, check_digest: bool = True):
                                        p]
         lib.mg_carry_fill_host.argtypes = [p, u32, p, u32, u64, p, p, u64, u64, u32, u32, u32, p, p]
         lib.mg_carry_plan_host.argtypes = [p, u32, u32, u32, p, C.POINTER(u64), C.POINTER(u64)]
+        lib.mg_carry_ladder.argtypes = [p, C.POINTER(CarryLadderJob), u32, C.POINTER(Gen), u32, p,
+                                        p, p, u32, p]
+        lib.mg_carry_fill_rungs_host.argtypes = [p, u32, p, u32, u64, p, p, u32, u64, u64, u32, u32,
+                                                 u32, u32, p]
+        lib.mg_carry_ladder_plan_host.argtypes = [p, p, u32, u32, u32, p, C.POINTER(u64),
+                                                  C.POINTER(u64)]
         lib.mg_batch_create.argtypes = [p, C.POINTER(p), u32, C.POINTER(p)]
         lib.mg_batch_free.argtypes = [p]
         lib.mg_batch_free.restype = None
@@ -511,6 +525,63 @@ class Engine:
                 res = (f, wit[i, :k].copy() if f >= 0 else None)
                 if want_fill:
                     res += (fill[i, :k * 8 * lanes].reshape(k, 8, lanes).copy(),)
+                out.append(res)
+        return out
+
+    def carry_ladder(self, jobs, seed: int, first_index: int, lanes: int, want_fill: bool = False):
+        """:meth:`carry_batch` with a ladder of pin masks per job, all rungs of
+        all jobs in one launch sequence (mg_carry_ladder).
+        ``jobs``: a list of ``(lp, pin_rows, pin_masks)`` — a program loaded
+        with its leaf generators, rows ``(n_leaves, 8)`` uint32 and masks
+        ``(n_rungs, (n_leaves + 31) // 32)`` uint32, strictest first, 1 to
+        ``CARRY_MAX_RUNGS`` of them (``carry.rungs`` builds both).  With R the
+        largest ``n_rungs`` of a batch a job has ``R * lanes`` columns: column
+        c lies on rung ``min(c // lanes, n_rungs - 1)`` and evaluates the pin
+        rows on the leaves that rung pins and the generator's candidate
+        ``first_index + c % lanes`` on the others.  Returns per job ``(first,
+        rung, leaves)``: the lowest column on which every root holds, its rung
+        (both -1: none) and its leaf rows ``(n_leaves, 8)`` (None when there is
+        none); with ``want_fill`` a fourth element, the job's leaf region
+        ``(n_leaves, 8, R * lanes)`` as the device filled it.  More than
+        ``CARRY_MAX_JOBS`` jobs run as consecutive batches, each with its own
+        R; the results do not depend on the split, since a job's lowest true
+        column lies below its own ``n_rungs * lanes``."""
+        jobs = [(lp, np.ascontiguousarray(r, dtype=np.uint32).reshape(-1, 8),
+                 np.ascontiguousarray(m, dtype=np.uint32)) for lp, r, m in jobs]
+        for lp, r, m in jobs:
+            n = len(lp.program.leaves)
+            if r.shape[0] != n or m.ndim != 2 or m.shape[1] != (n + 31) // 32 or \
+                    not 1 <= m.shape[0] <= CARRY_MAX_RUNGS:
+                raise ValueError("pin rows must be (n_leaves, 8) and the pin masks (n_rungs, "
+                                 "(n_leaves + 31) // 32) with 1 to %d rungs" % CARRY_MAX_RUNGS)
+        g = Gen(seed & (2**64 - 1), first_index)
+        out = []
+        for lo in range(0, len(jobs), CARRY_MAX_JOBS):
+            part = jobs[lo:lo + CARRY_MAX_JOBS]
+            n = len(part)
+            arr = (CarryLadderJob * n)()
+            for i, (lp, r, m) in enumerate(part):
+                arr[i].prog, arr[i].pin_rows, arr[i].pin_masks = lp.handle, _ptr(r), _ptr(m)
+                arr[i].n_rungs = m.shape[0]
+            counts = [len(lp.program.leaves) for lp, _, _ in part]
+            cols = max(m.shape[0] for _, _, m in part) * lanes
+            max_leaves = max(1, max(counts))
+            first = np.full(n, -1, dtype=np.int64)
+            rung = np.full(n, -1, dtype=np.int64)
+            wit = np.zeros((n, max_leaves, 8), dtype=np.uint32)
+            fill = None
+            if want_fill:
+                _, _, stride = carry_ladder_plan_host(counts, [m.shape[0] for _, _, m in part],
+                                                      lanes, max_leaves)
+                fill = np.zeros((n, max(1, stride)), dtype=np.uint32)
+            rc = self.lib.mg_carry_ladder(self._ctx, arr, n, C.byref(g), lanes, _ptr(first),
+                                          _ptr(rung), _ptr(wit), max_leaves, _ptr(fill))
+            self._check(rc, "mg_carry_ladder")
+            for i, k in enumerate(counts):
+                f = int(first[i])
+                res = (f, int(rung[i]), wit[i, :k].copy() if f >= 0 else None)
+                if want_fill:
+                    res += (fill[i, :k * 8 * cols].reshape(k, 8, cols).copy(),)
                 out.append(res)
         return out
 
@@ -1199,6 +1270,60 @@ def carry_fill_host(leafgen: Sequence[LeafGen], consts: np.ndarray, prog_seed: i
     if rc != 0:
         raise EngineError("mg_carry_fill_host refused its arguments (%d)" % rc)
     return (out, cls) if want_classes else out
+
+
+def carry_ladder_plan_host(n_leaves: Sequence[int], n_rungs: Sequence[int], lanes: int,
+                           max_leaves: int):
+    """Host-only: :func:`carry_plan_host` for mg_carry_ladder
+    (mg_carry_ladder_plan_host): the same regions under the same indices, a
+    job's mask region holding its ``n_rungs`` masks and every leaf region the
+    largest ``n_rungs`` x ``lanes`` columns.  :class:`EngineError` where the
+    library refuses: counts out of range, more than 2^20 columns or sizes
+    beyond 64 bits."""
+    lib = load_library(check_digest=False)
+    counts = np.ascontiguousarray(n_leaves, dtype=np.uint32)
+    rungs = np.ascontiguousarray(n_rungs, dtype=np.uint32)
+    n = counts.shape[0]
+    if rungs.shape[0] != n:
+        raise ValueError("one n_rungs per job")
+    offs = np.zeros(CARRY_SHARED + max(1, n) * CARRY_JOB_REGIONS, dtype=np.uint64)
+    total, stride = C.c_uint64(0), C.c_uint64(0)
+    rc = lib.mg_carry_ladder_plan_host(_ptr(counts), _ptr(rungs), n, lanes, max_leaves,
+                                       _ptr(offs), C.byref(total), C.byref(stride))
+    if rc != 0:
+        raise EngineError("carry_ladder: %d jobs at %d lanes: counts out of range, too many "
+                          "columns or a buffer beyond 64 bits" % (n, lanes))
+    return offs[:CARRY_SHARED + n * CARRY_JOB_REGIONS], int(total.value), int(stride.value)
+
+
+def carry_fill_rungs_host(leafgen: Sequence[LeafGen], consts: np.ndarray, prog_seed: int,
+                          pin_rows: np.ndarray, pin_masks: np.ndarray, seed: int,
+                          first_index: int, lanes: int, cols: Optional[int] = None, col0: int = 0,
+                          n_cols: Optional[int] = None):
+    """Host-only: columns ``col0 .. col0 + n_cols - 1`` of one mg_carry_ladder
+    job as the rung fill kernel writes them (mg_carry_fill_rungs_host, the
+    kernel's own lane function): ``(n_leaves, 8, n_cols)`` uint32.  ``cols``:
+    the job's columns in its batch (default: its own ``n_rungs * lanes``)."""
+    lib = load_library(check_digest=False)
+    gens = list(leafgen)
+    n = len(gens)
+    garr = (LeafGen * max(1, n))(*gens)
+    consts = np.ascontiguousarray(consts, dtype=np.uint32).reshape(-1, 8)
+    rows = np.ascontiguousarray(pin_rows, dtype=np.uint32).reshape(-1, 8)
+    masks = np.ascontiguousarray(pin_masks, dtype=np.uint32)
+    if rows.shape[0] != n or masks.ndim != 2 or masks.shape[1] != (n + 31) // 32:
+        raise ValueError("pin rows must be (n_leaves, 8) and the pin masks (n_rungs, "
+                         "(n_leaves + 31) // 32)")
+    cols = masks.shape[0] * lanes if cols is None else cols
+    n_cols = cols - col0 if n_cols is None else n_cols
+    out = np.zeros((n, 8, max(0, n_cols)), dtype=np.uint32)
+    rc = lib.mg_carry_fill_rungs_host(C.cast(garr, C.c_void_p), n, _ptr(consts), consts.shape[0],
+                                      prog_seed & (2**64 - 1), _ptr(rows), _ptr(masks),
+                                      masks.shape[0], seed & (2**64 - 1), first_index, lanes, cols,
+                                      col0, max(0, n_cols), _ptr(out))
+    if rc != 0:
+        raise EngineError("mg_carry_fill_rungs_host refused its arguments (%d)" % rc)
+    return out
 
 
 def census_batch_blocks_host(n_jobs: int, n: int) -> int:

@@ -127,6 +127,7 @@ class SolverStatistics:
         self.kernel_calls = 0           # engine calls whose device time kernel_time sums
         self.launches = 0               # kernel launches of those calls (_count_kernel)
         self.carry_gated = 0            # extensions not carried: a carried table above the cap
+        self.carry_rung_hits = [0, 0, 0]  # the ladder's hits per rung (carry.RUNG_NAMES)
         self.phase = {k: 0.0 for k in PHASES}
 
     def gpu_report(self) -> str:
@@ -135,9 +136,11 @@ class SolverStatistics:
                 self.repair_attempts, self.repair_hits,
                 " batches: {}".format(self.repair_batches) if self.repair_batches else "")
             if self.repair_attempts or self.repair_hits else "") + (
-            "\nGPU carry: exact: {} attempts: {} hits: {} candidates: {}{}".format(
+            "\nGPU carry: exact: {} attempts: {} hits: {} candidates: {}{}{}".format(
                 self.carry_exact, self.carry_attempts, self.carry_hits, self.carry_candidates,
-                " table-gated: {}".format(self.carry_gated) if self.carry_gated else "")
+                " table-gated: {}".format(self.carry_gated) if self.carry_gated else "",
+                " rung hits: {}".format("/".join(map(str, self.carry_rung_hits)))
+                if any(self.carry_rung_hits) else "")
             if self.carry_exact or self.carry_attempts or self.carry_gated else "")
 
     def _gpu_report(self) -> str:
@@ -241,7 +244,9 @@ REPAIR_BATCH = False
 # opt-in (MYTHRIL_GPU_CARRY=1): a group that found a witness is remembered
 # (_group_hit); an exact repeat is answered from the memo and a group that
 # extends remembered groups is evaluated once under their witnesses before it
-# is compiled for a search (carry.py); unset, nothing changes
+# is compiled for a search (carry.py); unset, nothing changes.
+# MYTHRIL_GPU_CARRY=2 ("ladder"): the same with the constant-keyed eval form
+# and a ladder of pin sets per group in one launch sequence
 CARRY = False
 SHAPE_MIN, SHAPE_FLOOR, SHAPE_PROBE = 4, 1.0 / 16, 8
 
@@ -268,6 +273,7 @@ def configure_from_env(env=None) -> None:
     search missed to one batched walk (``repair.repair_groups``);
     ``MYTHRIL_GPU_CARRY=1`` (off by default) remembers the witnesses of groups
     and evaluates them on the groups that extend them (``carry.py``),
+    ``MYTHRIL_GPU_CARRY=2`` does so with a ladder of pin sets per group,
     ``MYTHRIL_GPU_CARRY_LANES`` the candidates of such an evaluation when the
     extension has fresh symbols, ``MYTHRIL_GPU_CARRY_MAX_ENTRIES`` the largest
     carried table an extension is evaluated with."""
@@ -294,7 +300,8 @@ def configure_from_env(env=None) -> None:
         "1", "on", "true", "yes")
     REPAIR_BATCH = env.get("MYTHRIL_GPU_REPAIR_BATCH", "0").strip().lower() in (
         "1", "on", "true", "yes")
-    CARRY = env.get("MYTHRIL_GPU_CARRY", "0").strip().lower() in ("1", "on", "true", "yes")
+    CARRY = "ladder" if env.get("MYTHRIL_GPU_CARRY", "0").strip() == "2" else \
+        env.get("MYTHRIL_GPU_CARRY", "0").strip().lower() in ("1", "on", "true", "yes")
     if env.get("MYTHRIL_GPU_CARRY_LANES"):
         from . import carry
         carry.CARRY_LANES = min(1 << 20, max(1, int(env["MYTHRIL_GPU_CARRY_LANES"])))
@@ -742,9 +749,12 @@ def _carry_groups(groups, eng=None):
     with no launch (their program: the group's cached search program, else the
     one that evidenced the hit); the groups that extend remembered groups go
     into ONE ``Engine.carry_batch`` call on the first device, deduplicated by
-    key.  A group missing from the result goes on as before."""
+    key (with ``CARRY == "ladder"``: one ``Engine.carry_ladder`` call, every
+    group with its rungs).  A group missing from the result goes on as
+    before."""
     from . import carry
     out, jobs = {}, {}
+    ladder = CARRY == "ladder"
     cache = _SEARCH_CACHE or {}
     for key, nodes in groups:
         if key in out or key in jobs or not key:
@@ -758,27 +768,33 @@ def _carry_groups(groups, eng=None):
                 continue
             stats.carry_exact += 1
             out[key] = (what[1], prog)
-        elif max(carry.table_sizes(what[1]).values(), default=0) > carry.MAX_ENTRIES:
+        elif max((carry.table_sizes_ck(nodes, what[1]) if ladder else
+                  carry.table_sizes(what[1])).values(), default=0) > carry.MAX_ENTRIES:
             # the eval form reads a table entry by entry: a carried table of
             # this size makes the compile dearer than the search it may save
+            # (the ladder's form reads entries at constant keys as leaves, so
+            # only the others count)
             stats.carry_gated += 1
         else:
-            jobs[key] = (nodes, what[1])
+            jobs[key] = (nodes, what[1], what[2]) if ladder else (nodes, what[1])
     if jobs:
         eng = eng or get_engine((list(DEVICES) or [0])[0])
-        res = carry.run(eng, list(jobs.values()), SEARCH_SEED, search_leafgen, phase=_Phase)
+        res = (carry.run_ladder if ladder else carry.run)(eng, list(jobs.values()), SEARCH_SEED,
+                                                          search_leafgen, phase=_Phase)
         ran = [r for r in res if r is not None]
         if ran:
             # fill (when any job has a leaf), interpreter, gather
-            _count_kernel(eng, 3 if any(len(p.leaves) for _, p, _ in ran) else 2)
+            _count_kernel(eng, 3 if any(len(r[1].leaves) for r in ran) else 2)
         for key, r in zip(jobs, res):
             if r is None:                  # no eval form (Unsupported): nothing ran
                 continue
             stats.carry_attempts += 1
-            asg, prog, n = r
+            asg, prog, n = r[:3]
             stats.carry_candidates += n
             if asg is not None:
                 stats.carry_hits += 1
+                if ladder:
+                    stats.carry_rung_hits[r[3]] += 1
                 _note_hit(key, asg, prog)
                 out[key] = (asg, prog)
     return out

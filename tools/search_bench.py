@@ -143,7 +143,9 @@ def shape_lines(eng, n_queries, n_sample=48):
                     "carry": {"on": M.CARRY, "exact": M.stats.carry_exact,
                               "attempts": M.stats.carry_attempts, "hits": M.stats.carry_hits,
                               "candidates": M.stats.carry_candidates,
-                              "table_gated": M.stats.carry_gated},
+                              "table_gated": M.stats.carry_gated,
+                              # MYTHRIL_GPU_CARRY=2 (§3.19): hits per rung
+                              "rung_hits": list(M.stats.carry_rung_hits)},
                     # kernel launches per query (a search: its launches and the
                     # witness regeneration; a carry: fill, interpreter, gather)
                     # and the engine calls that made them
