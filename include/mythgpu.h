@@ -791,6 +791,88 @@ int mg_carry_ladder_plan_host(const uint32_t* n_leaves /*[n_jobs]*/,
                               uint32_t lanes, uint32_t max_leaves, uint64_t* out_offsets,
                               uint64_t* out_bytes, uint64_t* out_leaf_stride_w);
 
+/* The census of a pin ladder (csrc/mg_carry.h,
+ * mg_carry_census.hip): mg_carry_ladder's columns, and instead of the lowest
+ * true column alone a verdict census of every rung and `walkers` (W) start
+ * columns per job — why a ladder missed, and where a walk would begin.
+ * A job is a ladder job whose program carries its verdict mask as probes
+ * mask_probe0 .. (mythril_amd/census.py mask_probes; load the census_view), and
+ * its n_roots.  Columns are mg_carry_ladder's: C = R x lanes, R the batch's
+ * largest n_rungs.  Rung r of job j is censused over its own columns
+ * r x lanes .. r x lanes + lanes - 1 as mg_census does over candidates, with
+ * column numbers for indices; the surplus columns of a job with fewer rungs
+ * than R are evaluated and not counted.
+ * counts: [n_jobs][R][5 x max_roots + 2] u64.  Block (j, r) holds, at its
+ * front and for n = n_roots of job j, the counters as the device keeps them:
+ * pass [n], first_block [n], sole_block [n], nfail_hist [n + 1], sole_index
+ * [n] (all ones: none) and best = failing roots << 53 | column (all ones: no
+ * column).  Blocks of rungs a job does not have, and words past a block's
+ * 5 n + 2, are zero.
+ * The start rule.  For rung r let (f_r, b_r) be its best: failing roots and
+ * column.  The list of a job is first the bests of its rungs ordered by
+ * (f_r, r) ascending; then, for r = 0 .. n_rungs - 1 and k = 0 .. n_roots - 1
+ * in that order, every sole_index[r][k] that is set and is not b_r (1 failing
+ * root each).  Start w is list[w]; past the end of the list it is list[0].
+ * No column comes twice before the padding: rungs own disjoint column ranges;
+ * a column is the sole candidate of at most one root; and a best with one
+ * failing root is the lowest sole column of that root, the entry the rule
+ * leaves out.  start_col [n_jobs][W], start_nfail [n_jobs][W], starts
+ * [n_jobs][W][max_leaves][8]: the columns, their failing roots and their leaf
+ * rows, zero past the program's leaves.  Start 0 is the ladder's answer: when
+ * start_nfail[j][0] is 0, start_col[j][0] is mg_carry_ladder's first, its
+ * rung start_col / lanes and starts[j][0] its leaves.
+ * One call is a fixed sequence whatever n_jobs, with no host synchronisation
+ * inside: one upload (descriptors, records, masks, rows, generator tables and
+ * every counter block preset), the rung fill launch, one eval-mode interpreter
+ * launch over the job axis at C candidates writing every job's probe region,
+ * the census launch (grid tiles x R x jobs), the starts launch (one block per
+ * job), one download.  mg_last_kernel_ms covers the four launches.  fill_out:
+ * as mg_carry_ladder.
+ * Refused with MG_E_ARG before any upload or launch, the message beginning
+ * "carry_census:": whatever mg_carry_ladder refuses; walkers outside
+ * 1..MG_CARRY_MAX_WALKERS; n_roots outside 1..1024 or above max_roots; mask
+ * probes outside the program's probes. */
+#define MG_CARRY_MAX_WALKERS 64u
+typedef struct mg_carry_census_job {
+    mg_carry_ladder_job ladder;
+    uint32_t n_roots;           /* 1..1024 */
+    uint32_t mask_probe0;       /* the first probe of the verdict mask */
+} mg_carry_census_job;
+int mg_carry_census(mg_ctx* ctx, const mg_carry_census_job* jobs, uint32_t n_jobs,
+                    const mg_gen* gen, uint32_t lanes, uint32_t walkers, uint32_t max_roots,
+                    uint32_t max_leaves, uint64_t* counts /*[n_jobs][R][5 max_roots + 2]*/,
+                    int64_t* start_col /*[n_jobs][W]*/, uint32_t* start_nfail /*[n_jobs][W]*/,
+                    uint32_t* starts /*[n_jobs][W][max_leaves][8]*/,
+                    uint32_t* fill_out /*NULL, or every job's leaf region copied back*/);
+/* Host-only (no GPU): the plan of the device buffer mg_carry_census uses.
+ * out_offsets: mg_carry_ladder_plan_host's table — the same regions under the
+ * same indices — followed by MG_CARRY_CENSUS_SHARED entries (the census
+ * records) and MG_CARRY_CENSUS_JOB_REGIONS per job (its counter blocks, its
+ * probe region).  In address order: descriptors, records, first words, every
+ * job's masks, rows and generators — at the ladder's own offsets —, the census
+ * records, every job's counter blocks (mg_census_words(n_roots) x n_rungs u64),
+ * the output block, all leaf regions (the ladder's stride), all probe regions
+ * (*out_probe_stride_w: the batch's largest n_probes x 8 x C words rounded up
+ * to 256 bytes); every region 256-byte aligned.  MG_E_ARG for what
+ * mg_carry_ladder_plan_host refuses, walkers outside 1..64, an n_roots outside
+ * 1..1024, mask probes outside n_probes and sizes beyond 64 bits. */
+#define MG_CARRY_CENSUS_SHARED 1
+#define MG_CARRY_CENSUS_JOB_REGIONS 2
+int mg_carry_census_plan_host(const uint32_t* n_leaves /*[n_jobs]*/,
+                              const uint32_t* n_rungs /*[n_jobs]*/,
+                              const uint32_t* n_roots /*[n_jobs]*/,
+                              const uint32_t* n_probes /*[n_jobs]*/,
+                              const uint32_t* mask_probe0 /*[n_jobs]*/, uint32_t n_jobs,
+                              uint32_t lanes, uint32_t walkers, uint32_t max_leaves,
+                              uint64_t* out_offsets, uint64_t* out_bytes,
+                              uint64_t* out_leaf_stride_w, uint64_t* out_probe_stride_w);
+/* Host-only (no GPU): the start rule on one job's counter blocks
+ * ([n_rungs][5 n_roots + 2] u64, one after the other): start_col and
+ * start_nfail [walkers]; -1 and 0xFFFFFFFF when no rung counted a column.
+ * MG_E_ARG for a null pointer and counts out of range. */
+int mg_carry_starts_host(const uint64_t* counts, uint32_t n_roots, uint32_t n_rungs,
+                         uint32_t walkers, int64_t* start_col, uint32_t* start_nfail);
+
 /* Corpus batches: many programs, one launch.  Device-pointer API for
  * resident benchmarking; stream is a hipStream_t (NULL = the context's own
  * stream, which the synchronous calls also use).

@@ -380,6 +380,129 @@ def run_ladder(eng, items, seed: int, leafgen, lanes: Optional[int] = None, phas
     return out
 
 
+# ---------------------------------------------------------------------------
+# The census of a ladder (MYTHRIL_GPU_CARRY=3): which roots
+# block on which rung, and the columns a walk starts from
+# ---------------------------------------------------------------------------
+
+CARRY_WALKERS = 4              # MYTHRIL_GPU_CARRY_WALKERS: start columns per job
+MAX_WALKERS = 64               # include/mythgpu.h MG_CARRY_MAX_WALKERS
+
+
+def starts_ref(censuses, walkers: int) -> Tuple[np.ndarray, np.ndarray]:
+    """The start rule of mg_carry_census (include/mythgpu.h states it), on the
+    censuses of a job's rungs over their own columns: ``(start_col,
+    start_nfail)``, ``walkers`` entries each.  The list is first the bests of
+    the rungs ordered by (failing roots, rung) ascending; then, rung by rung and
+    root by root, every ``sole_index`` that is set and is not its rung's best
+    column, with 1 failing root.  Start w is list[w]; past the end of the list
+    it is list[0] (-1 and 0xFFFFFFFF when no rung counted a column)."""
+    cs = list(censuses)
+    lst = [(int(c.best_index), int(c.best_nfail))
+           for _, c in sorted(enumerate(cs), key=lambda rc: (rc[1].best_nfail, rc[0]))
+           if c.best_index >= 0]
+    for c in cs:
+        for k in range(c.n_roots):
+            s = int(c.sole_index[k])
+            if s >= 0 and s != c.best_index:
+                lst.append((s, 1))
+    pad = lst[0] if lst else (-1, 0xFFFFFFFF)
+    lst = (lst + [pad] * walkers)[:walkers]
+    return (np.array([c for c, _ in lst], dtype=np.int64),
+            np.array([f for _, f in lst], dtype=np.uint32))
+
+
+def compile_census_ck(nodes, asg: Assignment, probes, sizes: Optional[Dict[str, int]] = None
+                      ) -> Program:
+    """:func:`compile_eval_ck` with caller probes (``census.mask_probes(nodes)``
+    first, for a census; the repair's trees add theirs): the same table sizes
+    and the same cache, under a key that names the probes."""
+    probes = list(probes)
+    sizes = table_sizes_ck(nodes, asg) if sizes is None else sizes
+    key = ("ck-probes", tuple(n.id for n in nodes), tuple(p.id for p in probes),
+           tuple(sorted(sizes.items())))
+    prog = _EVAL_CACHE.get(key)
+    if prog is not None:
+        _EVAL_CACHE.move_to_end(key)
+        return prog
+    prog = compile_constraints(nodes, probes, solve=False, leaf_pools=True, const_keys=True,
+                               table_sizes=sizes or None)
+    _EVAL_CACHE[key] = prog
+    if len(_EVAL_CACHE) > EVAL_CACHE_SIZE:
+        _EVAL_CACHE.popitem(last=False)
+    return prog
+
+
+def run_census(eng, items, seed: int, leafgen, lanes: Optional[int] = None,
+               walkers: Optional[int] = None, phase=None):
+    """:func:`run_ladder` with a census in place of the gather: one
+    ``Engine.carry_census`` call for ``items``, a list of ``(nodes, assignment,
+    taken_keys)``.  Per item a dict — ``program`` (the constant-keyed eval form
+    with the verdict mask of ``nodes`` as its first probes), ``kept`` (the
+    indices in ``RUNG_NAMES`` of the rungs that ran), ``censuses`` (one
+    ``census.Census`` per kept rung over that rung's columns), ``start_col``,
+    ``start_nfail``, ``starts`` (``Engine.carry_census``), ``lanes``,
+    ``assignment`` (start 0 unpacked when it fails no root, else None) and
+    ``rung`` (its index in ``RUNG_NAMES``, -1 on a miss) — or None where the
+    group has no eval form or more roots than a census takes."""
+    import contextlib
+    from . import census as CS
+    from .ir import Unsupported
+    phase = phase or (lambda name: contextlib.nullcontext())
+    lanes = CARRY_LANES if lanes is None else lanes
+    walkers = CARRY_WALKERS if walkers is None else walkers
+    jobs, progs, free, kept, where = [], [], [], [], []
+    with phase("compile"):
+        for k, (nodes, asg, taken) in enumerate(items):
+            if not 1 <= len(nodes) <= CS.MAX_ROOTS:
+                continue
+            try:
+                probes = CS.mask_probes(nodes)
+                prog = compile_census_ck(nodes, asg, probes)
+                rows, ladder = rung_masks(prog, asg, *split_nodes(nodes, taken))
+            except (Unsupported, ValueError):
+                continue
+            keep = distinct(ladder)
+            progs.append(prog)
+            kept.append(keep)
+            free.append([n_free(prog, ladder[r]) for r in keep])
+            jobs.append((CS.census_view(prog, len(probes)), rows, ladder[keep], len(nodes)))
+            where.append(k)
+    out: List = [None] * len(items)
+    if not jobs:
+        return out
+    width = max(1, int(lanes)) if any(any(f) for f in free) else 1
+    width = min(width, (1 << 20) // max(len(keep) for keep in kept))   # the call's column cap
+    with phase("load"):
+        loaded = [(eng.load(p, leafgen(p), prog_seed=0), r, m, n) for p, r, m, n in jobs]
+    with phase("search"):
+        res = eng.carry_census(loaded, seed, 0, width, walkers)
+        for k, prog, keep, (cs, col, nfail, rows) in zip(where, progs, kept, res):
+            hit = int(nfail[0]) == 0
+            out[k] = {"program": prog, "kept": keep, "censuses": cs, "start_col": col,
+                      "start_nfail": nfail, "starts": rows, "lanes": width,
+                      "assignment": unpack(prog, rows[0]) if hit else None,
+                      "rung": keep[int(col[0]) // width] if hit else -1}
+    return out
+
+
+def miss_report(nodes, censuses, kept_rungs) -> List[dict]:
+    """Why a ladder missed: per kept rung ``{"rung": its name in RUNG_NAMES,
+    "n_cand", "best_nfail", "blockers": [{"root": position of the constraint in
+    ``nodes``, "constraint": its text, "pass", "first_block", "sole_block"}]}``
+    with ``Census.blockers()`` in its order, worst first."""
+    nodes = list(nodes)
+    out = []
+    for r, c in zip(kept_rungs, censuses):
+        out.append({"rung": RUNG_NAMES[r], "n_cand": int(c.n_cand),
+                    "best_nfail": int(c.best_nfail),
+                    "blockers": [{"root": k, "constraint": repr(nodes[k]),
+                                  "pass": int(c.pass_[k]),
+                                  "first_block": int(c.first_block[k]),
+                                  "sole_block": int(c.sole_block[k])} for k in c.blockers()]})
+    return out
+
+
 def run(eng, items, seed: int, leafgen, lanes: Optional[int] = None, phase=None):
     """One ``Engine.carry_batch`` call for ``items``, a list of ``(nodes,
     assignment)``: per item ``(assignment, program, candidates)`` — the witness

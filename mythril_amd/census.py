@@ -177,6 +177,41 @@ def reduce_bits(bits: np.ndarray, first_index: int) -> Census:
                   np.bincount(nfail, minlength=r + 1).astype(np.int64), best_nfail, best_index)
 
 
+def pack_block(c: Census) -> np.ndarray:
+    """The device counter block of a census (csrc/mg_census.h; include/mythgpu.h
+    describes it above mg_carry_census): 5 n + 2 uint64 — pass, first_block,
+    sole_block, nfail_hist (n + 1), sole_index (all ones: none), best = failing
+    roots << 53 | offset from ``first_index`` (all ones over an empty range).
+    mg_carry_census counts columns from 0, so there the offset is the index."""
+    n = c.n_roots
+    ones = np.uint64(2**64 - 1)
+    sole = np.where(np.asarray(c.sole_index) < 0, ones,
+                    np.asarray(c.sole_index).astype(np.uint64))
+    best = ones if c.best_index < 0 else np.uint64((int(c.best_nfail) << 53) | int(c.best_index))
+    return np.concatenate([np.asarray(c.pass_, dtype=np.uint64),
+                           np.asarray(c.first_block, dtype=np.uint64),
+                           np.asarray(c.sole_block, dtype=np.uint64),
+                           np.asarray(c.nfail_hist, dtype=np.uint64)[:n + 1], sole,
+                           np.array([best], dtype=np.uint64)])
+
+
+def unpack_block(block: np.ndarray, n_roots: int, first_index: int, n_cand: int,
+                 kernel_ms: float = 0.0) -> Census:
+    """:func:`pack_block` backwards for a block whose indices are absolute
+    (mg_carry_census: column numbers)."""
+    n = n_roots
+    b = np.asarray(block, dtype=np.uint64)
+    ones = np.uint64(2**64 - 1)
+    sole = b[4 * n + 1:5 * n + 1]
+    sole_index = np.where(sole == ones, np.int64(-1), sole.astype(np.int64))
+    best = int(b[5 * n + 1])
+    best_nfail, best_index = (n + 1, -1) if best == 2**64 - 1 else \
+        (best >> 53, best & ((1 << 53) - 1))
+    return Census(n, first_index, n_cand, b[:n].astype(np.int64), b[n:2 * n].astype(np.int64),
+                  b[2 * n:3 * n].astype(np.int64), sole_index, b[3 * n:4 * n + 1].astype(np.int64),
+                  int(best_nfail), int(best_index), kernel_ms)
+
+
 def reduce_masks(masks: np.ndarray, n_roots: int, first_index: int) -> Census:
     """Exactly the outputs of the census kernel, from host mask probes
     (n_mask, 8, n) u32 of candidates first_index ..: the kernel's

@@ -172,6 +172,18 @@ hipError_t mg_launch_carry_gather_rungs(const mg_carry_dev_job* d_jobs, uint32_t
                                         uint32_t cols, uint32_t max_leaves,
                                         long long* d_out_first, long long* d_out_rung,
                                         uint32_t* d_out_leaves, hipStream_t stream);
+// the two after mg_carry_census's (mg_carry_census.hip)
+hipError_t mg_launch_carry_census(const mg_carry_dev_job* d_jobs,
+                                  const mg_carry_census_dev_job* d_cjobs, uint32_t n_jobs,
+                                  uint32_t rungs, uint32_t lanes, uint32_t cols,
+                                  hipStream_t stream);
+hipError_t mg_launch_carry_starts(const mg_carry_dev_job* d_jobs,
+                                  const mg_carry_census_dev_job* d_cjobs, uint32_t n_jobs,
+                                  uint32_t walkers, uint32_t cols, uint32_t max_leaves,
+                                  long long* d_out_col, uint32_t* d_out_nfail,
+                                  uint32_t* d_out_rows, hipStream_t stream);
+static_assert(MG_CARRY_MAX_WALKERS == MG_WALK_MAX_WALKERS,
+              "mg_carry_census hands its starts to the walks");
 
 struct mg_ctx {
     int device = 0;
@@ -2012,6 +2024,40 @@ int mg_carry_plan_host(const uint32_t* n_leaves, uint32_t n_jobs, uint32_t lanes
                          out_leaf_stride_w) ? MG_OK : MG_E_ARG;
 }
 
+// What mg_carry_ladder refuses of the shared counts and of one job
+// (mg_carry_census asks the same); `who` begins the message.
+static int carry_ladder_check_shared(mg_ctx* ctx, const char* who, uint32_t n_jobs,
+                                     uint32_t lanes, uint32_t max_leaves) {
+    if (n_jobs < 1 || n_jobs > MG_CARRY_MAX_JOBS)
+        return fail(ctx, MG_E_ARG, "%s: %u jobs outside 1..%u", who, n_jobs, MG_CARRY_MAX_JOBS);
+    if (lanes < 1 || lanes > MG_REPAIR_MAX_LANES)
+        return fail(ctx, MG_E_ARG, "%s: %u lanes outside 1..%u", who, lanes, MG_REPAIR_MAX_LANES);
+    if (max_leaves > MG_CARRY_MAX_LEAVES)
+        return fail(ctx, MG_E_ARG, "%s: max_leaves %u above %u", who, max_leaves,
+                    MG_CARRY_MAX_LEAVES);
+    return MG_OK;
+}
+
+static int carry_ladder_check_job(mg_ctx* ctx, const char* who, uint32_t g,
+                                  const mg_carry_ladder_job& j, uint32_t max_leaves) {
+    if (!j.prog) return fail(ctx, MG_E_ARG, "%s: job %u: null program", who, g);
+    if (j.prog->ctx != ctx)
+        return fail(ctx, MG_E_ARG, "%s: job %u: a program of another context", who, g);
+    if (j.prog->n_leaves > max_leaves)
+        return fail(ctx, MG_E_ARG, "%s: job %u: %u leaves above max_leaves %u", who, g,
+                    j.prog->n_leaves, max_leaves);
+    if (j.n_rungs < 1 || j.n_rungs > MG_CARRY_MAX_RUNGS)
+        return fail(ctx, MG_E_ARG, "%s: job %u: %u rungs outside 1..%u", who, g, j.n_rungs,
+                    MG_CARRY_MAX_RUNGS);
+    if (j.prog->n_leaves && (!j.pin_rows || !j.pin_masks))
+        return fail(ctx, MG_E_ARG, "%s: job %u: null pin rows or pin masks", who, g);
+    if (j.prog->leafgen.size() != j.prog->n_leaves ||
+        !mg_carry_gen_ok(j.prog->leafgen.data(), j.prog->n_leaves, j.prog->n_consts))
+        return fail(ctx, MG_E_ARG, "%s: job %u: the program's leaf generators are not loaded",
+                    who, g);
+    return MG_OK;
+}
+
 // The pin ladder (include/mythgpu.h mg_carry_ladder, DESIGN.md §3.19;
 // csrc/mg_carry.h, mg_carry_ladder.hip): mg_carry_batch's sequence with
 // n_rungs masks per job and the largest n_rungs x lanes columns.
@@ -2021,34 +2067,14 @@ int mg_carry_ladder(mg_ctx* ctx, const mg_carry_ladder_job* jobs, uint32_t n_job
     if (!ctx) return MG_E_ARG;
     if (!jobs || !gen || !first || !rung || !leaves)
         return fail(ctx, MG_E_ARG, "carry_ladder: null argument");
-    if (n_jobs < 1 || n_jobs > MG_CARRY_MAX_JOBS)
-        return fail(ctx, MG_E_ARG, "carry_ladder: %u jobs outside 1..%u", n_jobs,
-                    MG_CARRY_MAX_JOBS);
-    if (lanes < 1 || lanes > MG_REPAIR_MAX_LANES)
-        return fail(ctx, MG_E_ARG, "carry_ladder: %u lanes outside 1..%u", lanes,
-                    MG_REPAIR_MAX_LANES);
-    if (max_leaves > MG_CARRY_MAX_LEAVES)
-        return fail(ctx, MG_E_ARG, "carry_ladder: max_leaves %u above %u", max_leaves,
-                    MG_CARRY_MAX_LEAVES);
+    int rc = carry_ladder_check_shared(ctx, "carry_ladder", n_jobs, lanes, max_leaves);
+    if (rc != MG_OK) return rc;
     std::vector<uint32_t> n_leaves(n_jobs), n_rungs(n_jobs);
     uint32_t most = 0, max_lds = 0, top = 0;
     for (uint32_t g = 0; g < n_jobs; ++g) {
         const mg_carry_ladder_job& j = jobs[g];
-        if (!j.prog) return fail(ctx, MG_E_ARG, "carry_ladder: job %u: null program", g);
-        if (j.prog->ctx != ctx)
-            return fail(ctx, MG_E_ARG, "carry_ladder: job %u: a program of another context", g);
-        if (j.prog->n_leaves > max_leaves)
-            return fail(ctx, MG_E_ARG, "carry_ladder: job %u: %u leaves above max_leaves %u", g,
-                        j.prog->n_leaves, max_leaves);
-        if (j.n_rungs < 1 || j.n_rungs > MG_CARRY_MAX_RUNGS)
-            return fail(ctx, MG_E_ARG, "carry_ladder: job %u: %u rungs outside 1..%u", g,
-                        j.n_rungs, MG_CARRY_MAX_RUNGS);
-        if (j.prog->n_leaves && (!j.pin_rows || !j.pin_masks))
-            return fail(ctx, MG_E_ARG, "carry_ladder: job %u: null pin rows or pin masks", g);
-        if (j.prog->leafgen.size() != j.prog->n_leaves ||
-            !mg_carry_gen_ok(j.prog->leafgen.data(), j.prog->n_leaves, j.prog->n_consts))
-            return fail(ctx, MG_E_ARG, "carry_ladder: job %u: the program's leaf generators are "
-                        "not loaded", g);
+        rc = carry_ladder_check_job(ctx, "carry_ladder", g, j, max_leaves);
+        if (rc != MG_OK) return rc;
         n_leaves[g] = j.prog->n_leaves;
         n_rungs[g] = j.n_rungs;
         most = n_leaves[g] > most ? n_leaves[g] : most;
@@ -2070,7 +2096,7 @@ int mg_carry_ladder(mg_ctx* ctx, const mg_carry_ladder_job* jobs, uint32_t n_job
                     n_jobs, cols, (unsigned long long)MG_WALK_BATCH_DEFAULT_BYTES);
     HIPCHECK(ctx, hipSetDevice(ctx->device));
     void* ws;
-    int rc = workspace(ctx, (size_t)bytes + 256, &ws);
+    rc = workspace(ctx, (size_t)bytes + 256, &ws);
     if (rc) return rc;
     uint8_t* w = (uint8_t*)ws;
     // the host image of everything uploaded, at the offsets of the plan
@@ -2161,6 +2187,179 @@ int mg_carry_ladder_plan_host(const uint32_t* n_leaves, const uint32_t* n_rungs,
                               uint64_t* out_bytes, uint64_t* out_leaf_stride_w) {
     return mg_carry_ladder_plan(n_leaves, n_rungs, n_jobs, lanes, max_leaves, out_offsets,
                                 out_bytes, out_leaf_stride_w) ? MG_OK : MG_E_ARG;
+}
+
+// The census of a pin ladder (include/mythgpu.h mg_carry_census, DESIGN.md
+// §3.20; csrc/mg_carry.h, mg_carry_census.hip): the ladder's fill, the
+// interpreter's launch writing every job's mask probes, a census per (job,
+// rung) and the start columns, between one upload and one download.
+int mg_carry_census(mg_ctx* ctx, const mg_carry_census_job* jobs, uint32_t n_jobs,
+                    const mg_gen* gen, uint32_t lanes, uint32_t walkers, uint32_t max_roots,
+                    uint32_t max_leaves, uint64_t* counts, int64_t* start_col,
+                    uint32_t* start_nfail, uint32_t* starts, uint32_t* fill_out) {
+    if (!ctx) return MG_E_ARG;
+    if (!jobs || !gen || !counts || !start_col || !start_nfail || !starts)
+        return fail(ctx, MG_E_ARG, "carry_census: null argument");
+    int rc = carry_ladder_check_shared(ctx, "carry_census", n_jobs, lanes, max_leaves);
+    if (rc != MG_OK) return rc;
+    if (walkers < 1 || walkers > MG_CARRY_MAX_WALKERS)
+        return fail(ctx, MG_E_ARG, "carry_census: %u walkers outside 1..%u", walkers,
+                    MG_CARRY_MAX_WALKERS);
+    std::vector<uint32_t> n_leaves(n_jobs), n_rungs(n_jobs), n_roots(n_jobs), n_probes(n_jobs),
+        probe0(n_jobs);
+    uint32_t most = 0, max_lds = 0, top = 0;
+    for (uint32_t g = 0; g < n_jobs; ++g) {
+        const mg_carry_census_job& j = jobs[g];
+        rc = carry_ladder_check_job(ctx, "carry_census", g, j.ladder, max_leaves);
+        if (rc != MG_OK) return rc;
+        if (!mg_census_roots_ok(j.n_roots))
+            return fail(ctx, MG_E_ARG, "carry_census: job %u: n_roots %u outside 1..%u", g,
+                        j.n_roots, MG_CENSUS_MAX_ROOTS);
+        if (j.n_roots > max_roots)
+            return fail(ctx, MG_E_ARG, "carry_census: job %u: n_roots %u above max_roots %u", g,
+                        j.n_roots, max_roots);
+        if (!mg_census_mask_ok(j.ladder.prog->n_probes, j.n_roots, j.mask_probe0))
+            return fail(ctx, MG_E_ARG, "carry_census: job %u: mask probes %u..%u outside the "
+                        "program's %u probes", g, j.mask_probe0,
+                        j.mask_probe0 + (j.n_roots + 255) / 256 - 1, j.ladder.prog->n_probes);
+        n_leaves[g] = j.ladder.prog->n_leaves;
+        n_rungs[g] = j.ladder.n_rungs;
+        n_roots[g] = j.n_roots;
+        n_probes[g] = j.ladder.prog->n_probes;
+        probe0[g] = j.mask_probe0;
+        most = n_leaves[g] > most ? n_leaves[g] : most;
+        top = n_rungs[g] > top ? n_rungs[g] : top;
+        max_lds = j.ladder.prog->n_lds > max_lds ? j.ladder.prog->n_lds : max_lds;
+    }
+    uint32_t cols = 0;
+    if (!mg_carry_ladder_ok(n_rungs.data(), n_jobs, lanes, &cols))
+        return fail(ctx, MG_E_ARG, "carry_census: %u rungs of %u lanes above %u columns", top,
+                    lanes, MG_REPAIR_MAX_LANES);
+    std::vector<uint64_t> off(MG_CC_TABLE(n_jobs));
+    uint64_t bytes = 0, leaf_w = 0, probe_w = 0;
+    if (mg_carry_census_plan(n_leaves.data(), n_rungs.data(), n_roots.data(), n_probes.data(),
+                             probe0.data(), n_jobs, lanes, walkers, max_leaves, off.data(),
+                             &bytes, &leaf_w, &probe_w, nullptr) != MG_CC_OK)
+        return fail(ctx, MG_E_ARG, "carry_census: the batch's buffer exceeds 64 bits");
+    if (bytes > MG_WALK_BATCH_DEFAULT_BYTES)
+        return fail(ctx, MG_E_ARG, "carry_census: %llu bytes needed for %u jobs at %u columns "
+                    "and %u walkers, at most %llu; pass fewer jobs, rungs, lanes or walkers",
+                    (unsigned long long)bytes, n_jobs, cols, walkers,
+                    (unsigned long long)MG_WALK_BATCH_DEFAULT_BYTES);
+    HIPCHECK(ctx, hipSetDevice(ctx->device));
+    void* ws;
+    rc = workspace(ctx, (size_t)bytes + 256, &ws);
+    if (rc) return rc;
+    uint8_t* w = (uint8_t*)ws;
+    // the host image of everything uploaded, at the offsets of the plan; the
+    // counters come back into it with the output block behind them
+    const size_t up_b = (size_t)off[MG_CY_OUT];
+    const size_t count0 = (size_t)off[MG_CC_OFF(n_jobs, 0, MG_CC_COUNTS)];
+    const size_t out_b = (size_t)n_jobs * (size_t)mg_carry_census_out_job(walkers, max_leaves);
+    std::vector<uint8_t> img(up_b + out_b, 0);
+    mg_pdesc* h_descs = (mg_pdesc*)(img.data() + off[MG_CY_DESCS]);
+    mg_carry_dev_job* h_jobs = (mg_carry_dev_job*)(img.data() + off[MG_CY_JOBS]);
+    mg_carry_census_dev_job* h_cjobs =
+        (mg_carry_census_dev_job*)(img.data() + off[MG_CC_BASE(n_jobs) + MG_CC_RECORDS]);
+    for (uint32_t g = 0; g < n_jobs; ++g) {
+        const mg_carry_ladder_job& j = jobs[g].ladder;
+        const uint32_t n = n_leaves[g], roots = n_roots[g];
+        auto at = [&](uint32_t k) { return off[MG_CY_OFF(g, k)]; };
+        if (n) {
+            memcpy(img.data() + at(MG_CY_MASK), j.pin_masks,
+                   (size_t)((n + 31) / 32) * 4 * j.n_rungs);
+            memcpy(img.data() + at(MG_CY_ROWS), j.pin_rows, (size_t)n * 32);
+            memcpy(img.data() + at(MG_CY_GEN), j.prog->leafgen.data(), (size_t)n * sizeof(mg_leafgen));
+        }
+        h_descs[g] = j.prog->h_desc;
+        mg_carry_dev_job& d = h_jobs[g];
+        d.mask = (const uint32_t*)(w + at(MG_CY_MASK));
+        d.rows = (const uint32_t*)(w + at(MG_CY_ROWS));
+        d.gen = (const mg_leafgen*)(w + at(MG_CY_GEN));
+        d.consts = j.prog->h_desc.consts;
+        d.leaves = (uint32_t*)(w + at(MG_CY_LEAVES));
+        d.prog_seed = j.prog->h_desc.prog_seed;
+        d.n_leaves = n;
+        d.n_rungs = j.n_rungs;
+        mg_carry_census_dev_job& c = h_cjobs[g];
+        c.mrows = (const uint32_t*)(w + off[MG_CC_OFF(n_jobs, g, MG_CC_PROBES)]) +
+                  (size_t)probe0[g] * 8 * cols;
+        c.counts = (unsigned long long*)(w + off[MG_CC_OFF(n_jobs, g, MG_CC_COUNTS)]);
+        c.n_roots = roots;
+        unsigned long long* h =
+            (unsigned long long*)(img.data() + off[MG_CC_OFF(n_jobs, g, MG_CC_COUNTS)]);
+        for (uint32_t r = 0; r < j.n_rungs; ++r)
+            for (uint32_t k = mg_census_sole_index(roots); k < mg_census_words(roots); ++k)
+                h[(size_t)r * mg_census_words(roots) + k] = ~0ull;
+    }
+    const mg_pdesc* d_descs = (const mg_pdesc*)(w + off[MG_CY_DESCS]);
+    const mg_carry_dev_job* d_jobs = (const mg_carry_dev_job*)(w + off[MG_CY_JOBS]);
+    const mg_carry_census_dev_job* d_cjobs =
+        (const mg_carry_census_dev_job*)(w + off[MG_CC_BASE(n_jobs) + MG_CC_RECORDS]);
+    long long* d_out_col = (long long*)(w + off[MG_CY_OUT]);
+    uint32_t* d_out_nfail = (uint32_t*)(w + off[MG_CY_OUT] + (size_t)n_jobs * walkers * 8);
+    uint32_t* d_out_rows = (uint32_t*)(w + off[MG_CY_OUT] + (size_t)n_jobs * walkers * 12);
+    HIPCHECK(ctx, hipMemcpyAsync(w, img.data(), up_b, hipMemcpyHostToDevice, ctx->stream));
+    mg_run run = empty_run();
+    run.leaves = (const uint32_t*)(w + off[MG_CY_OFF(0, MG_CY_LEAVES)]);
+    run.leaves_prog_words = leaf_w;
+    run.probes = (uint32_t*)(w + off[MG_CC_OFF(n_jobs, 0, MG_CC_PROBES)]);
+    run.probe_prog_words = probe_w;
+    run.probes_per_prog = 1;
+    run.stride = cols;
+    run.n_assign = cols;
+    timing_begin(ctx);
+    HIPCHECK(ctx, mg_launch_carry_fill_rungs(d_jobs, n_jobs, most, gen->seed, gen->first_index,
+                                             lanes, cols, ctx->stream));
+    HIPCHECK(ctx, launch(ctx, 0, d_descs, n_jobs, run, max_lds, ctx->stream));
+    HIPCHECK(ctx, mg_launch_carry_census(d_jobs, d_cjobs, n_jobs, top, lanes, cols, ctx->stream));
+    HIPCHECK(ctx, mg_launch_carry_starts(d_jobs, d_cjobs, n_jobs, walkers, cols, max_leaves,
+                                         d_out_col, d_out_nfail, d_out_rows, ctx->stream));
+    timing_end(ctx);
+    // the counter regions end where the output block begins: one copy
+    HIPCHECK(ctx, hipMemcpyAsync(img.data() + count0, w + count0, up_b - count0 + out_b,
+                                 hipMemcpyDeviceToHost, ctx->stream));
+    if (fill_out && leaf_w)
+        HIPCHECK(ctx, hipMemcpyAsync(fill_out, run.leaves, (size_t)n_jobs * leaf_w * 4,
+                                     hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
+    timing_read(ctx);
+    const size_t block_w = 5 * (size_t)max_roots + 2;
+    memset(counts, 0, (size_t)n_jobs * top * block_w * 8);
+    for (uint32_t g = 0; g < n_jobs; ++g)
+        for (uint32_t r = 0; r < n_rungs[g]; ++r)
+            memcpy(counts + ((size_t)g * top + r) * block_w,
+                   img.data() + off[MG_CC_OFF(n_jobs, g, MG_CC_COUNTS)] +
+                       (size_t)r * mg_census_words(n_roots[g]) * 8,
+                   (size_t)mg_census_words(n_roots[g]) * 8);
+    const uint8_t* h_out = img.data() + up_b;
+    memcpy(start_col, h_out, (size_t)n_jobs * walkers * 8);
+    memcpy(start_nfail, h_out + (size_t)n_jobs * walkers * 8, (size_t)n_jobs * walkers * 4);
+    memcpy(starts, h_out + (size_t)n_jobs * walkers * 12,
+           (size_t)n_jobs * walkers * max_leaves * 32);
+    return MG_OK;
+}
+
+int mg_carry_census_plan_host(const uint32_t* n_leaves, const uint32_t* n_rungs,
+                              const uint32_t* n_roots, const uint32_t* n_probes,
+                              const uint32_t* mask_probe0, uint32_t n_jobs, uint32_t lanes,
+                              uint32_t walkers, uint32_t max_leaves, uint64_t* out_offsets,
+                              uint64_t* out_bytes, uint64_t* out_leaf_stride_w,
+                              uint64_t* out_probe_stride_w) {
+    return mg_carry_census_plan(n_leaves, n_rungs, n_roots, n_probes, mask_probe0, n_jobs, lanes,
+                                walkers, max_leaves, out_offsets, out_bytes, out_leaf_stride_w,
+                                out_probe_stride_w, nullptr) == MG_CC_OK ? MG_OK : MG_E_ARG;
+}
+
+int mg_carry_starts_host(const uint64_t* counts, uint32_t n_roots, uint32_t n_rungs,
+                         uint32_t walkers, int64_t* start_col, uint32_t* start_nfail) {
+    if (!counts || !start_col || !start_nfail) return MG_E_ARG;
+    if (!mg_census_roots_ok(n_roots) || n_rungs < 1 || n_rungs > MG_CARRY_MAX_RUNGS ||
+        walkers < 1 || walkers > MG_CARRY_MAX_WALKERS)
+        return MG_E_ARG;
+    mg_carry_pick_starts((const unsigned long long*)counts, n_roots, n_rungs, walkers, start_col,
+                         start_nfail);
+    return MG_OK;
 }
 
 // Host only: lanes lane0 .. lane0 + n_lanes - 1 of round r of the lane

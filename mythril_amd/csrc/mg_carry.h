@@ -32,7 +32,11 @@
  * candidate c % lanes (mg_carry_rung, mg_carry_fill_rung_lane).  Its buffer is
  * the one above with a job's mask region holding its n_rungs masks one after
  * the other, the output block n_jobs i64 first, n_jobs i64 rung and the rows,
- * and leaf regions of C columns (mg_carry_ladder_plan). */
+ * and leaf regions of C columns (mg_carry_ladder_plan).
+ *
+ * mg_carry_census adds per-rung counter blocks, probe
+ * regions and an output block of W starts to the ladder's buffer
+ * (mg_carry_census_plan, at the end of this file, with the start rule). */
 #ifndef MG_CARRY_H
 #define MG_CARRY_H
 
@@ -41,6 +45,7 @@
 #include "mythgpu_ir.h"
 #include "mg_device.h"
 #include "mg_repair.h"
+#include "mg_census.h"
 
 enum { MG_CY_DESCS, MG_CY_JOBS, MG_CY_FIRST, MG_CY_OUT, MG_CY_SHARED };
 enum { MG_CY_MASK, MG_CY_ROWS, MG_CY_GEN, MG_CY_LEAVES, MG_CY_JOB_REGIONS };
@@ -213,12 +218,12 @@ static inline bool mg_cy_add(uint64_t* a, uint64_t count, uint64_t unit) {
     return !__builtin_add_overflow(*a, b, a);
 }
 
-/* The layout both calls share: job g has n_rungs[g] masks (NULL: one each),
- * the output block out_fixed bytes per job before its rows, a leaf region
- * `cols` columns. */
-static inline bool mg_cy_plan(const uint32_t* n_leaves, const uint32_t* n_rungs, uint32_t n_jobs,
-                              uint64_t cols, uint32_t out_fixed, uint32_t max_leaves,
-                              uint64_t* offsets, uint64_t* bytes, uint64_t* leaf_stride_w) {
+/* The uploaded front of every carry buffer: descriptors, job records, first
+ * words, then job by job its masks (n_rungs[g] of them, NULL: one each), rows
+ * and generators.  *at: where the front ends; *most: the largest n_leaves. */
+static inline bool mg_cy_plan_front(const uint32_t* n_leaves, const uint32_t* n_rungs,
+                                    uint32_t n_jobs, uint64_t* offsets, uint64_t* at_out,
+                                    uint32_t* most_out) {
     uint64_t at = 0;
     offsets[MG_CY_DESCS] = at;
     if (!mg_cy_add(&at, n_jobs, sizeof(mg_pdesc))) return false;
@@ -237,10 +242,20 @@ static inline bool mg_cy_plan(const uint32_t* n_leaves, const uint32_t* n_rungs,
         offsets[MG_CY_OFF(g, MG_CY_GEN)] = at;
         if (!mg_cy_add(&at, n, sizeof(mg_leafgen))) return false;
     }
+    *at_out = at;
+    *most_out = most;
+    return true;
+}
+
+/* The downloaded block and the leaf regions from *at on: out_job bytes of
+ * output per job, then every job's leaf region of most x 8 x cols words,
+ * rounded up to 256 bytes. */
+static inline bool mg_cy_plan_back(uint32_t n_jobs, uint32_t most, uint64_t cols, uint64_t out_job,
+                                   uint64_t* offsets, uint64_t* at_io, uint64_t* leaf_stride_w) {
+    uint64_t at = *at_io;
     offsets[MG_CY_OUT] = at;
     uint64_t out_b;
-    if (__builtin_mul_overflow((uint64_t)max_leaves * 32u + out_fixed, (uint64_t)n_jobs, &out_b))
-        return false;
+    if (__builtin_mul_overflow(out_job, (uint64_t)n_jobs, &out_b)) return false;
     if (!mg_cy_add(&at, out_b, 1)) return false;
     uint64_t leaf_b = 0;
     if (!mg_cy_add(&leaf_b, (uint64_t)most * 32u, cols)) return false;
@@ -248,8 +263,24 @@ static inline bool mg_cy_plan(const uint32_t* n_leaves, const uint32_t* n_rungs,
         offsets[MG_CY_OFF(g, MG_CY_LEAVES)] = at;
         if (__builtin_add_overflow(at, leaf_b, &at)) return false;
     }
-    *bytes = at;
+    *at_io = at;
     if (leaf_stride_w) *leaf_stride_w = leaf_b / 4;
+    return true;
+}
+
+/* The layout mg_carry_batch and mg_carry_ladder share: job g has n_rungs[g]
+ * masks (NULL: one each), the output block out_fixed bytes per job before its
+ * rows, a leaf region `cols` columns. */
+static inline bool mg_cy_plan(const uint32_t* n_leaves, const uint32_t* n_rungs, uint32_t n_jobs,
+                              uint64_t cols, uint32_t out_fixed, uint32_t max_leaves,
+                              uint64_t* offsets, uint64_t* bytes, uint64_t* leaf_stride_w) {
+    uint64_t at = 0;
+    uint32_t most = 0;
+    if (!mg_cy_plan_front(n_leaves, n_rungs, n_jobs, offsets, &at, &most)) return false;
+    if (!mg_cy_plan_back(n_jobs, most, cols, (uint64_t)max_leaves * 32u + out_fixed, offsets, &at,
+                         leaf_stride_w))
+        return false;
+    *bytes = at;
     return true;
 }
 
@@ -292,6 +323,177 @@ static inline bool mg_carry_ladder_plan(const uint32_t* n_leaves, const uint32_t
         return false;
     return mg_cy_plan(n_leaves, n_rungs, n_jobs, cols, 16, max_leaves, offsets, bytes,
                       leaf_stride_w);
+}
+
+/* mg_carry_census: the ladder's fill and evaluation, then a
+ * verdict census of every rung's own columns and W start columns per job.
+ * Its buffer is the ladder's with three kinds of region more, in this order:
+ *   descs, jobs, first, per job masks, rows, generators      as the ladder
+ *   census records        one mg_carry_census_dev_job per job
+ *   per job, its counters n_rungs blocks of mg_census_words(n_roots) u64 one
+ *                         after the other, as mg_census.h lays a block out
+ *     (up to here one upload: the sums zero, the minima all ones)
+ *   out                   start_col [n_jobs][W] i64, start_nfail [n_jobs][W]
+ *                         u32, starts [n_jobs][W][max_leaves][8] u32
+ *     (counters and out come back in one download)
+ *   per job, its leaves   as the ladder, C columns
+ *   per job, its probes   [probe][limb][C] at a common stride: the largest
+ *                         n_probes of the batch x 8 x C words, rounded up to
+ *                         256 bytes (the stride the interpreter's shell applies)
+ * offsets[]: the ladder's table, then MG_CC_SHARED entries, then
+ * MG_CC_JOB_REGIONS per job. */
+enum { MG_CC_RECORDS, MG_CC_SHARED };
+enum { MG_CC_COUNTS, MG_CC_PROBES, MG_CC_JOB_REGIONS };
+#define MG_CC_BASE(n_jobs) ((size_t)MG_CY_SHARED + (size_t)(n_jobs) * MG_CY_JOB_REGIONS)
+#define MG_CC_OFF(n_jobs, g, k) \
+    (MG_CC_BASE(n_jobs) + MG_CC_SHARED + (size_t)(g) * MG_CC_JOB_REGIONS + (k))
+#define MG_CC_TABLE(n_jobs) (MG_CC_BASE(n_jobs) + MG_CC_SHARED + (size_t)(n_jobs) * MG_CC_JOB_REGIONS)
+
+static_assert(MG_CARRY_CENSUS_SHARED == MG_CC_SHARED &&
+              MG_CARRY_CENSUS_JOB_REGIONS == MG_CC_JOB_REGIONS,
+              "include/mythgpu.h documents the length of the offset table");
+
+/* What the census and starts kernels read of a job beside its mg_carry_dev_job
+ * (same index). */
+struct mg_carry_census_dev_job {
+    const uint32_t* mrows;      /* in its probe region: row 0 of its first mask probe */
+    unsigned long long* counts; /* its n_rungs counter blocks */
+    uint32_t n_roots;
+    uint32_t pad;
+};
+
+/* why a plan is refused (mg_carry_census words them) */
+enum {
+    MG_CC_OK, MG_CC_NULL, MG_CC_LADDER, MG_CC_WALKERS, MG_CC_ROOTS, MG_CC_MASK, MG_CC_OVERFLOW
+};
+
+/* bytes of the output block per job */
+static inline uint64_t mg_carry_census_out_job(uint32_t walkers, uint32_t max_leaves) {
+    return (uint64_t)walkers * (12u + (uint64_t)max_leaves * 32u);
+}
+
+/* Every offset of mg_carry_census's buffer and its size, with checked
+ * arithmetic.  *bad (may be NULL): the job a per-job refusal names.
+ * *probe_stride_w (u32 words, may be NULL): the distance between two jobs'
+ * probe regions. */
+static inline int mg_carry_census_plan(const uint32_t* n_leaves, const uint32_t* n_rungs,
+                                       const uint32_t* n_roots, const uint32_t* n_probes,
+                                       const uint32_t* mask_probe0, uint32_t n_jobs,
+                                       uint32_t lanes, uint32_t walkers, uint32_t max_leaves,
+                                       uint64_t* offsets, uint64_t* bytes,
+                                       uint64_t* leaf_stride_w, uint64_t* probe_stride_w,
+                                       uint32_t* bad) {
+    if (!n_leaves || !n_roots || !n_probes || !mask_probe0 || !offsets || !bytes)
+        return MG_CC_NULL;
+    uint32_t cols = 0;
+    if (!mg_carry_ladder_ok(n_rungs, n_jobs, lanes, &cols)) return MG_CC_LADDER;
+    if (walkers < 1 || walkers > MG_CARRY_MAX_WALKERS) return MG_CC_WALKERS;
+    uint32_t most_probes = 0;
+    for (uint32_t g = 0; g < n_jobs; ++g) {
+        if (bad) *bad = g;
+        if (n_roots[g] < 1 || n_roots[g] > MG_CENSUS_MAX_ROOTS) return MG_CC_ROOTS;
+        const uint32_t n_mask = (n_roots[g] + 255u) / 256u;
+        if (mask_probe0[g] >= n_probes[g] || n_mask > n_probes[g] - mask_probe0[g])
+            return MG_CC_MASK;
+        most_probes = n_probes[g] > most_probes ? n_probes[g] : most_probes;
+    }
+    uint64_t at = 0;
+    uint32_t most = 0;
+    if (!mg_cy_plan_front(n_leaves, n_rungs, n_jobs, offsets, &at, &most)) return MG_CC_OVERFLOW;
+    offsets[MG_CC_BASE(n_jobs) + MG_CC_RECORDS] = at;
+    if (!mg_cy_add(&at, n_jobs, sizeof(mg_carry_census_dev_job))) return MG_CC_OVERFLOW;
+    for (uint32_t g = 0; g < n_jobs; ++g) {
+        offsets[MG_CC_OFF(n_jobs, g, MG_CC_COUNTS)] = at;
+        if (!mg_cy_add(&at, (uint64_t)mg_census_words(n_roots[g]) * n_rungs[g], 8))
+            return MG_CC_OVERFLOW;
+    }
+    if (!mg_cy_plan_back(n_jobs, most, cols, mg_carry_census_out_job(walkers, max_leaves), offsets,
+                         &at, leaf_stride_w))
+        return MG_CC_OVERFLOW;
+    uint64_t probe_b = 0;
+    if (!mg_cy_add(&probe_b, (uint64_t)most_probes * 32u, cols)) return MG_CC_OVERFLOW;
+    for (uint32_t g = 0; g < n_jobs; ++g) {
+        offsets[MG_CC_OFF(n_jobs, g, MG_CC_PROBES)] = at;
+        if (__builtin_add_overflow(at, probe_b, &at)) return MG_CC_OVERFLOW;
+    }
+    *bytes = at;
+    if (probe_stride_w) *probe_stride_w = probe_b / 4;
+    return MG_CC_OK;
+}
+
+/* The start rule (include/mythgpu.h states it above mg_carry_census;
+ * carry.starts_ref is its specification).  counts: a job's n_rungs counter
+ * blocks of mg_census_words(n_roots) words one after the other.
+ *
+ * The list: the bests of the rungs that counted a column, by (failing roots,
+ * rung) ascending; then, rung by rung and root by root, every sole_index that
+ * is set and is not its rung's best column (1 failing root each).  No column
+ * comes twice: rungs own disjoint column ranges, so two entries of different
+ * rungs differ; within a rung a column is the sole candidate of at most one
+ * root (its only failing root), and a rung's best with one failing root is
+ * the lowest column with one failing root, hence the lowest sole column of
+ * that root — the one entry the rule leaves out; a best with zero or several
+ * failing roots is no sole column at all. */
+MG_CARRY_FN unsigned long long mg_carry_rung_best(const unsigned long long* counts,
+                                                  uint32_t n_roots, uint32_t r) {
+    return counts[(uint64_t)r * mg_census_words(n_roots) + mg_census_best(n_roots)];
+}
+
+#define MG_CARRY_COL_MASK ((1ull << MG_CENSUS_OFFSET_BITS) - 1)
+
+/* the per-entry predicate: entry e = r * n_roots + k of the sole part of the
+ * list exists; *col: its column */
+MG_CARRY_FN bool mg_carry_sole_entry(const unsigned long long* counts, uint32_t n_roots,
+                                     uint32_t e, unsigned long long* col) {
+    const uint32_t r = e / n_roots, k = e % n_roots;
+    const unsigned long long si =
+        counts[(uint64_t)r * mg_census_words(n_roots) + mg_census_sole_index(n_roots) + k];
+    const unsigned long long best = mg_carry_rung_best(counts, n_roots, r);
+    *col = si;
+    return si != ~0ull && (best == ~0ull || si != (best & MG_CARRY_COL_MASK));
+}
+
+/* the place of rung r's best among the bests, or n_rungs when the rung counted
+ * no column */
+MG_CARRY_FN uint32_t mg_carry_best_rank(const unsigned long long* counts, uint32_t n_roots,
+                                        uint32_t n_rungs, uint32_t r) {
+    const unsigned long long mine = mg_carry_rung_best(counts, n_roots, r);
+    if (mine == ~0ull) return n_rungs;
+    const unsigned long long f = mine >> MG_CENSUS_OFFSET_BITS;
+    uint32_t rank = 0;
+    for (uint32_t q = 0; q < n_rungs; ++q) {
+        const unsigned long long other = mg_carry_rung_best(counts, n_roots, q);
+        if (other == ~0ull || q == r) continue;
+        const unsigned long long g = other >> MG_CENSUS_OFFSET_BITS;
+        if (g < f || (g == f && q < r)) ++rank;
+    }
+    return rank;
+}
+
+/* The rule in sequential form: start_col [walkers] (-1: the job counted no
+ * column at all), start_nfail [walkers] (0xFFFFFFFF then). */
+static inline void mg_carry_pick_starts(const unsigned long long* counts, uint32_t n_roots,
+                                        uint32_t n_rungs, uint32_t walkers, int64_t* start_col,
+                                        uint32_t* start_nfail) {
+    uint32_t n = 0;
+    for (uint32_t place = 0; place < n_rungs && n < walkers; ++place)
+        for (uint32_t r = 0; r < n_rungs; ++r)
+            if (mg_carry_best_rank(counts, n_roots, n_rungs, r) == place) {
+                const unsigned long long b = mg_carry_rung_best(counts, n_roots, r);
+                start_col[n] = (int64_t)(b & MG_CARRY_COL_MASK);
+                start_nfail[n++] = (uint32_t)(b >> MG_CENSUS_OFFSET_BITS);
+                break;
+            }
+    for (uint32_t e = 0; e < n_rungs * n_roots && n < walkers; ++e) {
+        unsigned long long col;
+        if (!mg_carry_sole_entry(counts, n_roots, e, &col)) continue;
+        start_col[n] = (int64_t)col;
+        start_nfail[n++] = 1;
+    }
+    for (uint32_t w = n; w < walkers; ++w) {
+        start_col[w] = n ? start_col[0] : -1;
+        start_nfail[w] = n ? start_nfail[0] : 0xFFFFFFFFu;
+    }
 }
 
 #endif

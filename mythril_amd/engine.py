@@ -41,7 +41,8 @@ EXPORTS = ("mg_init", "mg_init_layout", "mg_layouts", "mg_free", "mg_last_error"
            "mg_walk_batch_plan_host", "mg_walk_batch_shape_ok_host", "mg_census_batch",
            "mg_census_batch_plan_host", "mg_census_batch_blocks_host", "mg_batch_witness",
            "mg_carry_batch", "mg_carry_fill_host", "mg_carry_plan_host", "mg_carry_ladder",
-           "mg_carry_fill_rungs_host", "mg_carry_ladder_plan_host")
+           "mg_carry_fill_rungs_host", "mg_carry_ladder_plan_host", "mg_carry_census",
+           "mg_carry_census_plan_host", "mg_carry_starts_host")
 
 
 def layouts() -> Dict[int, Tuple[int, int]]:
@@ -132,12 +133,20 @@ class CarryLadderJob(C.Structure):
                 ("n_rungs", C.c_uint32), ("pad", C.c_uint32)]
 
 
+class CarryCensusJob(C.Structure):
+    """mg_carry_census_job (include/mythgpu.h): one job of mg_carry_census."""
+    _fields_ = [("ladder", CarryLadderJob), ("n_roots", C.c_uint32), ("mask_probe0", C.c_uint32)]
+
+
 # include/mythgpu.h
 CARRY_MAX_JOBS = 256
 CARRY_MAX_RUNGS = 8
 CARRY_MAX_LANES = 1 << 20
 CARRY_SHARED = 4
 CARRY_JOB_REGIONS = 4
+CARRY_MAX_WALKERS = 64
+CARRY_CENSUS_SHARED = 1
+CARRY_CENSUS_JOB_REGIONS = 2
 CENSUS_BATCH_MAX_JOBS = 256
 CENSUS_BATCH_SHARED = 2
 CENSUS_BATCH_JOB_REGIONS = 2
@@ -237,6 +246,11 @@ def load_library(path: str = _LIB_PATH, check_digest: bool = True):
                                                  u32, u32, p]
         lib.mg_carry_ladder_plan_host.argtypes = [p, p, u32, u32, u32, p, C.POINTER(u64),
                                                   C.POINTER(u64)]
+        lib.mg_carry_census.argtypes = [p, C.POINTER(CarryCensusJob), u32, C.POINTER(Gen), u32, u32,
+                                        u32, u32, p, p, p, p, p]
+        lib.mg_carry_census_plan_host.argtypes = [p, p, p, p, p, u32, u32, u32, u32, p,
+                                                  C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
+        lib.mg_carry_starts_host.argtypes = [p, u32, u32, u32, p, p]
         lib.mg_batch_create.argtypes = [p, C.POINTER(p), u32, C.POINTER(p)]
         lib.mg_batch_free.argtypes = [p]
         lib.mg_batch_free.restype = None
@@ -582,6 +596,73 @@ class Engine:
                 res = (f, int(rung[i]), wit[i, :k].copy() if f >= 0 else None)
                 if want_fill:
                     res += (fill[i, :k * 8 * cols].reshape(k, 8, cols).copy(),)
+                out.append(res)
+        return out
+
+    def carry_census(self, jobs, seed: int, first_index: int, lanes: int, walkers: int,
+                     want_fill: bool = False):
+        """:meth:`carry_ladder`'s columns, censused per rung, and ``walkers``
+        start columns per job, all jobs in one launch sequence
+        (mg_carry_census).  ``jobs``: a list of ``(lp,
+        pin_rows, pin_masks, n_roots)`` — a ladder job whose program carries
+        its verdict mask as its first probes (``census.mask_probes``; load the
+        ``census.census_view``).  Returns per job ``(censuses, start_col,
+        start_nfail, starts)``: one :class:`mythril_amd.census.Census` per rung
+        over the rung's own columns (``first_index = r * lanes``, ``n_cand =
+        lanes``: indices are column numbers), and the columns
+        (``(walkers,)`` int64), failing roots (uint32) and leaf rows
+        (``(walkers, n_leaves, 8)`` uint32) that ``carry.starts_ref`` picks
+        from those censuses.  When ``start_nfail[0] == 0``, ``start_col[0]`` is
+        :meth:`carry_ladder`'s ``first``, ``start_col[0] // lanes`` its rung
+        and ``starts[0]`` its leaves.  With ``want_fill`` a fifth element, the
+        job's leaf region.  More than ``CARRY_MAX_JOBS`` jobs run as
+        consecutive batches."""
+        from .census import unpack_block
+        jobs = [(lp, np.ascontiguousarray(r, dtype=np.uint32).reshape(-1, 8),
+                 np.ascontiguousarray(m, dtype=np.uint32), int(k)) for lp, r, m, k in jobs]
+        for lp, r, m, k in jobs:
+            n = len(lp.program.leaves)
+            if r.shape[0] != n or m.ndim != 2 or m.shape[1] != (n + 31) // 32 or \
+                    not 1 <= m.shape[0] <= CARRY_MAX_RUNGS:
+                raise ValueError("pin rows must be (n_leaves, 8) and the pin masks (n_rungs, "
+                                 "(n_leaves + 31) // 32) with 1 to %d rungs" % CARRY_MAX_RUNGS)
+        g = Gen(seed & (2**64 - 1), first_index)
+        w = max(1, min(int(walkers), CARRY_MAX_WALKERS))         # (the library refuses the rest)
+        out = []
+        for lo in range(0, len(jobs), CARRY_MAX_JOBS):
+            part = jobs[lo:lo + CARRY_MAX_JOBS]
+            n = len(part)
+            arr = (CarryCensusJob * n)()
+            for i, (lp, r, m, k) in enumerate(part):
+                lad = arr[i].ladder
+                lad.prog, lad.pin_rows, lad.pin_masks, lad.n_rungs = \
+                    lp.handle, _ptr(r), _ptr(m), m.shape[0]
+                arr[i].n_roots, arr[i].mask_probe0 = max(0, k) & 0xFFFFFFFF, 0
+            counts = [len(lp.program.leaves) for lp, _, _, _ in part]
+            top = max(m.shape[0] for _, _, m, _ in part)
+            cols = top * lanes
+            max_leaves = max(1, max(counts))
+            max_roots = max(1, min(max(k for _, _, _, k in part), 1024))
+            blocks = np.zeros((n, top, 5 * max_roots + 2), dtype=np.uint64)
+            col = np.full((n, w), -1, dtype=np.int64)
+            nfail = np.zeros((n, w), dtype=np.uint32)
+            rows = np.zeros((n, w, max_leaves, 8), dtype=np.uint32)
+            fill = None
+            if want_fill:
+                _, _, stride = carry_ladder_plan_host(counts, [m.shape[0] for _, _, m, _ in part],
+                                                      lanes, max_leaves)
+                fill = np.zeros((n, max(1, stride)), dtype=np.uint32)
+            rc = self.lib.mg_carry_census(self._ctx, arr, n, C.byref(g), lanes, walkers, max_roots,
+                                          max_leaves, _ptr(blocks), _ptr(col), _ptr(nfail),
+                                          _ptr(rows), _ptr(fill))
+            self._check(rc, "mg_carry_census")
+            ms = self.last_kernel_ms()
+            for i, (nl, (_, _, m, k)) in enumerate(zip(counts, part)):
+                cs = [unpack_block(blocks[i, r], k, r * lanes, lanes, ms)
+                      for r in range(m.shape[0])]
+                res = (cs, col[i].copy(), nfail[i].copy(), rows[i, :, :nl].copy())
+                if want_fill:
+                    res += (fill[i, :nl * 8 * cols].reshape(nl, 8, cols).copy(),)
                 out.append(res)
         return out
 
@@ -1294,6 +1375,50 @@ def carry_ladder_plan_host(n_leaves: Sequence[int], n_rungs: Sequence[int], lane
         raise EngineError("carry_ladder: %d jobs at %d lanes: counts out of range, too many "
                           "columns or a buffer beyond 64 bits" % (n, lanes))
     return offs[:CARRY_SHARED + n * CARRY_JOB_REGIONS], int(total.value), int(stride.value)
+
+
+def carry_census_plan_host(n_leaves: Sequence[int], n_rungs: Sequence[int],
+                           n_roots: Sequence[int], n_probes: Sequence[int],
+                           mask_probe0: Sequence[int], lanes: int, walkers: int, max_leaves: int):
+    """Host-only: the plan of mg_carry_census's device buffer
+    (mg_carry_census_plan_host): ``(offsets, bytes, leaf_stride_w,
+    probe_stride_w)``.  ``offsets``: :func:`carry_ladder_plan_host`'s table
+    followed by the census records' offset and per job its counter blocks' and
+    its probe region's.  :class:`EngineError` where the library refuses."""
+    lib = load_library(check_digest=False)
+    arrs = [np.ascontiguousarray(a, dtype=np.uint32)
+            for a in (n_leaves, n_rungs, n_roots, n_probes, mask_probe0)]
+    n = arrs[0].shape[0]
+    if any(a.shape[0] != n for a in arrs):
+        raise ValueError("one count of each kind per job")
+    size = CARRY_SHARED + CARRY_CENSUS_SHARED + n * (CARRY_JOB_REGIONS + CARRY_CENSUS_JOB_REGIONS)
+    offs = np.zeros(size + CARRY_JOB_REGIONS + CARRY_CENSUS_JOB_REGIONS, dtype=np.uint64)
+    total, stride, pstride = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+    rc = lib.mg_carry_census_plan_host(*[_ptr(a) for a in arrs], n, lanes, walkers, max_leaves,
+                                       _ptr(offs), C.byref(total), C.byref(stride),
+                                       C.byref(pstride))
+    if rc != 0:
+        raise EngineError("carry_census: %d jobs at %d lanes and %d walkers: counts out of range, "
+                          "too many columns, mask probes outside the program's or a buffer "
+                          "beyond 64 bits" % (n, lanes, walkers))
+    return offs[:size], int(total.value), int(stride.value), int(pstride.value)
+
+
+def carry_starts_host(blocks: np.ndarray, n_roots: int, walkers: int):
+    """Host-only: the start rule (mg_carry_starts_host) on one job's counter
+    blocks ``(n_rungs, 5 * n_roots + 2)`` uint64 (``census.pack_block`` of each
+    rung's census): ``(start_col, start_nfail)``."""
+    lib = load_library(check_digest=False)
+    blocks = np.ascontiguousarray(blocks, dtype=np.uint64)
+    if blocks.ndim != 2 or blocks.shape[1] != 5 * n_roots + 2:
+        raise ValueError("counter blocks must be (n_rungs, 5 * n_roots + 2)")
+    col = np.full(max(1, walkers), -1, dtype=np.int64)
+    nfail = np.zeros(max(1, walkers), dtype=np.uint32)
+    rc = lib.mg_carry_starts_host(_ptr(blocks), n_roots, blocks.shape[0], walkers, _ptr(col),
+                                  _ptr(nfail))
+    if rc != 0:
+        raise EngineError("mg_carry_starts_host refused its arguments (%d)" % rc)
+    return col, nfail
 
 
 def carry_fill_rungs_host(leafgen: Sequence[LeafGen], consts: np.ndarray, prog_seed: int,

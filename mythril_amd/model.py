@@ -128,6 +128,8 @@ class SolverStatistics:
         self.launches = 0               # kernel launches of those calls (_count_kernel)
         self.carry_gated = 0            # extensions not carried: a carried table above the cap
         self.carry_rung_hits = [0, 0, 0]  # the ladder's hits per rung (carry.RUNG_NAMES)
+        self.carry_walk_attempts = 0    # groups that missed every rung and walked (knob 3)
+        self.carry_walk_hits = 0        # ... to a model
         self.phase = {k: 0.0 for k in PHASES}
 
     def gpu_report(self) -> str:
@@ -136,11 +138,13 @@ class SolverStatistics:
                 self.repair_attempts, self.repair_hits,
                 " batches: {}".format(self.repair_batches) if self.repair_batches else "")
             if self.repair_attempts or self.repair_hits else "") + (
-            "\nGPU carry: exact: {} attempts: {} hits: {} candidates: {}{}{}".format(
+            "\nGPU carry: exact: {} attempts: {} hits: {} candidates: {}{}{}{}".format(
                 self.carry_exact, self.carry_attempts, self.carry_hits, self.carry_candidates,
                 " table-gated: {}".format(self.carry_gated) if self.carry_gated else "",
                 " rung hits: {}".format("/".join(map(str, self.carry_rung_hits)))
-                if any(self.carry_rung_hits) else "")
+                if any(self.carry_rung_hits) else "",
+                " walks: {} walk hits: {}".format(self.carry_walk_attempts, self.carry_walk_hits)
+                if self.carry_walk_attempts or self.carry_walk_hits else "")
             if self.carry_exact or self.carry_attempts or self.carry_gated else "")
 
     def _gpu_report(self) -> str:
@@ -246,8 +250,13 @@ REPAIR_BATCH = False
 # extends remembered groups is evaluated once under their witnesses before it
 # is compiled for a search (carry.py); unset, nothing changes.
 # MYTHRIL_GPU_CARRY=2 ("ladder"): the same with the constant-keyed eval form
-# and a ladder of pin sets per group in one launch sequence
+# and a ladder of pin sets per group in one launch sequence.
+# MYTHRIL_GPU_CARRY=3 ("walk"): as 2, and the groups that miss on every rung
+# walk from the ladder's best columns (repair.repair_carried)
+# with CARRY_WALKERS start columns for at most CARRY_ROUNDS rounds
 CARRY = False
+CARRY_WALKERS = 4              # MYTHRIL_GPU_CARRY_WALKERS
+CARRY_ROUNDS = 16              # MYTHRIL_GPU_CARRY_ROUNDS
 SHAPE_MIN, SHAPE_FLOOR, SHAPE_PROBE = 4, 1.0 / 16, 8
 
 
@@ -274,11 +283,14 @@ def configure_from_env(env=None) -> None:
     ``MYTHRIL_GPU_CARRY=1`` (off by default) remembers the witnesses of groups
     and evaluates them on the groups that extend them (``carry.py``),
     ``MYTHRIL_GPU_CARRY=2`` does so with a ladder of pin sets per group,
+    ``MYTHRIL_GPU_CARRY=3`` also walks from the ladder's best columns when
+    every rung misses (``MYTHRIL_GPU_CARRY_WALKERS`` start columns, default 4,
+    at most ``MYTHRIL_GPU_CARRY_ROUNDS`` rounds, default 16),
     ``MYTHRIL_GPU_CARRY_LANES`` the candidates of such an evaluation when the
     extension has fresh symbols, ``MYTHRIL_GPU_CARRY_MAX_ENTRIES`` the largest
     carried table an extension is evaluated with."""
     global GPU_ENABLED, DEVICES, SEARCH_CANDIDATES, SEARCH_BUDGET_MS, SHAPE_GATE, REFUTE, REPAIR
-    global REPAIR_SCORED, REPAIR_BATCH, CARRY
+    global REPAIR_SCORED, REPAIR_BATCH, CARRY, CARRY_WALKERS, CARRY_ROUNDS
     import os
     env = os.environ if env is None else env
     GPU_ENABLED = env.get("MYTHRIL_GPU", "1").strip().lower() not in ("0", "off", "false", "no")
@@ -300,8 +312,12 @@ def configure_from_env(env=None) -> None:
         "1", "on", "true", "yes")
     REPAIR_BATCH = env.get("MYTHRIL_GPU_REPAIR_BATCH", "0").strip().lower() in (
         "1", "on", "true", "yes")
-    CARRY = "ladder" if env.get("MYTHRIL_GPU_CARRY", "0").strip() == "2" else \
+    CARRY = {"2": "ladder", "3": "walk"}.get(env.get("MYTHRIL_GPU_CARRY", "0").strip()) or \
         env.get("MYTHRIL_GPU_CARRY", "0").strip().lower() in ("1", "on", "true", "yes")
+    if env.get("MYTHRIL_GPU_CARRY_WALKERS"):
+        CARRY_WALKERS = min(64, max(1, int(env["MYTHRIL_GPU_CARRY_WALKERS"])))
+    if env.get("MYTHRIL_GPU_CARRY_ROUNDS"):
+        CARRY_ROUNDS = min(1 << 16, max(1, int(env["MYTHRIL_GPU_CARRY_ROUNDS"])))
     if env.get("MYTHRIL_GPU_CARRY_LANES"):
         from . import carry
         carry.CARRY_LANES = min(1 << 20, max(1, int(env["MYTHRIL_GPU_CARRY_LANES"])))
@@ -750,11 +766,12 @@ def _carry_groups(groups, eng=None):
     one that evidenced the hit); the groups that extend remembered groups go
     into ONE ``Engine.carry_batch`` call on the first device, deduplicated by
     key (with ``CARRY == "ladder"``: one ``Engine.carry_ladder`` call, every
-    group with its rungs).  A group missing from the result goes on as
-    before."""
+    group with its rungs; with ``CARRY == "walk"`` the groups that miss on
+    every rung then go into one ``repair.repair_carried`` call).  A group
+    missing from the result goes on as before."""
     from . import carry
     out, jobs = {}, {}
-    ladder = CARRY == "ladder"
+    ladder = CARRY in ("ladder", "walk")
     cache = _SEARCH_CACHE or {}
     for key, nodes in groups:
         if key in out or key in jobs or not key:
@@ -797,6 +814,24 @@ def _carry_groups(groups, eng=None):
                     stats.carry_rung_hits[r[3]] += 1
                 _note_hit(key, asg, prog)
                 out[key] = (asg, prog)
+        missed = [key for key, r in zip(jobs, res) if r is not None and r[0] is None]
+        if CARRY == "walk" and missed:
+            # every rung missed: walk from the ladder's best columns, all
+            # groups in one census and one walk
+            from .repair import REPAIRED, repair_carried
+            with _Phase("search"):
+                walked = repair_carried([jobs[key] for key in missed], carry.CARRY_LANES,
+                                        CARRY_WALKERS, max_rounds=CARRY_ROUNDS,
+                                        sync_every=min(8, CARRY_ROUNDS),
+                                        device=(list(DEVICES) or [0])[0], count=_count_kernel)
+            for key, g in zip(missed, walked):
+                if "rungs" not in g:           # nothing ran: refuted, ground, unsupported
+                    continue
+                stats.carry_walk_attempts += 1
+                if g["status"] == REPAIRED:
+                    stats.carry_walk_hits += 1
+                    _note_hit(key, g["assignment"], g["program"])
+                    out[key] = (g["assignment"], g["program"])
     return out
 
 

@@ -2042,6 +2042,27 @@ class _CensusJob:
         return self.eng.census(self.view, M.SEARCH_SEED, 0, self.n_cand, self.n_roots, 0)
 
 
+class _CarryCensusJob:
+    """Where :func:`_repair_steps` with ``carried`` hands the census of its
+    ladder to its driver: ``job`` is a job of ``Engine.carry_census`` on
+    ``eng``; the answer is that call's ``(censuses, start_col, start_nfail,
+    starts)`` for it.  ``free``: some rung has a free leaf (else one lane says
+    all).  ``single()`` is the call for this job alone at ``carry.CARRY_LANES``;
+    :func:`repair_carried` serves all groups of an engine with one call."""
+    stage = 0
+
+    def __init__(self, eng, view, rows, masks, n_roots, walkers, free):
+        self.eng, self.walkers, self.free = eng, walkers, free
+        self.job = (view, rows, masks, n_roots)
+
+    def single(self, lanes=None):
+        from . import carry as CY
+        from . import model as M
+        lanes = CY.CARRY_LANES if lanes is None else lanes
+        return self.eng.carry_census([self.job], M.SEARCH_SEED, 0, lanes if self.free else 1,
+                                     self.walkers)[0]
+
+
 class _WitnessJob:
     """Where :func:`_repair_steps` asks for the leaves of the candidates
     ``picks`` of the full masked program: a list of (n_leaves, 8) rows, one per
@@ -2087,7 +2108,7 @@ class _TreeWalk:
 
 
 def _repair_steps(nodes, n_cand, form, lanes, max_rounds, device, seed, sync_every, scored,
-                  walkers):
+                  walkers, carried=None):
     """:func:`repair_group` in three steps, as a generator.  Prepare: compile,
     build the tables, then two hand-overs: the census is yielded as a
     :class:`_CensusJob` and its ``Census`` sent back, and the starts, picked
@@ -2097,7 +2118,19 @@ def _repair_steps(nodes, n_cand, form, lanes, max_rounds, device, seed, sync_eve
     the single call, :func:`repair_groups` with one batched call for all
     groups; the table-scored walk and the count walk run here.  Finish: the
     fresh evaluation, ``failing``, ``atom_state``, the assignment.  Returns the
-    group's dict."""
+    group's dict.
+
+    ``carried``: an ``(assignment, taken_keys)`` pair of ``carry.plan`` — the
+    walk from the carried starts of DESIGN.md §3.20.  The programs are the
+    constant-keyed eval form of the carry (``carry.compile_census_ck``, the
+    table sizes of ``carry.table_sizes_ck``) with the same probe lists and
+    fallbacks, loaded with ``model.search_leafgen``; the census hand-over is a
+    :class:`_CarryCensusJob` (stage 0) whose answer — the censuses of the
+    ladder's rungs, the start columns, their failing roots and their rows —
+    replaces both the census and the witness hand-over: ``census`` is the
+    per-rung list, ``rungs`` the kept rung indices, ``start`` ``{"col", "rung",
+    "nfail"}`` of start 0 and ``starts`` the columns.  A start 0 that fails no
+    root goes straight to the fresh evaluation; else the walk runs as ever."""
     from . import census as CS
     from . import model as M
     from .assign import unpack
@@ -2108,6 +2141,18 @@ def _repair_steps(nodes, n_cand, form, lanes, max_rounds, device, seed, sync_eve
         raise ValueError("form must be 'search' or 'eval'")
     nodes = list(nodes)
     out: dict = {"n_roots": len(nodes), "status": STUCK}
+    if carried is not None:
+        from . import carry as CY
+        asg, taken = carried
+        sizes = CY.table_sizes_ck(nodes, asg)
+
+        def compile_(probes):
+            if not probes:
+                return CY.compile_eval_ck(nodes, asg, sizes)
+            return CY.compile_census_ck(nodes, asg, probes, sizes)
+    else:
+        def compile_(probes):
+            return CS._compile(nodes, probes, form)
     if len(nodes) > 1 and refuted(nodes):
         out["status"] = CS.REFUTED
         return out
@@ -2124,11 +2169,11 @@ def _repair_steps(nodes, n_cand, form, lanes, max_rounds, device, seed, sync_eve
     resid, table = residuals(nodes) if scored else ([], flat_table(len(nodes)))
     n_amask = 0
     try:
-        ground = M._ground_value(CS._compile(nodes, (), form))
+        ground = M._ground_value(compile_(()))
         if ground is not None:
             out["status"] = CS.GROUND_TRUE if ground else CS.GROUND_FALSE
             return out
-        masked = CS._compile(nodes, CS.mask_probes(nodes), form)
+        masked = compile_(CS.mask_probes(nodes))
         if trees is not None:
             # the atom mask and the trees' residuals; else the table's, below
             extra = CS.mask_probes(trees.atom_nodes) + trees.probes
@@ -2136,8 +2181,7 @@ def _repair_steps(nodes, n_cand, form, lanes, max_rounds, device, seed, sync_eve
             if scored == "sum":
                 # the side rows after the residuals, then the arguments
                 try:
-                    with_trees = CS._compile(
-                        nodes, CS.mask_probes(nodes) + extra + sprobes + uprobes, form)
+                    with_trees = compile_(CS.mask_probes(nodes) + extra + sprobes + uprobes)
                 except Unsupported:
                     with_trees = None
                 if with_trees is None or with_trees.n_user_probes != \
@@ -2148,7 +2192,7 @@ def _repair_steps(nodes, n_cand, form, lanes, max_rounds, device, seed, sync_eve
             if apps and with_trees is None:
                 # the arguments of the UF slots after the residuals
                 try:
-                    with_trees = CS._compile(nodes, CS.mask_probes(nodes) + extra + uprobes, form)
+                    with_trees = compile_(CS.mask_probes(nodes) + extra + uprobes)
                 except Unsupported:
                     with_trees = None
                 if with_trees is None or with_trees.n_user_probes != \
@@ -2156,7 +2200,7 @@ def _repair_steps(nodes, n_cand, form, lanes, max_rounds, device, seed, sync_eve
                     with_trees, apps, uprobes = None, [], []
             try:
                 if with_trees is None:
-                    with_trees = CS._compile(nodes, CS.mask_probes(nodes) + extra, form)
+                    with_trees = compile_(CS.mask_probes(nodes) + extra)
             except Unsupported:
                 with_trees = None
             if with_trees is not None and with_trees.n_user_probes == \
@@ -2168,7 +2212,7 @@ def _repair_steps(nodes, n_cand, form, lanes, max_rounds, device, seed, sync_eve
             # residuals the compiler folds or cannot place: the walkers rank by
             # the count alone
             try:
-                with_resid = CS._compile(nodes, CS.mask_probes(nodes) + resid, form)
+                with_resid = compile_(CS.mask_probes(nodes) + resid)
             except Unsupported:
                 with_resid = None
             if with_resid is not None and \
@@ -2226,27 +2270,50 @@ def _repair_steps(nodes, n_cand, form, lanes, max_rounds, device, seed, sync_eve
         out.update(status=CS.UNSUPPORTED, why="no leaf to move")
         return out
     eng = get_engine(device, nreg=masked.nreg)
-    gens = CS._leafgen(masked, form)
+    if carried is not None:
+        gens = M.search_leafgen(masked)                  # as the carry loads its programs
+        try:
+            pin_rows, ladder = CY.rung_masks(masked, asg, *CY.split_nodes(nodes, taken))
+        except ValueError as e:
+            out.update(status=CS.UNSUPPORTED, why=str(e))
+            return out
+        keep = CY.distinct(ladder)
+    else:
+        gens = CS._leafgen(masked, form)
     view = eng.load(CS.census_view(masked, n_mask), gens, prog_seed=0)
     full = eng.load(masked, gens, prog_seed=0)
-    c = yield _CensusJob(eng, view, len(nodes), n_cand)
-    out["census"] = c
-    if not c.n_cand:
-        return out
-    # the starts, picked on the host: the best candidate, then the sole
-    # blockers' candidates in rank order, padded with the best
-    picks = [c.best_index]
-    if c.best_nfail and scored:
-        for k in c.blockers():
-            if c.sole_index[k] >= 0 and int(c.sole_index[k]) not in picks:
-                picks.append(int(c.sole_index[k]))
-        picks = (picks + [c.best_index] * walkers)[:walkers]
-    rows = yield _WitnessJob(eng, full, picks)
+    if carried is not None:
+        # the ladder's columns censused per rung; the starts are picked on the
+        # device (carry.starts_ref) and their rows come with them
+        free = [CY.n_free(masked, ladder[r]) for r in keep]
+        cs, col, fails, rows = yield _CarryCensusJob(eng, view, pin_rows, ladder[keep], len(nodes),
+                                                    walkers, any(free))
+        out["census"], out["rungs"] = cs, keep
+        picks = [int(v) for v in col]
+        best_nfail = int(fails[0])
+        out["start"] = {"col": picks[0], "rung": keep[picks[0] // max(1, cs[0].n_cand)],
+                        "nfail": best_nfail}
+        rows = list(rows)
+    else:
+        c = yield _CensusJob(eng, view, len(nodes), n_cand)
+        out["census"] = c
+        if not c.n_cand:
+            return out
+        # the starts, picked on the host: the best candidate, then the sole
+        # blockers' candidates in rank order, padded with the best
+        picks = [c.best_index]
+        if c.best_nfail and scored:
+            for k in c.blockers():
+                if c.sole_index[k] >= 0 and int(c.sole_index[k]) not in picks:
+                    picks.append(int(c.sole_index[k]))
+            picks = (picks + [c.best_index] * walkers)[:walkers]
+        rows = yield _WitnessJob(eng, full, picks)
+        out["start"] = {"index": c.best_index, "nfail": c.best_nfail}
+        best_nfail = c.best_nfail
     leaves = rows[0]
-    out["start"] = {"index": c.best_index, "nfail": c.best_nfail}
     out["repair"] = None
     seed = M.SEARCH_SEED if seed is None else seed
-    if c.best_nfail and scored:
+    if best_nfail and scored:
         starts = np.stack(rows)
         wide = eng.load(CS.census_view(masked, n_mask + n_amask + len(resid)), gens, prog_seed=0)
         n = len(nodes)
@@ -2295,7 +2362,7 @@ def _repair_steps(nodes, n_cand, form, lanes, max_rounds, device, seed, sync_eve
                 out["atom_state"] = [(bool(h), 0 if h else int(d)) for h, d in zip(abits, dist)]
             return out
         leaves = res.leaves[res.winner]
-    elif c.best_nfail:
+    elif best_nfail:
         res = eng.repair(view, leaves, len(nodes), seed, lanes, max_rounds, sync_every)
         out["repair"] = res
         if res.nfail:
@@ -2372,6 +2439,78 @@ def repair_groups(groups: Sequence[Sequence], n_cand: int = 1 << 16, form: str =
                                          sync_every, max_bytes)
             for i, res in zip(idx, results):
                 advance(i, res)
+    return out
+
+
+def repair_carried(items, lanes_carry: Optional[int] = None, walkers: Optional[int] = None,
+                   lanes: int = 4096, max_rounds: int = 64, sync_every: int = 8, scored="sum",
+                   max_bytes: Optional[int] = None, device: int = 0, seed: Optional[int] = None,
+                   count=None) -> List[dict]:
+    """The walk from a carried start of the groups
+    ``items``, a list of ``(nodes, assignment, taken_keys)`` as
+    ``carry.run_ladder`` takes them: every group is compiled as
+    :func:`_repair_steps` does with ``carried`` set, the ladders of all groups
+    of an engine are censused in ONE ``Engine.carry_census`` call at
+    ``lanes_carry`` candidates per rung (default ``carry.CARRY_LANES``; 1 when
+    no rung of any group has a free leaf) and ``walkers`` start columns
+    (default ``carry.CARRY_WALKERS``), the groups whose start 0 still fails a
+    root walk together in one ``Engine.walk_batch`` and every group is finished
+    by the fresh evaluation of the full masked program.  Per group the dict of
+    :func:`repair_group` with ``census`` the per-rung list, ``rungs``,
+    ``start`` and ``starts`` as :func:`_repair_steps` describes them, and
+    ``miss_report`` (``carry.miss_report``) where a census ran.
+    ``count(eng, launches)``: called after every launch sequence
+    (``model._count_kernel``)."""
+    from . import carry as CY
+    from . import model as M
+    lanes_carry = CY.CARRY_LANES if lanes_carry is None else lanes_carry
+    walkers = CY.CARRY_WALKERS if walkers is None else walkers
+    items = [(list(nodes), asg, taken) for nodes, asg, taken in items]
+    runs = [_repair_steps(nodes, 0, "eval", lanes, max_rounds, device, seed, sync_every, scored,
+                          walkers, carried=(asg, taken)) for nodes, asg, taken in items]
+    out: List[Optional[dict]] = [None] * len(runs)
+    waiting = {}
+
+    def advance(i, value=None):
+        try:
+            waiting[i] = next(runs[i]) if value is None else runs[i].send(value)
+        except StopIteration as done:
+            waiting.pop(i, None)
+            out[i] = done.value
+
+    for i in range(len(runs)):
+        advance(i)
+    walked = set()
+    while waiting:
+        stage = min(w.stage for w in waiting.values())
+        engines = []
+        for w in waiting.values():
+            if w.stage == stage and not any(e is w.eng for e in engines):
+                engines.append(w.eng)
+        for eng in engines:
+            idx = [i for i in waiting if waiting[i].stage == stage and waiting[i].eng is eng]
+            if stage == _CarryCensusJob.stage:
+                jobs = [waiting[i].job for i in idx]
+                width = max(1, int(lanes_carry)) if any(waiting[i].free for i in idx) else 1
+                width = min(width, (1 << 20) // max(j[2].shape[0] for j in jobs))
+                results = eng.carry_census(jobs, M.SEARCH_SEED, 0, width, walkers)
+                if count:
+                    # fill, interpreter, census, starts
+                    count(eng, 4 * ((len(jobs) + 255) // 256))
+            else:
+                if walked & set(idx):
+                    raise RuntimeError("a group asked for a second walk")
+                walked |= set(idx)
+                results = eng.walk_batch([waiting[i].job for i in idx], lanes, max_rounds,
+                                         sync_every, max_bytes)
+                if count:
+                    # per round: mutate, interpreter, pick
+                    count(eng, 3 * max(r.rounds for r in results))
+            for i, res in zip(idx, results):
+                advance(i, res)
+    for (nodes, _, _), g in zip(items, out):
+        if "rungs" in g:
+            g["miss_report"] = CY.miss_report(nodes, g["census"], g["rungs"])
     return out
 
 

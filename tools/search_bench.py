@@ -145,7 +145,10 @@ def shape_lines(eng, n_queries, n_sample=48):
                               "candidates": M.stats.carry_candidates,
                               "table_gated": M.stats.carry_gated,
                               # MYTHRIL_GPU_CARRY=2 (§3.19): hits per rung
-                              "rung_hits": list(M.stats.carry_rung_hits)},
+                              "rung_hits": list(M.stats.carry_rung_hits),
+                              # MYTHRIL_GPU_CARRY=3 (§3.20): walks from a carried start
+                              "walk_attempts": M.stats.carry_walk_attempts,
+                              "walk_hits": M.stats.carry_walk_hits},
                     # kernel launches per query (a search: its launches and the
                     # witness regeneration; a carry: fill, interpreter, gather)
                     # and the engine calls that made them
