@@ -791,6 +791,67 @@ int mg_carry_ladder_plan_host(const uint32_t* n_leaves /*[n_jobs]*/,
                               uint32_t lanes, uint32_t max_leaves, uint64_t* out_offsets,
                               uint64_t* out_bytes, uint64_t* out_leaf_stride_w);
 
+/* Witness sets on the pin ladder (csrc/mg_carry.h,
+ * mg_carry_sets.hip): a ladder whose rungs carry their own pin rows, so one
+ * compiled group tries several remembered witnesses in one launch sequence.
+ * A job names an eval-form program (loaded with its leaf generators), n_sets
+ * sets of pin rows, set s at pin_rows + s * n_leaves * 8, n_rungs pin masks as
+ * mg_carry_ladder_job has them, and rung_set: the row set of every rung.
+ * The contract is mg_carry_ladder's word for word — the columns (C = R x
+ * lanes, column c on rung r = min(c / lanes, n_rungs - 1) at candidate
+ * c % lanes), first, rung, leaves, fill_out, the sequence (one upload, the set
+ * fill launch, one eval-mode interpreter launch over the job axis at C
+ * candidates, the gather launch of mg_carry_ladder, one download, no host
+ * synchronisation inside) and what mg_last_kernel_ms covers — with ONE
+ * difference: a leaf that mask r pins holds its row of set rung_set[r].  With
+ * one set and rung_set all zero the results are those of mg_carry_ladder.
+ * Refused with MG_E_ARG before any upload or launch, the message beginning
+ * "carry_sets:": whatever mg_carry_ladder refuses; n_sets outside
+ * 1..MG_CARRY_MAX_SETS; a null rung_set; a rung_set[r] not below n_sets. */
+#define MG_CARRY_MAX_SETS 8u
+typedef struct mg_carry_sets_job {
+    const mg_prog* prog;        /* eval-form program, loaded with its leaf generators */
+    const uint32_t* pin_rows;   /* [n_sets][n_leaves][8]                               */
+    const uint32_t* pin_masks;  /* [n_rungs][(n_leaves + 31) / 32], strictest first    */
+    const uint32_t* rung_set;   /* [n_rungs], each < n_sets                            */
+    uint32_t n_rungs;           /* 1..MG_CARRY_MAX_RUNGS                               */
+    uint32_t n_sets;            /* 1..MG_CARRY_MAX_SETS                                */
+} mg_carry_sets_job;
+int mg_carry_ladder_sets(mg_ctx* ctx, const mg_carry_sets_job* jobs, uint32_t n_jobs,
+                         const mg_gen* gen, uint32_t lanes,
+                         int64_t* first /*[n_jobs], -1: none*/,
+                         int64_t* rung /*[n_jobs], -1: none*/,
+                         uint32_t* leaves /*[n_jobs][max_leaves][8]*/, uint32_t max_leaves,
+                         uint32_t* fill_out /*NULL, or every job's leaf region copied back*/);
+/* Host-only (no GPU): mg_carry_fill_rungs_host for a job of
+ * mg_carry_ladder_sets, from the set fill kernel's lane function.  MG_E_ARG as
+ * mg_carry_fill_rungs_host, and for n_sets outside 1..MG_CARRY_MAX_SETS, a
+ * null rung_set and a rung_set[r] not below n_sets. */
+int mg_carry_fill_sets_host(const mg_leafgen* leaves, uint32_t n_leaves, const uint32_t* consts,
+                            uint32_t n_consts, uint64_t prog_seed,
+                            const uint32_t* pin_rows /*[n_sets][n_leaves][8]*/,
+                            const uint32_t* pin_masks /*[n_rungs][(n_leaves + 31) / 32]*/,
+                            const uint32_t* rung_set /*[n_rungs]*/, uint32_t n_rungs,
+                            uint32_t n_sets, uint64_t seed, uint64_t first_index, uint32_t lanes,
+                            uint32_t cols, uint32_t col0, uint32_t n_cols, uint32_t* out);
+/* Host-only (no GPU): the plan of the device buffer mg_carry_ladder_sets uses.
+ * out_offsets: mg_carry_ladder_plan_host's table — the same regions under the
+ * same indices, job j's rows region holding its n_sets[j] row sets (n_sets[j]
+ * x n_leaves[j] x 32 bytes) — followed by MG_CARRY_SETS_SHARED entries (the
+ * set records) and MG_CARRY_SETS_JOB_REGIONS per job (its rung_set, n_rungs
+ * u32).  In address order: descriptors, records, first words, every job's
+ * masks, row sets and generators, the set records, every job's rung_set, the
+ * output block, all leaf regions; every region 256-byte aligned.  MG_E_ARG
+ * for what mg_carry_ladder_plan_host refuses, an n_sets outside
+ * 1..MG_CARRY_MAX_SETS and sizes beyond 64 bits. */
+#define MG_CARRY_SETS_SHARED 1
+#define MG_CARRY_SETS_JOB_REGIONS 1
+int mg_carry_sets_plan_host(const uint32_t* n_leaves /*[n_jobs]*/,
+                            const uint32_t* n_rungs /*[n_jobs]*/,
+                            const uint32_t* n_sets /*[n_jobs]*/, uint32_t n_jobs, uint32_t lanes,
+                            uint32_t max_leaves, uint64_t* out_offsets, uint64_t* out_bytes,
+                            uint64_t* out_leaf_stride_w);
+
 /* The census of a pin ladder (csrc/mg_carry.h,
  * mg_carry_census.hip): mg_carry_ladder's columns, and instead of the lowest
  * true column alone a verdict census of every rung and `walkers` (W) start

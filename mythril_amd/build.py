@@ -15,7 +15,7 @@ JIT_STUB = os.path.join(LIBDIR, "mg_jit_stub.s")
 SOURCES = ["mg_interp_asm.hip", "mg_keccak.hip", "mg_census.hip", "mg_census_batch.hip",
            "mg_repair.hip", "mg_walk.hip", "mg_walk_tree.hip", "mg_walk_aim.hip", "mg_walk_sum.hip",
            "mg_walk_batch.hip", "mg_carry.hip", "mg_carry_ladder.hip",
-           "mg_carry_census.hip", "mg_host.cpp", "mg_api.cpp"]
+           "mg_carry_sets.hip", "mg_carry_census.hip", "mg_host.cpp", "mg_api.cpp"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("MYTHGPU_ARCH", "gfx950")
 

@@ -21,6 +21,13 @@ extended group is compiled in eval form WITH constant keys
 (:func:`compile_eval_ck`), several pin sets — all, read, new (:func:`rungs`) —
 are tried strictest first, and ``Engine.carry_ladder`` evaluates every rung of
 every job in the same three launches (:func:`run_ladder`).
+
+``MYTHRIL_GPU_CARRY=4`` gives the ladder's rungs their own pin rows (DESIGN.md
+§3.21): the remembered subsets :func:`union` skips because they share a name
+with one taken before them become further pin sets (:func:`plan_sets`), every
+rung of every set is a block of columns of the one compiled group
+(:func:`rungs_sets`), and ``Engine.carry_ladder_sets`` evaluates them in the
+ladder's three launches (:func:`run_sets`).
 """
 
 from __future__ import annotations
@@ -377,6 +384,132 @@ def run_ladder(eng, items, seed: int, leafgen, lanes: Optional[int] = None, phas
         for k, prog, f, keep, (first, rung, leaves) in zip(where, progs, free, kept, res):
             out[k] = (unpack(prog, leaves) if first >= 0 else None, prog,
                       sum(width if x else 1 for x in f), keep[rung] if first >= 0 else -1)
+    return out
+
+
+# ---------------------------------------------------------------------------
+# Witness sets (MYTHRIL_GPU_CARRY=4): the ladder with several
+# pin sets per group, every rung pinning from the rows of its own set
+# ---------------------------------------------------------------------------
+
+# pin sets tried per extension (MYTHRIL_GPU_CARRY_SETS, 1..8).  Untuned: 4 is
+# enough for the parent and child a JUMPI leaves in the memo and one more pair;
+# DESIGN.md §7 round 19 records what sets beyond the first carry
+MAX_SETS = 4
+SETS_LIMIT = 8                 # include/mythgpu.h MG_CARRY_MAX_SETS
+
+
+def plan_sets(key: frozenset, memo: HitMemo, max_sets: Optional[int] = None):
+    """:func:`plan` with alternatives, a pure function of (key, memo):
+    ``("exact", assignment)`` for a remembered key, else ``("extend",
+    [(assignment, subset keys taken), ...])`` with at most ``max_sets``
+    (default ``MAX_SETS``) pin sets, or None.  Alternative 0 is :func:`plan`'s
+    union.  Alternative i > 0 is :func:`union` over ``memo.subsets(key)`` with
+    the first subset no earlier alternative took moved to the front, the others
+    behind it in their original order — so every remembered subset that
+    :func:`union` skipped for a shared name heads a pin set of its own, until
+    every subset has been taken by some alternative.  An alternative that
+    interprets no name is dropped."""
+    hit = memo.hits.get(key)
+    if hit is not None:
+        return ("exact", hit)
+    subs = memo.subsets(key)
+    max_sets = MAX_SETS if max_sets is None else max_sets
+    alts, covered = [], set()
+    for _ in range(max(1, min(int(max_sets), len(subs)))):
+        start = next((i for i in range(len(subs)) if i not in covered), None)
+        if start is None:
+            break
+        order = [start] + [i for i in range(len(subs)) if i != start]
+        asg, taken = union([memo.hits[subs[i]] for i in order])
+        covered.update(order[t] for t in taken)
+        if _names(asg):
+            alts.append((asg, [subs[order[t]] for t in taken]))
+    return ("extend", alts) if alts else None
+
+
+def sizes_sets(nodes, alts) -> Dict[str, int]:
+    """The table sizes of the one program all alternatives of a group are
+    evaluated on: per table the maximum of :func:`table_sizes_ck` over the
+    alternatives, so every alternative's tables fit."""
+    out: Dict[str, int] = {}
+    for asg, _ in alts:
+        for name, k in table_sizes_ck(nodes, asg).items():
+            out[name] = max(out.get(name, 0), k)
+    return out
+
+
+def _mask_bits(mask: np.ndarray, n: int) -> np.ndarray:
+    l = np.arange(n)
+    return ((mask[l >> 5] >> (l & 31).astype(np.uint32)) & 1).astype(bool)
+
+
+def rungs_sets(program: Program, alts, nodes):
+    """``(rows, masks, rung_set, kept)`` of one job of the ladder with sets:
+    ``rows`` ((n_sets, n_leaves, 8) uint32), set s as :func:`rung_masks` gives
+    the rows of alternative s of ``alts`` (:func:`plan_sets`'s pairs);
+    ``masks`` ((n_rungs, words) uint32) and ``rung_set`` ((n_rungs,) uint32,
+    each below n_sets), the rungs in the order they are tried; ``kept``, per
+    rung its ``(index in RUNG_NAMES, set)``.  The order is rung-major and
+    set-minor — ("all", set 0), ("all", set 1), ..., ("read", set 0), ... — so
+    the lowest true column keeps as much of a remembered model as possible and
+    alternative 0 wins ties.  A rung whose mask and pinned rows repeat an
+    earlier rung's is dropped (rows of leaves the mask leaves free do not
+    count); the list is cut at ``MAX_RUNGS``."""
+    n = len(program.leaves)
+    made = [rung_masks(program, asg, *split_nodes(nodes, taken)) for asg, taken in alts]
+    rows = np.stack([r for r, _ in made]).astype(np.uint32).reshape(len(made), n, 8)
+    kept, seen = [], set()
+    for r in range(len(RUNG_NAMES)):
+        for s, (_, ladder) in enumerate(made):
+            what = (ladder[r].tobytes(), rows[s][_mask_bits(ladder[r], n)].tobytes())
+            if what not in seen:
+                seen.add(what)
+                kept.append((r, s))
+    kept = kept[:MAX_RUNGS]
+    masks = np.stack([made[s][1][r] for r, s in kept]).astype(np.uint32)
+    return rows, masks, np.array([s for _, s in kept], dtype=np.uint32), kept
+
+
+def run_sets(eng, items, seed: int, leafgen, lanes: Optional[int] = None, phase=None):
+    """:func:`run_ladder` with pin sets: one ``Engine.carry_ladder_sets`` call
+    for ``items``, a list of ``(nodes, alts)`` (:func:`plan_sets`'s second
+    element).  A group is compiled ONCE, under alternative 0 at the table
+    sizes of :func:`sizes_sets`; its alternatives cost columns.  Per item
+    ``(assignment, program, candidates, rung, set)`` — as :func:`run_ladder`,
+    and the alternative whose rows the hit column pinned (-1 on a miss) — or
+    None where the group has no eval form."""
+    import contextlib
+    from .ir import Unsupported
+    phase = phase or (lambda name: contextlib.nullcontext())
+    lanes = CARRY_LANES if lanes is None else lanes
+    jobs, progs, free, kept, where = [], [], [], [], []
+    with phase("compile"):
+        for k, (nodes, alts) in enumerate(items):
+            try:
+                prog = compile_eval_ck(nodes, alts[0][0], sizes_sets(nodes, alts))
+                rows, masks, rung_set, keep = rungs_sets(prog, alts, nodes)
+            except (Unsupported, ValueError):
+                continue
+            progs.append(prog)
+            kept.append(keep)
+            free.append([n_free(prog, m) for m in masks])
+            jobs.append((prog, rows, masks, rung_set))
+            where.append(k)
+    out: List = [None] * len(items)
+    if not jobs:
+        return out
+    width = max(1, int(lanes)) if any(any(f) for f in free) else 1
+    width = min(width, (1 << 20) // max(len(keep) for keep in kept))   # the call's column cap
+    with phase("load"):
+        loaded = [(eng.load(p, leafgen(p), prog_seed=0), r, m, s) for p, r, m, s in jobs]
+    with phase("search"):
+        res = eng.carry_ladder_sets(loaded, seed, 0, width)
+        for k, prog, f, keep, (first, rung, leaves) in zip(where, progs, free, kept, res):
+            hit = first >= 0
+            out[k] = (unpack(prog, leaves) if hit else None, prog,
+                      sum(width if x else 1 for x in f),
+                      keep[rung][0] if hit else -1, keep[rung][1] if hit else -1)
     return out
 
 

@@ -172,6 +172,11 @@ hipError_t mg_launch_carry_gather_rungs(const mg_carry_dev_job* d_jobs, uint32_t
                                         uint32_t cols, uint32_t max_leaves,
                                         long long* d_out_first, long long* d_out_rung,
                                         uint32_t* d_out_leaves, hipStream_t stream);
+// the fill of mg_carry_ladder_sets (mg_carry_sets.hip); its gather is the ladder's
+hipError_t mg_launch_carry_fill_sets(const mg_carry_dev_job* d_jobs,
+                                     const mg_carry_sets_dev_job* d_sjobs, uint32_t n_jobs,
+                                     uint32_t most_leaves, uint64_t seed, uint64_t first_index,
+                                     uint32_t lanes, uint32_t cols, hipStream_t stream);
 // the two after mg_carry_census's (mg_carry_census.hip)
 hipError_t mg_launch_carry_census(const mg_carry_dev_job* d_jobs,
                                   const mg_carry_census_dev_job* d_cjobs, uint32_t n_jobs,
@@ -2187,6 +2192,159 @@ int mg_carry_ladder_plan_host(const uint32_t* n_leaves, const uint32_t* n_rungs,
                               uint64_t* out_bytes, uint64_t* out_leaf_stride_w) {
     return mg_carry_ladder_plan(n_leaves, n_rungs, n_jobs, lanes, max_leaves, out_offsets,
                                 out_bytes, out_leaf_stride_w) ? MG_OK : MG_E_ARG;
+}
+
+// Witness sets on the pin ladder (include/mythgpu.h mg_carry_ladder_sets,
+// DESIGN.md §3.21; csrc/mg_carry.h, mg_carry_sets.hip): mg_carry_ladder's
+// sequence with n_sets row sets per job and a row set per rung.
+int mg_carry_ladder_sets(mg_ctx* ctx, const mg_carry_sets_job* jobs, uint32_t n_jobs,
+                         const mg_gen* gen, uint32_t lanes, int64_t* first, int64_t* rung,
+                         uint32_t* leaves, uint32_t max_leaves, uint32_t* fill_out) {
+    if (!ctx) return MG_E_ARG;
+    if (!jobs || !gen || !first || !rung || !leaves)
+        return fail(ctx, MG_E_ARG, "carry_sets: null argument");
+    int rc = carry_ladder_check_shared(ctx, "carry_sets", n_jobs, lanes, max_leaves);
+    if (rc != MG_OK) return rc;
+    std::vector<uint32_t> n_leaves(n_jobs), n_rungs(n_jobs), n_sets(n_jobs);
+    uint32_t most = 0, max_lds = 0, top = 0;
+    for (uint32_t g = 0; g < n_jobs; ++g) {
+        const mg_carry_sets_job& j = jobs[g];
+        const mg_carry_ladder_job as_ladder = {j.prog, j.pin_rows, j.pin_masks, j.n_rungs, 0};
+        rc = carry_ladder_check_job(ctx, "carry_sets", g, as_ladder, max_leaves);
+        if (rc != MG_OK) return rc;
+        if (j.n_sets < 1 || j.n_sets > MG_CARRY_MAX_SETS)
+            return fail(ctx, MG_E_ARG, "carry_sets: job %u: %u sets outside 1..%u", g, j.n_sets,
+                        MG_CARRY_MAX_SETS);
+        if (!j.rung_set) return fail(ctx, MG_E_ARG, "carry_sets: job %u: null rung_set", g);
+        if (!mg_carry_rung_set_ok(j.rung_set, j.n_rungs, j.n_sets))
+            return fail(ctx, MG_E_ARG, "carry_sets: job %u: a rung_set entry not below its %u "
+                        "sets", g, j.n_sets);
+        n_leaves[g] = j.prog->n_leaves;
+        n_rungs[g] = j.n_rungs;
+        n_sets[g] = j.n_sets;
+        most = n_leaves[g] > most ? n_leaves[g] : most;
+        top = j.n_rungs > top ? j.n_rungs : top;
+        max_lds = j.prog->n_lds > max_lds ? j.prog->n_lds : max_lds;
+    }
+    uint32_t cols = 0;
+    if (!mg_carry_sets_ok(n_rungs.data(), n_sets.data(), n_jobs, lanes, &cols))
+        return fail(ctx, MG_E_ARG, "carry_sets: %u rungs of %u lanes above %u columns", top,
+                    lanes, MG_REPAIR_MAX_LANES);
+    std::vector<uint64_t> off(MG_CS_TABLE(n_jobs));
+    uint64_t bytes = 0, leaf_w = 0;
+    if (!mg_carry_sets_plan(n_leaves.data(), n_rungs.data(), n_sets.data(), n_jobs, lanes,
+                            max_leaves, off.data(), &bytes, &leaf_w))
+        return fail(ctx, MG_E_ARG, "carry_sets: the batch's buffer exceeds 64 bits");
+    if (bytes > MG_WALK_BATCH_DEFAULT_BYTES)
+        return fail(ctx, MG_E_ARG, "carry_sets: %llu bytes needed for %u jobs at %u columns, "
+                    "at most %llu; pass fewer jobs, rungs or lanes", (unsigned long long)bytes,
+                    n_jobs, cols, (unsigned long long)MG_WALK_BATCH_DEFAULT_BYTES);
+    HIPCHECK(ctx, hipSetDevice(ctx->device));
+    void* ws;
+    rc = workspace(ctx, (size_t)bytes + 256, &ws);
+    if (rc) return rc;
+    uint8_t* w = (uint8_t*)ws;
+    // the host image of everything uploaded, at the offsets of the plan
+    const size_t up_b = (size_t)off[MG_CY_OUT];
+    std::vector<uint8_t> img(up_b, 0);
+    mg_pdesc* h_descs = (mg_pdesc*)(img.data() + off[MG_CY_DESCS]);
+    mg_carry_dev_job* h_jobs = (mg_carry_dev_job*)(img.data() + off[MG_CY_JOBS]);
+    mg_carry_sets_dev_job* h_sjobs =
+        (mg_carry_sets_dev_job*)(img.data() + off[MG_CS_BASE(n_jobs) + MG_CS_RECORDS]);
+    memset(img.data() + off[MG_CY_FIRST], 0xFF, (size_t)n_jobs * 8);
+    for (uint32_t g = 0; g < n_jobs; ++g) {
+        const mg_carry_sets_job& j = jobs[g];
+        const uint32_t n = n_leaves[g];
+        auto at = [&](uint32_t k) { return off[MG_CY_OFF(g, k)]; };
+        const uint64_t at_set = off[MG_CS_OFF(n_jobs, g, MG_CS_RUNG_SET)];
+        if (n) {
+            memcpy(img.data() + at(MG_CY_MASK), j.pin_masks,
+                   (size_t)((n + 31) / 32) * 4 * j.n_rungs);
+            memcpy(img.data() + at(MG_CY_ROWS), j.pin_rows, (size_t)n * 32 * j.n_sets);
+            memcpy(img.data() + at(MG_CY_GEN), j.prog->leafgen.data(), (size_t)n * sizeof(mg_leafgen));
+        }
+        memcpy(img.data() + at_set, j.rung_set, (size_t)j.n_rungs * 4);
+        h_descs[g] = j.prog->h_desc;
+        mg_carry_dev_job& d = h_jobs[g];
+        d.mask = (const uint32_t*)(w + at(MG_CY_MASK));
+        d.rows = (const uint32_t*)(w + at(MG_CY_ROWS));
+        d.gen = (const mg_leafgen*)(w + at(MG_CY_GEN));
+        d.consts = j.prog->h_desc.consts;              // the first n_consts entries: as loaded
+        d.leaves = (uint32_t*)(w + at(MG_CY_LEAVES));
+        d.prog_seed = j.prog->h_desc.prog_seed;
+        d.n_leaves = n;
+        d.n_rungs = j.n_rungs;
+        h_sjobs[g].rung_set = (const uint32_t*)(w + at_set);
+        h_sjobs[g].n_sets = j.n_sets;
+        h_sjobs[g].pad = 0;
+    }
+    const mg_pdesc* d_descs = (const mg_pdesc*)(w + off[MG_CY_DESCS]);
+    const mg_carry_dev_job* d_jobs = (const mg_carry_dev_job*)(w + off[MG_CY_JOBS]);
+    const mg_carry_sets_dev_job* d_sjobs =
+        (const mg_carry_sets_dev_job*)(w + off[MG_CS_BASE(n_jobs) + MG_CS_RECORDS]);
+    unsigned long long* d_first = (unsigned long long*)(w + off[MG_CY_FIRST]);
+    long long* d_out_first = (long long*)(w + off[MG_CY_OUT]);
+    long long* d_out_rung = d_out_first + n_jobs;
+    uint32_t* d_out_leaves = (uint32_t*)(w + off[MG_CY_OUT] + (size_t)n_jobs * 16);
+    HIPCHECK(ctx, hipMemcpyAsync(w, img.data(), up_b, hipMemcpyHostToDevice, ctx->stream));
+    mg_run run = empty_run();
+    run.leaves = (const uint32_t*)(w + off[MG_CY_OFF(0, MG_CY_LEAVES)]);
+    run.leaves_prog_words = leaf_w;
+    run.first_sat = d_first;                           // first_index 0: the column itself
+    run.stride = cols;
+    run.n_assign = cols;
+    timing_begin(ctx);
+    HIPCHECK(ctx, mg_launch_carry_fill_sets(d_jobs, d_sjobs, n_jobs, most, gen->seed,
+                                            gen->first_index, lanes, cols, ctx->stream));
+    HIPCHECK(ctx, launch(ctx, 0, d_descs, n_jobs, run, max_lds, ctx->stream));
+    HIPCHECK(ctx, mg_launch_carry_gather_rungs(d_jobs, n_jobs, d_first, lanes, cols, max_leaves,
+                                               d_out_first, d_out_rung, d_out_leaves,
+                                               ctx->stream));
+    timing_end(ctx);
+    const size_t out_b = (size_t)n_jobs * 16 + (size_t)n_jobs * max_leaves * 32;
+    std::vector<uint8_t> h_out(out_b);
+    HIPCHECK(ctx, hipMemcpyAsync(h_out.data(), d_out_first, out_b, hipMemcpyDeviceToHost,
+                                 ctx->stream));
+    if (fill_out && leaf_w)
+        HIPCHECK(ctx, hipMemcpyAsync(fill_out, run.leaves, (size_t)n_jobs * leaf_w * 4,
+                                     hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHECK(ctx, hipStreamSynchronize(ctx->stream));
+    timing_read(ctx);
+    memcpy(first, h_out.data(), (size_t)n_jobs * 8);
+    memcpy(rung, h_out.data() + (size_t)n_jobs * 8, (size_t)n_jobs * 8);
+    memcpy(leaves, h_out.data() + (size_t)n_jobs * 16, (size_t)n_jobs * max_leaves * 32);
+    return MG_OK;
+}
+
+int mg_carry_fill_sets_host(const mg_leafgen* leaves, uint32_t n_leaves, const uint32_t* consts,
+                            uint32_t n_consts, uint64_t prog_seed, const uint32_t* pin_rows,
+                            const uint32_t* pin_masks, const uint32_t* rung_set, uint32_t n_rungs,
+                            uint32_t n_sets, uint64_t seed, uint64_t first_index, uint32_t lanes,
+                            uint32_t cols, uint32_t col0, uint32_t n_cols, uint32_t* out) {
+    if (n_rungs < 1 || n_rungs > MG_CARRY_MAX_RUNGS) return MG_E_ARG;
+    if (n_sets < 1 || n_sets > MG_CARRY_MAX_SETS || !mg_carry_rung_set_ok(rung_set, n_rungs, n_sets))
+        return MG_E_ARG;
+    if (lanes < 1 || cols < lanes || cols > MG_REPAIR_MAX_LANES || col0 > cols ||
+        n_cols > cols - col0)
+        return MG_E_ARG;
+    if (n_leaves == 0 || n_cols == 0) return MG_OK;
+    if (!leaves || !pin_rows || !pin_masks || !out || (n_consts && !consts)) return MG_E_ARG;
+    if (!mg_carry_gen_ok(leaves, n_leaves, n_consts)) return MG_E_ARG;
+    const uint32_t words = (n_leaves + 31) / 32;
+    for (uint32_t l = 0; l < n_leaves; ++l)
+        for (uint32_t i = 0; i < n_cols; ++i)
+            mg_carry_fill_set_lane(pin_masks, words, n_rungs, rung_set, pin_rows, n_leaves, leaves,
+                                   consts, prog_seed, seed, first_index, l, col0 + i, lanes,
+                                   n_cols, i, out);
+    return MG_OK;
+}
+
+int mg_carry_sets_plan_host(const uint32_t* n_leaves, const uint32_t* n_rungs,
+                            const uint32_t* n_sets, uint32_t n_jobs, uint32_t lanes,
+                            uint32_t max_leaves, uint64_t* out_offsets, uint64_t* out_bytes,
+                            uint64_t* out_leaf_stride_w) {
+    return mg_carry_sets_plan(n_leaves, n_rungs, n_sets, n_jobs, lanes, max_leaves, out_offsets,
+                              out_bytes, out_leaf_stride_w) ? MG_OK : MG_E_ARG;
 }
 
 // The census of a pin ladder (include/mythgpu.h mg_carry_census, DESIGN.md

@@ -34,6 +34,12 @@
  * the other, the output block n_jobs i64 first, n_jobs i64 rung and the rows,
  * and leaf regions of C columns (mg_carry_ladder_plan).
  *
+ * mg_carry_ladder_sets is the ladder with n_sets row sets
+ * per job: rung r pins from row set rung_set[r] (mg_carry_fill_set_lane).  Its
+ * buffer is the ladder's with a job's rows region holding its n_sets row sets
+ * one after the other, and before the output block one record per job and
+ * every job's rung_set (mg_carry_sets_plan, after the ladder's plan).
+ *
  * mg_carry_census adds per-rung counter blocks, probe
  * regions and an output block of W starts to the ladder's buffer
  * (mg_carry_census_plan, at the end of this file, with the start rule). */
@@ -193,6 +199,22 @@ MG_CARRY_FN void mg_carry_fill_rung_lane(const uint32_t* masks, uint32_t words, 
                        first_index, leaf, col % lanes, stride, out_col, out);
 }
 
+/* The set fill kernel's lane function: mg_carry_fill_rung_lane for a job whose
+ * n_sets row sets of n_leaves x 8 words each lie one after the other at
+ * `rows`; the column's rung r pins from row set rung_set[r]. */
+MG_CARRY_FN void mg_carry_fill_set_lane(const uint32_t* masks, uint32_t words, uint32_t n_rungs,
+                                        const uint32_t* rung_set, const uint32_t* rows,
+                                        uint32_t n_leaves, const mg_leafgen* gen,
+                                        const uint32_t* consts, uint64_t prog_seed, uint64_t seed,
+                                        uint64_t first_index, uint32_t leaf, uint32_t col,
+                                        uint32_t lanes, uint64_t stride, uint64_t out_col,
+                                        uint32_t* out) {
+    const uint32_t r = mg_carry_rung(col, lanes, n_rungs);
+    mg_carry_fill_lane(masks + (uint64_t)r * words, rows + (uint64_t)rung_set[r] * n_leaves * 8,
+                       gen, consts, prog_seed, seed, first_index, leaf, col % lanes, stride,
+                       out_col, out);
+}
+
 /* the shared counts mg_carry_batch accepts */
 static inline bool mg_carry_shared_ok(uint32_t n_jobs, uint32_t lanes) {
     return n_jobs >= 1 && n_jobs <= MG_CARRY_MAX_JOBS && lanes >= 1 &&
@@ -219,11 +241,12 @@ static inline bool mg_cy_add(uint64_t* a, uint64_t count, uint64_t unit) {
 }
 
 /* The uploaded front of every carry buffer: descriptors, job records, first
- * words, then job by job its masks (n_rungs[g] of them, NULL: one each), rows
- * and generators.  *at: where the front ends; *most: the largest n_leaves. */
+ * words, then job by job its masks (n_rungs[g] of them, NULL: one each), row
+ * sets (n_sets[g] of them, NULL: one each) and generators.  *at: where the
+ * front ends; *most: the largest n_leaves. */
 static inline bool mg_cy_plan_front(const uint32_t* n_leaves, const uint32_t* n_rungs,
-                                    uint32_t n_jobs, uint64_t* offsets, uint64_t* at_out,
-                                    uint32_t* most_out) {
+                                    const uint32_t* n_sets, uint32_t n_jobs, uint64_t* offsets,
+                                    uint64_t* at_out, uint32_t* most_out) {
     uint64_t at = 0;
     offsets[MG_CY_DESCS] = at;
     if (!mg_cy_add(&at, n_jobs, sizeof(mg_pdesc))) return false;
@@ -238,7 +261,7 @@ static inline bool mg_cy_plan_front(const uint32_t* n_leaves, const uint32_t* n_
         offsets[MG_CY_OFF(g, MG_CY_MASK)] = at;
         if (!mg_cy_add(&at, (n + 31) / 32 * (n_rungs ? n_rungs[g] : 1u), 4)) return false;
         offsets[MG_CY_OFF(g, MG_CY_ROWS)] = at;
-        if (!mg_cy_add(&at, n, 32)) return false;
+        if (!mg_cy_add(&at, n * (n_sets ? n_sets[g] : 1u), 32)) return false;
         offsets[MG_CY_OFF(g, MG_CY_GEN)] = at;
         if (!mg_cy_add(&at, n, sizeof(mg_leafgen))) return false;
     }
@@ -276,7 +299,7 @@ static inline bool mg_cy_plan(const uint32_t* n_leaves, const uint32_t* n_rungs,
                               uint64_t* offsets, uint64_t* bytes, uint64_t* leaf_stride_w) {
     uint64_t at = 0;
     uint32_t most = 0;
-    if (!mg_cy_plan_front(n_leaves, n_rungs, n_jobs, offsets, &at, &most)) return false;
+    if (!mg_cy_plan_front(n_leaves, n_rungs, nullptr, n_jobs, offsets, &at, &most)) return false;
     if (!mg_cy_plan_back(n_jobs, most, cols, (uint64_t)max_leaves * 32u + out_fixed, offsets, &at,
                          leaf_stride_w))
         return false;
@@ -323,6 +346,77 @@ static inline bool mg_carry_ladder_plan(const uint32_t* n_leaves, const uint32_t
         return false;
     return mg_cy_plan(n_leaves, n_rungs, n_jobs, cols, 16, max_leaves, offsets, bytes,
                       leaf_stride_w);
+}
+
+/* mg_carry_ladder_sets: the ladder's buffer with n_sets[g]
+ * row sets in job g's rows region and two kinds of region more, in this order:
+ *   descs, jobs, first, per job masks, row sets, generators  as the ladder
+ *   set records           one mg_carry_sets_dev_job per job
+ *   per job, its rung_set n_rungs u32: the row set of every rung
+ *     (up to here one upload)
+ *   out, per job its leaves                                  as the ladder
+ * offsets[]: the ladder's table, then MG_CS_SHARED entries, then
+ * MG_CS_JOB_REGIONS per job. */
+enum { MG_CS_RECORDS, MG_CS_SHARED };
+enum { MG_CS_RUNG_SET, MG_CS_JOB_REGIONS };
+#define MG_CS_BASE(n_jobs) ((size_t)MG_CY_SHARED + (size_t)(n_jobs) * MG_CY_JOB_REGIONS)
+#define MG_CS_OFF(n_jobs, g, k) \
+    (MG_CS_BASE(n_jobs) + MG_CS_SHARED + (size_t)(g) * MG_CS_JOB_REGIONS + (k))
+#define MG_CS_TABLE(n_jobs) (MG_CS_BASE(n_jobs) + MG_CS_SHARED + (size_t)(n_jobs) * MG_CS_JOB_REGIONS)
+
+static_assert(MG_CARRY_SETS_SHARED == MG_CS_SHARED &&
+              MG_CARRY_SETS_JOB_REGIONS == MG_CS_JOB_REGIONS,
+              "include/mythgpu.h documents the length of the offset table");
+
+/* What the set fill kernel reads of a job beside its mg_carry_dev_job (same
+ * index), whose `rows` is the first of the job's n_sets row sets. */
+struct mg_carry_sets_dev_job {
+    const uint32_t* rung_set;   /* [n_rungs], each below n_sets */
+    uint32_t n_sets;
+    uint32_t pad;
+};
+
+/* every rung of a job names one of its row sets */
+static inline bool mg_carry_rung_set_ok(const uint32_t* rung_set, uint32_t n_rungs,
+                                        uint32_t n_sets) {
+    if (!rung_set) return false;
+    for (uint32_t r = 0; r < n_rungs; ++r)
+        if (rung_set[r] >= n_sets) return false;
+    return true;
+}
+
+/* the shared counts mg_carry_ladder_sets accepts: the ladder's, and 1 to
+ * MG_CARRY_MAX_SETS row sets per job */
+static inline bool mg_carry_sets_ok(const uint32_t* n_rungs, const uint32_t* n_sets,
+                                    uint32_t n_jobs, uint32_t lanes, uint32_t* cols) {
+    if (!n_sets || !mg_carry_ladder_ok(n_rungs, n_jobs, lanes, cols)) return false;
+    for (uint32_t g = 0; g < n_jobs; ++g)
+        if (n_sets[g] < 1 || n_sets[g] > MG_CARRY_MAX_SETS) return false;
+    return true;
+}
+
+/* mg_carry_ladder_plan for mg_carry_ladder_sets. */
+static inline bool mg_carry_sets_plan(const uint32_t* n_leaves, const uint32_t* n_rungs,
+                                      const uint32_t* n_sets, uint32_t n_jobs, uint32_t lanes,
+                                      uint32_t max_leaves, uint64_t* offsets, uint64_t* bytes,
+                                      uint64_t* leaf_stride_w) {
+    uint32_t cols = 0;
+    if (!n_leaves || !offsets || !bytes || !mg_carry_sets_ok(n_rungs, n_sets, n_jobs, lanes, &cols))
+        return false;
+    uint64_t at = 0;
+    uint32_t most = 0;
+    if (!mg_cy_plan_front(n_leaves, n_rungs, n_sets, n_jobs, offsets, &at, &most)) return false;
+    offsets[MG_CS_BASE(n_jobs) + MG_CS_RECORDS] = at;
+    if (!mg_cy_add(&at, n_jobs, sizeof(mg_carry_sets_dev_job))) return false;
+    for (uint32_t g = 0; g < n_jobs; ++g) {
+        offsets[MG_CS_OFF(n_jobs, g, MG_CS_RUNG_SET)] = at;
+        if (!mg_cy_add(&at, n_rungs[g], 4)) return false;
+    }
+    if (!mg_cy_plan_back(n_jobs, most, cols, (uint64_t)max_leaves * 32u + 16u, offsets, &at,
+                         leaf_stride_w))
+        return false;
+    *bytes = at;
+    return true;
 }
 
 /* mg_carry_census: the ladder's fill and evaluation, then a
@@ -399,7 +493,8 @@ static inline int mg_carry_census_plan(const uint32_t* n_leaves, const uint32_t*
     }
     uint64_t at = 0;
     uint32_t most = 0;
-    if (!mg_cy_plan_front(n_leaves, n_rungs, n_jobs, offsets, &at, &most)) return MG_CC_OVERFLOW;
+    if (!mg_cy_plan_front(n_leaves, n_rungs, nullptr, n_jobs, offsets, &at, &most))
+        return MG_CC_OVERFLOW;
     offsets[MG_CC_BASE(n_jobs) + MG_CC_RECORDS] = at;
     if (!mg_cy_add(&at, n_jobs, sizeof(mg_carry_census_dev_job))) return MG_CC_OVERFLOW;
     for (uint32_t g = 0; g < n_jobs; ++g) {

@@ -42,7 +42,8 @@ EXPORTS = ("mg_init", "mg_init_layout", "mg_layouts", "mg_free", "mg_last_error"
            "mg_census_batch_plan_host", "mg_census_batch_blocks_host", "mg_batch_witness",
            "mg_carry_batch", "mg_carry_fill_host", "mg_carry_plan_host", "mg_carry_ladder",
            "mg_carry_fill_rungs_host", "mg_carry_ladder_plan_host", "mg_carry_census",
-           "mg_carry_census_plan_host", "mg_carry_starts_host")
+           "mg_carry_census_plan_host", "mg_carry_starts_host", "mg_carry_ladder_sets",
+           "mg_carry_fill_sets_host", "mg_carry_sets_plan_host")
 
 
 def layouts() -> Dict[int, Tuple[int, int]]:
@@ -133,6 +134,12 @@ class CarryLadderJob(C.Structure):
                 ("n_rungs", C.c_uint32), ("pad", C.c_uint32)]
 
 
+class CarrySetsJob(C.Structure):
+    """mg_carry_sets_job (include/mythgpu.h): one job of mg_carry_ladder_sets."""
+    _fields_ = [("prog", C.c_void_p), ("pin_rows", C.c_void_p), ("pin_masks", C.c_void_p),
+                ("rung_set", C.c_void_p), ("n_rungs", C.c_uint32), ("n_sets", C.c_uint32)]
+
+
 class CarryCensusJob(C.Structure):
     """mg_carry_census_job (include/mythgpu.h): one job of mg_carry_census."""
     _fields_ = [("ladder", CarryLadderJob), ("n_roots", C.c_uint32), ("mask_probe0", C.c_uint32)]
@@ -147,6 +154,9 @@ CARRY_JOB_REGIONS = 4
 CARRY_MAX_WALKERS = 64
 CARRY_CENSUS_SHARED = 1
 CARRY_CENSUS_JOB_REGIONS = 2
+CARRY_MAX_SETS = 8
+CARRY_SETS_SHARED = 1
+CARRY_SETS_JOB_REGIONS = 1
 CENSUS_BATCH_MAX_JOBS = 256
 CENSUS_BATCH_SHARED = 2
 CENSUS_BATCH_JOB_REGIONS = 2
@@ -251,6 +261,12 @@ def load_library(path: str = _LIB_PATH, check_digest: bool = True):
         lib.mg_carry_census_plan_host.argtypes = [p, p, p, p, p, u32, u32, u32, u32, p,
                                                   C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
         lib.mg_carry_starts_host.argtypes = [p, u32, u32, u32, p, p]
+        lib.mg_carry_ladder_sets.argtypes = [p, C.POINTER(CarrySetsJob), u32, C.POINTER(Gen), u32,
+                                             p, p, p, u32, p]
+        lib.mg_carry_fill_sets_host.argtypes = [p, u32, p, u32, u64, p, p, p, u32, u32, u64, u64,
+                                                u32, u32, u32, u32, p]
+        lib.mg_carry_sets_plan_host.argtypes = [p, p, p, u32, u32, u32, p, C.POINTER(u64),
+                                                C.POINTER(u64)]
         lib.mg_batch_create.argtypes = [p, C.POINTER(p), u32, C.POINTER(p)]
         lib.mg_batch_free.argtypes = [p]
         lib.mg_batch_free.restype = None
@@ -591,6 +607,64 @@ class Engine:
             rc = self.lib.mg_carry_ladder(self._ctx, arr, n, C.byref(g), lanes, _ptr(first),
                                           _ptr(rung), _ptr(wit), max_leaves, _ptr(fill))
             self._check(rc, "mg_carry_ladder")
+            for i, k in enumerate(counts):
+                f = int(first[i])
+                res = (f, int(rung[i]), wit[i, :k].copy() if f >= 0 else None)
+                if want_fill:
+                    res += (fill[i, :k * 8 * cols].reshape(k, 8, cols).copy(),)
+                out.append(res)
+        return out
+
+    def carry_ladder_sets(self, jobs, seed: int, first_index: int, lanes: int,
+                          want_fill: bool = False):
+        """:meth:`carry_ladder` with several sets of pin rows per job, every
+        rung pinning from a set of its own (mg_carry_ladder_sets, DESIGN.md
+        §3.21).  ``jobs``: a list of ``(lp, pin_rows, pin_masks, rung_set)`` —
+        rows ``(n_sets, n_leaves, 8)`` uint32 with 1 to ``CARRY_MAX_SETS`` sets,
+        masks as :meth:`carry_ladder` takes them and ``rung_set`` ``(n_rungs,)``
+        uint32, the row set of every rung, each below ``n_sets``
+        (``carry.rungs_sets`` builds the three).  Columns, results,
+        ``want_fill`` and the split above ``CARRY_MAX_JOBS`` jobs are
+        :meth:`carry_ladder`'s; with one set the results are too."""
+        jobs = [(lp, np.ascontiguousarray(r, dtype=np.uint32),
+                 np.ascontiguousarray(m, dtype=np.uint32),
+                 np.ascontiguousarray(s, dtype=np.uint32)) for lp, r, m, s in jobs]
+        for lp, r, m, s in jobs:
+            n = len(lp.program.leaves)
+            if r.ndim != 3 or r.shape[1:] != (n, 8) or not 1 <= r.shape[0] <= CARRY_MAX_SETS:
+                raise ValueError("pin rows must be (n_sets, n_leaves, 8) with 1 to %d sets"
+                                 % CARRY_MAX_SETS)
+            if m.ndim != 2 or m.shape[1] != (n + 31) // 32 or \
+                    not 1 <= m.shape[0] <= CARRY_MAX_RUNGS:
+                raise ValueError("the pin masks must be (n_rungs, (n_leaves + 31) // 32) with 1 "
+                                 "to %d rungs" % CARRY_MAX_RUNGS)
+            if s.shape != (m.shape[0],) or (s >= r.shape[0]).any():
+                raise ValueError("rung_set must name one of the job's %d row sets for each of "
+                                 "its %d rungs" % (r.shape[0], m.shape[0]))
+        g = Gen(seed & (2**64 - 1), first_index)
+        out = []
+        for lo in range(0, len(jobs), CARRY_MAX_JOBS):
+            part = jobs[lo:lo + CARRY_MAX_JOBS]
+            n = len(part)
+            arr = (CarrySetsJob * n)()
+            for i, (lp, r, m, s) in enumerate(part):
+                arr[i].prog, arr[i].pin_rows, arr[i].pin_masks = lp.handle, _ptr(r), _ptr(m)
+                arr[i].rung_set, arr[i].n_rungs, arr[i].n_sets = _ptr(s), m.shape[0], r.shape[0]
+            counts = [len(lp.program.leaves) for lp, _, _, _ in part]
+            cols = max(m.shape[0] for _, _, m, _ in part) * lanes
+            max_leaves = max(1, max(counts))
+            first = np.full(n, -1, dtype=np.int64)
+            rung = np.full(n, -1, dtype=np.int64)
+            wit = np.zeros((n, max_leaves, 8), dtype=np.uint32)
+            fill = None
+            if want_fill:
+                _, _, stride = carry_sets_plan_host(counts, [m.shape[0] for _, _, m, _ in part],
+                                                    [r.shape[0] for _, r, _, _ in part], lanes,
+                                                    max_leaves)
+                fill = np.zeros((n, max(1, stride)), dtype=np.uint32)
+            rc = self.lib.mg_carry_ladder_sets(self._ctx, arr, n, C.byref(g), lanes, _ptr(first),
+                                               _ptr(rung), _ptr(wit), max_leaves, _ptr(fill))
+            self._check(rc, "mg_carry_ladder_sets")
             for i, k in enumerate(counts):
                 f = int(first[i])
                 res = (f, int(rung[i]), wit[i, :k].copy() if f >= 0 else None)
@@ -1448,6 +1522,60 @@ def carry_fill_rungs_host(leafgen: Sequence[LeafGen], consts: np.ndarray, prog_s
                                       col0, max(0, n_cols), _ptr(out))
     if rc != 0:
         raise EngineError("mg_carry_fill_rungs_host refused its arguments (%d)" % rc)
+    return out
+
+
+def carry_sets_plan_host(n_leaves: Sequence[int], n_rungs: Sequence[int], n_sets: Sequence[int],
+                         lanes: int, max_leaves: int):
+    """Host-only: the plan of mg_carry_ladder_sets's device buffer
+    (mg_carry_sets_plan_host): ``(offsets, bytes, leaf_stride_w)``.
+    ``offsets``: :func:`carry_ladder_plan_host`'s table — a job's rows region
+    holding its ``n_sets`` row sets — followed by the set records' offset and
+    per job its rung_set's.  :class:`EngineError` where the library refuses."""
+    lib = load_library(check_digest=False)
+    arrs = [np.ascontiguousarray(a, dtype=np.uint32) for a in (n_leaves, n_rungs, n_sets)]
+    n = arrs[0].shape[0]
+    if any(a.shape[0] != n for a in arrs):
+        raise ValueError("one count of each kind per job")
+    size = CARRY_SHARED + CARRY_SETS_SHARED + n * (CARRY_JOB_REGIONS + CARRY_SETS_JOB_REGIONS)
+    offs = np.zeros(size + CARRY_JOB_REGIONS + CARRY_SETS_JOB_REGIONS, dtype=np.uint64)
+    total, stride = C.c_uint64(0), C.c_uint64(0)
+    rc = lib.mg_carry_sets_plan_host(*[_ptr(a) for a in arrs], n, lanes, max_leaves, _ptr(offs),
+                                     C.byref(total), C.byref(stride))
+    if rc != 0:
+        raise EngineError("carry_sets: %d jobs at %d lanes: counts out of range, too many "
+                          "columns or a buffer beyond 64 bits" % (n, lanes))
+    return offs[:size], int(total.value), int(stride.value)
+
+
+def carry_fill_sets_host(leafgen: Sequence[LeafGen], consts: np.ndarray, prog_seed: int,
+                         pin_rows: np.ndarray, pin_masks: np.ndarray, rung_set: np.ndarray,
+                         seed: int, first_index: int, lanes: int, cols: Optional[int] = None,
+                         col0: int = 0, n_cols: Optional[int] = None):
+    """Host-only: :func:`carry_fill_rungs_host` for one mg_carry_ladder_sets
+    job (mg_carry_fill_sets_host, the set fill kernel's own lane function):
+    ``pin_rows`` ``(n_sets, n_leaves, 8)``, ``rung_set`` ``(n_rungs,)``."""
+    lib = load_library(check_digest=False)
+    gens = list(leafgen)
+    n = len(gens)
+    garr = (LeafGen * max(1, n))(*gens)
+    consts = np.ascontiguousarray(consts, dtype=np.uint32).reshape(-1, 8)
+    rows = np.ascontiguousarray(pin_rows, dtype=np.uint32)
+    masks = np.ascontiguousarray(pin_masks, dtype=np.uint32)
+    sets = np.ascontiguousarray(rung_set, dtype=np.uint32)
+    if rows.ndim != 3 or rows.shape[1:] != (n, 8) or masks.ndim != 2 or \
+            masks.shape[1] != (n + 31) // 32 or sets.shape != (masks.shape[0],):
+        raise ValueError("pin rows must be (n_sets, n_leaves, 8), the pin masks (n_rungs, "
+                         "(n_leaves + 31) // 32) and rung_set (n_rungs,)")
+    cols = masks.shape[0] * lanes if cols is None else cols
+    n_cols = cols - col0 if n_cols is None else n_cols
+    out = np.zeros((n, 8, max(0, n_cols)), dtype=np.uint32)
+    rc = lib.mg_carry_fill_sets_host(C.cast(garr, C.c_void_p), n, _ptr(consts), consts.shape[0],
+                                     prog_seed & (2**64 - 1), _ptr(rows), _ptr(masks), _ptr(sets),
+                                     masks.shape[0], rows.shape[0], seed & (2**64 - 1),
+                                     first_index, lanes, cols, col0, max(0, n_cols), _ptr(out))
+    if rc != 0:
+        raise EngineError("mg_carry_fill_sets_host refused its arguments (%d)" % rc)
     return out
 
 

@@ -128,6 +128,8 @@ class SolverStatistics:
         self.launches = 0               # kernel launches of those calls (_count_kernel)
         self.carry_gated = 0            # extensions not carried: a carried table above the cap
         self.carry_rung_hits = [0, 0, 0]  # the ladder's hits per rung (carry.RUNG_NAMES)
+        from . import carry
+        self.carry_set_hits = [0] * carry.MAX_SETS  # ... and per pin set (knob 4)
         self.carry_walk_attempts = 0    # groups that missed every rung and walked (knob 3)
         self.carry_walk_hits = 0        # ... to a model
         self.phase = {k: 0.0 for k in PHASES}
@@ -138,11 +140,13 @@ class SolverStatistics:
                 self.repair_attempts, self.repair_hits,
                 " batches: {}".format(self.repair_batches) if self.repair_batches else "")
             if self.repair_attempts or self.repair_hits else "") + (
-            "\nGPU carry: exact: {} attempts: {} hits: {} candidates: {}{}{}{}".format(
+            "\nGPU carry: exact: {} attempts: {} hits: {} candidates: {}{}{}{}{}".format(
                 self.carry_exact, self.carry_attempts, self.carry_hits, self.carry_candidates,
                 " table-gated: {}".format(self.carry_gated) if self.carry_gated else "",
                 " rung hits: {}".format("/".join(map(str, self.carry_rung_hits)))
                 if any(self.carry_rung_hits) else "",
+                " set hits: {}".format("/".join(map(str, self.carry_set_hits)))
+                if any(self.carry_set_hits[1:]) else "",
                 " walks: {} walk hits: {}".format(self.carry_walk_attempts, self.carry_walk_hits)
                 if self.carry_walk_attempts or self.carry_walk_hits else "")
             if self.carry_exact or self.carry_attempts or self.carry_gated else "")
@@ -254,6 +258,8 @@ REPAIR_BATCH = False
 # MYTHRIL_GPU_CARRY=3 ("walk"): as 2, and the groups that miss on every rung
 # walk from the ladder's best columns (repair.repair_carried)
 # with CARRY_WALKERS start columns for at most CARRY_ROUNDS rounds
+# MYTHRIL_GPU_CARRY=4 ("sets"): as 2, with up to carry.MAX_SETS pin sets per
+# group, every rung pinning from its own set's rows (carry.run_sets, §3.21)
 CARRY = False
 CARRY_WALKERS = 4              # MYTHRIL_GPU_CARRY_WALKERS
 CARRY_ROUNDS = 16              # MYTHRIL_GPU_CARRY_ROUNDS
@@ -286,6 +292,8 @@ def configure_from_env(env=None) -> None:
     ``MYTHRIL_GPU_CARRY=3`` also walks from the ladder's best columns when
     every rung misses (``MYTHRIL_GPU_CARRY_WALKERS`` start columns, default 4,
     at most ``MYTHRIL_GPU_CARRY_ROUNDS`` rounds, default 16),
+    ``MYTHRIL_GPU_CARRY=4`` runs the ladder of 2 with up to
+    ``MYTHRIL_GPU_CARRY_SETS`` (default 4, 1..8) remembered witnesses per group,
     ``MYTHRIL_GPU_CARRY_LANES`` the candidates of such an evaluation when the
     extension has fresh symbols, ``MYTHRIL_GPU_CARRY_MAX_ENTRIES`` the largest
     carried table an extension is evaluated with."""
@@ -312,12 +320,16 @@ def configure_from_env(env=None) -> None:
         "1", "on", "true", "yes")
     REPAIR_BATCH = env.get("MYTHRIL_GPU_REPAIR_BATCH", "0").strip().lower() in (
         "1", "on", "true", "yes")
-    CARRY = {"2": "ladder", "3": "walk"}.get(env.get("MYTHRIL_GPU_CARRY", "0").strip()) or \
+    CARRY = {"2": "ladder", "3": "walk", "4": "sets"}.get(
+        env.get("MYTHRIL_GPU_CARRY", "0").strip()) or \
         env.get("MYTHRIL_GPU_CARRY", "0").strip().lower() in ("1", "on", "true", "yes")
     if env.get("MYTHRIL_GPU_CARRY_WALKERS"):
         CARRY_WALKERS = min(64, max(1, int(env["MYTHRIL_GPU_CARRY_WALKERS"])))
     if env.get("MYTHRIL_GPU_CARRY_ROUNDS"):
         CARRY_ROUNDS = min(1 << 16, max(1, int(env["MYTHRIL_GPU_CARRY_ROUNDS"])))
+    if env.get("MYTHRIL_GPU_CARRY_SETS"):
+        from . import carry
+        carry.MAX_SETS = min(carry.SETS_LIMIT, max(1, int(env["MYTHRIL_GPU_CARRY_SETS"])))
     if env.get("MYTHRIL_GPU_CARRY_LANES"):
         from . import carry
         carry.CARRY_LANES = min(1 << 20, max(1, int(env["MYTHRIL_GPU_CARRY_LANES"])))
@@ -767,16 +779,19 @@ def _carry_groups(groups, eng=None):
     into ONE ``Engine.carry_batch`` call on the first device, deduplicated by
     key (with ``CARRY == "ladder"``: one ``Engine.carry_ladder`` call, every
     group with its rungs; with ``CARRY == "walk"`` the groups that miss on
-    every rung then go into one ``repair.repair_carried`` call).  A group
-    missing from the result goes on as before."""
+    every rung then go into one ``repair.repair_carried`` call; with ``CARRY
+    == "sets"``: one ``Engine.carry_ladder_sets`` call, every group with the
+    rungs of all its pin sets).  A group missing from the result goes on as
+    before."""
     from . import carry
     out, jobs = {}, {}
-    ladder = CARRY in ("ladder", "walk")
+    sets = CARRY == "sets"
+    ladder = CARRY in ("ladder", "walk", "sets")
     cache = _SEARCH_CACHE or {}
     for key, nodes in groups:
         if key in out or key in jobs or not key:
             continue
-        what = carry.plan(key, _hit_memo)
+        what = carry.plan_sets(key, _hit_memo) if sets else carry.plan(key, _hit_memo)
         if what is None:
             continue
         if what[0] == "exact":
@@ -785,7 +800,8 @@ def _carry_groups(groups, eng=None):
                 continue
             stats.carry_exact += 1
             out[key] = (what[1], prog)
-        elif max((carry.table_sizes_ck(nodes, what[1]) if ladder else
+        elif max((carry.sizes_sets(nodes, what[1]) if sets else
+                  carry.table_sizes_ck(nodes, what[1]) if ladder else
                   carry.table_sizes(what[1])).values(), default=0) > carry.MAX_ENTRIES:
             # the eval form reads a table entry by entry: a carried table of
             # this size makes the compile dearer than the search it may save
@@ -793,11 +809,11 @@ def _carry_groups(groups, eng=None):
             # only the others count)
             stats.carry_gated += 1
         else:
-            jobs[key] = (nodes, what[1], what[2]) if ladder else (nodes, what[1])
+            jobs[key] = (nodes, what[1], what[2]) if ladder and not sets else (nodes, what[1])
     if jobs:
         eng = eng or get_engine((list(DEVICES) or [0])[0])
-        res = (carry.run_ladder if ladder else carry.run)(eng, list(jobs.values()), SEARCH_SEED,
-                                                          search_leafgen, phase=_Phase)
+        run = carry.run_sets if sets else carry.run_ladder if ladder else carry.run
+        res = run(eng, list(jobs.values()), SEARCH_SEED, search_leafgen, phase=_Phase)
         ran = [r for r in res if r is not None]
         if ran:
             # fill (when any job has a leaf), interpreter, gather
@@ -812,6 +828,9 @@ def _carry_groups(groups, eng=None):
                 stats.carry_hits += 1
                 if ladder:
                     stats.carry_rung_hits[r[3]] += 1
+                if sets:                   # (MAX_SETS may have grown since the last reset)
+                    stats.carry_set_hits += [0] * (r[4] + 1 - len(stats.carry_set_hits))
+                    stats.carry_set_hits[r[4]] += 1
                 _note_hit(key, asg, prog)
                 out[key] = (asg, prog)
         missed = [key for key, r in zip(jobs, res) if r is not None and r[0] is None]

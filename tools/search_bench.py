@@ -146,6 +146,8 @@ def shape_lines(eng, n_queries, n_sample=48):
                               "table_gated": M.stats.carry_gated,
                               # MYTHRIL_GPU_CARRY=2 (§3.19): hits per rung
                               "rung_hits": list(M.stats.carry_rung_hits),
+                              # MYTHRIL_GPU_CARRY=4 (§3.21): hits per pin set
+                              "set_hits": list(M.stats.carry_set_hits),
                               # MYTHRIL_GPU_CARRY=3 (§3.20): walks from a carried start
                               "walk_attempts": M.stats.carry_walk_attempts,
                               "walk_hits": M.stats.carry_walk_hits},
