@@ -28,6 +28,13 @@ with one taken before them become further pin sets (:func:`plan_sets`), every
 rung of every set is a block of columns of the one compiled group
 (:func:`rungs_sets`), and ``Engine.carry_ladder_sets`` evaluates them in the
 ladder's three launches (:func:`run_sets`).
+
+``MYTHRIL_GPU_CARRY=5`` is the delta carry: only the
+constraints an extension ADDS are compiled and evaluated
+(:func:`delta_job`), on the two rungs that move no leaf the remembered
+constraints read, so their roots hold as they did; a hit's column is written
+into the remembered witness (:func:`merge_delta`), and
+``Engine.carry_ladder`` runs every such job of a call (:func:`run_delta`).
 """
 
 from __future__ import annotations
@@ -37,7 +44,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from .assign import Assignment, leaf_values, unpack
+from .assign import Assignment, leaf_values, lookup, unpack
 from .ir import Program, compile_constraints, scan_const_keys
 
 # candidates of a job with at least one free leaf (MYTHRIL_GPU_CARRY_LANES);
@@ -172,6 +179,7 @@ _EVAL_CACHE: "OrderedDict[tuple, Program]" = OrderedDict()
 
 def clear() -> None:
     _EVAL_CACHE.clear()
+    _PARENT_CACHE.clear()
 
 
 def compile_eval(nodes, asg: Assignment) -> Program:
@@ -384,6 +392,175 @@ def run_ladder(eng, items, seed: int, leafgen, lanes: Optional[int] = None, phas
         for k, prog, f, keep, (first, rung, leaves) in zip(where, progs, free, kept, res):
             out[k] = (unpack(prog, leaves) if first >= 0 else None, prog,
                       sum(width if x else 1 for x in f), keep[rung] if first >= 0 else -1)
+    return out
+
+
+# ---------------------------------------------------------------------------
+# The delta carry (MYTHRIL_GPU_CARRY=5): only the constraints
+# an extension adds are compiled and evaluated, on the rungs that keep every
+# leaf the parent reads
+# ---------------------------------------------------------------------------
+
+DELTA_RUNG_NAMES = ("all", "read")
+_PARENT_CACHE: "OrderedDict[frozenset, tuple]" = OrderedDict()
+
+
+def _parent_reads(parent_nodes, taken_keys):
+    """``(symbol names, numeral keys read per table, symbolic reads per
+    table)`` of a delta job's parent, cached by the subset keys taken: the
+    children of one JUMPI, and the extensions after them, share their parent,
+    and node ids are never reused."""
+    key = frozenset(taken_keys)
+    got = _PARENT_CACHE.get(key)
+    if got is not None:
+        _PARENT_CACHE.move_to_end(key)
+        return got
+    sym: Dict[str, int] = {}
+    read = scan_const_keys(parent_nodes, sym_counts=sym)
+    got = _PARENT_CACHE[key] = (_symbol_names(parent_nodes), read, sym)
+    if len(_PARENT_CACHE) > EVAL_CACHE_SIZE:
+        _PARENT_CACHE.popitem(last=False)
+    return got
+
+
+def delta_job(nodes, asg: Assignment, taken_keys):
+    """``(program, rows, ladder)`` of one delta job: the constant-keyed eval
+    form of the NEW nodes of the group alone (:func:`split_nodes`), sized by
+    ``table_sizes_ck(new_nodes, asg)``; ``rows`` as :func:`pins` gives them;
+    ``ladder`` ((2, words) uint32), the masks of ``DELTA_RUNG_NAMES``,
+    strictest first:
+
+    * "all": the rule of :func:`pins`.
+    * "read" (read-strict): as "all", but a ``cval`` leaf is free when the
+      parent reads its table at NO symbolic key (``scan_const_keys``'
+      ``sym_counts``) and the leaf's key is not among the numeral keys the
+      parent read.  :func:`rung_masks` frees such a leaf as soon as the scan
+      lists the table, because the ladder evaluates the parent's roots again;
+      the delta does not, so a symbolic read — which may have met any entry —
+      keeps every entry.  Where the scan's key list is full (``CKEY_CAP``) it
+      may have dropped a key the parent read: the table frees nothing.
+
+    The parent's roots are not evaluated: they held under ``asg``, and neither
+    rung moves a leaf they read.  That needs ``asg`` to speak for every symbol
+    the two sides share, so ``ValueError`` is raised (with the reason) when a
+    leaf of the program has a source the parent's nodes mention and ``asg``
+    does not interpret — the delta would choose it freely and the parent's
+    roots might not hold — and when the group has no new node."""
+    from .ir import CKEY_CAP
+    parent_nodes, new_nodes = split_nodes(nodes, taken_keys)
+    if not new_nodes or not parent_nodes:
+        raise ValueError("no delta: %d new and %d remembered constraints" % (
+            len(new_nodes), len(parent_nodes)))
+    program = compile_eval_ck(new_nodes, asg, table_sizes_ck(new_nodes, asg))
+    shared, read, sym = _parent_reads(parent_nodes, taken_keys)
+    for leaf in program.leaves:
+        if leaf.kind != "aux" and leaf.source in shared and not pinned(leaf, asg):
+            raise ValueError("the witness is silent about %s, which the remembered "
+                             "constraints read" % leaf.source)
+    mask, rows = pins(program, asg)
+    ladder = np.stack([mask, mask.copy()])
+    for l, leaf in enumerate(program.leaves):
+        if leaf.kind != "cval" or not pinned(leaf, asg) or sym.get(leaf.source):
+            continue
+        keys = read.get(leaf.source, ())
+        if len(keys) >= CKEY_CAP:
+            continue
+        if program.table_ckeys[leaf.source][leaf.entry] not in keys:
+            ladder[1, l >> 5] &= ~np.uint32(1 << (l & 31))
+    return program, rows, ladder
+
+
+def _freed_keys(program: Program, asg: Assignment, mask: np.ndarray) -> Dict[str, List[int]]:
+    """Per table ``asg`` interprets, the keys of the ``cval`` leaves of
+    ``program`` that ``mask`` leaves free."""
+    out: Dict[str, List[int]] = {}
+    for l, leaf in enumerate(program.leaves):
+        if leaf.kind == "cval" and pinned(leaf, asg) and not int(mask[l >> 5]) >> (l & 31) & 1:
+            key = program.table_ckeys[leaf.source][leaf.entry]
+            if key not in out.setdefault(leaf.source, []):
+                out[leaf.source].append(key)
+    return out
+
+
+def merge_delta(asg: Assignment, program: Program, leaves: np.ndarray,
+                mask: np.ndarray) -> Assignment:
+    """The assignment of the whole group after a delta hit: a copy of ``asg``,
+    with every var, array and function of ``unpack(program, leaves)`` that
+    ``asg`` does not interpret, and — for the tables it does — exactly the
+    entries at the keys of ``cval`` leaves that were free under ``mask``
+    (:func:`delta_job`'s rung that hit): such an entry is written, in place of
+    the don't-care entry the table held at that key if it held one.  Nothing
+    else of a carried table changes (``model._merge`` replaces whole tables:
+    the entries the parent's roots read would be lost)."""
+    got = unpack(program, leaves)
+    out = Assignment(asg.vars, asg.arrays, asg.funcs)
+    for name, v in got.vars.items():
+        out.vars.setdefault(name, v)
+    for mine, theirs in ((out.arrays, got.arrays), (out.funcs, got.funcs)):
+        for name, tab in theirs.items():
+            if name not in out.arrays and name not in out.funcs:
+                mine[name] = tab
+    for name, keys in _freed_keys(program, asg, mask).items():
+        mine = out.arrays if name in out.arrays else out.funcs
+        entries, default = mine[name]
+        new = got.table(name)
+        mine[name] = ([(k, lookup(new, k)) for k in keys] +
+                      [e for e in entries if e[0] not in keys], default)
+    return out
+
+
+def run_delta(eng, items, seed: int, leafgen, lanes: Optional[int] = None, phase=None):
+    """:func:`run_ladder` on the delta: one ``Engine.carry_ladder`` call for the
+    eligible ``items`` (``(nodes, assignment, taken_keys)``), every job the
+    program of its new nodes alone (:func:`delta_job`).  Per item
+    ``(assignment, program, candidates, rung)`` — on a hit the MERGED
+    assignment of the whole group (:func:`merge_delta`) and the index in
+    ``DELTA_RUNG_NAMES`` of the rung that hit, on a miss None and -1 —,
+    ``("ineligible", reason)`` where :func:`delta_job` refuses, or None where
+    the new nodes have no eval form.  A delta program that folds to a constant
+    (``model._ground_value``) is answered without a launch, ``candidates`` 0:
+    true is a hit on "all" with the witness as it is, false a miss.  The width
+    rule and the column cap are :func:`run_ladder`'s."""
+    import contextlib
+    from .ir import Unsupported
+    from .model import _ground_value
+    phase = phase or (lambda name: contextlib.nullcontext())
+    lanes = CARRY_LANES if lanes is None else lanes
+    out: List = [None] * len(items)
+    jobs, progs, free, kept, where = [], [], [], [], []
+    with phase("compile"):
+        for k, (nodes, asg, taken) in enumerate(items):
+            try:
+                prog, rows, ladder = delta_job(nodes, asg, taken)
+            except Unsupported:
+                continue
+            except ValueError as e:
+                out[k] = ("ineligible", str(e))
+                continue
+            ground = _ground_value(prog)
+            if ground is not None:
+                out[k] = (Assignment(asg.vars, asg.arrays, asg.funcs) if ground else None, prog,
+                          0, 0 if ground else -1)
+                continue
+            keep = distinct(ladder)
+            progs.append(prog)
+            kept.append(keep)
+            free.append([n_free(prog, ladder[r]) for r in keep])
+            jobs.append((prog, rows, ladder[keep]))
+            where.append(k)
+    if not jobs:
+        return out
+    width = max(1, int(lanes)) if any(any(f) for f in free) else 1
+    width = min(width, (1 << 20) // max(len(keep) for keep in kept))   # the call's column cap
+    with phase("load"):
+        loaded = [(eng.load(p, leafgen(p), prog_seed=0), r, m) for p, r, m in jobs]
+    with phase("search"):
+        res = eng.carry_ladder(loaded, seed, 0, width)
+        for k, (prog, _, masks), f, keep, (first, rung, leaves) in zip(where, jobs, free, kept,
+                                                                       res):
+            hit = first >= 0
+            out[k] = (merge_delta(items[k][1], prog, leaves, masks[rung]) if hit else None, prog,
+                      sum(width if x else 1 for x in f), keep[rung] if hit else -1)
     return out
 
 

@@ -132,6 +132,11 @@ class SolverStatistics:
         self.carry_set_hits = [0] * carry.MAX_SETS  # ... and per pin set (knob 4)
         self.carry_walk_attempts = 0    # groups that missed every rung and walked (knob 3)
         self.carry_walk_hits = 0        # ... to a model
+        self.carry_delta_attempts = 0   # extensions evaluated on their new constraints (knob 5)
+        self.carry_delta_hits = [0, 0]  # ... that hit, per rung (carry.DELTA_RUNG_NAMES)
+        self.carry_delta_ineligible = 0  # ... refused by carry.delta_job: the ladder ran
+        self.carry_delta_roots = 0      # roots those evaluations compiled
+        self.carry_delta_group_roots = 0  # ... of this many roots in their groups
         self.phase = {k: 0.0 for k in PHASES}
 
     def gpu_report(self) -> str:
@@ -140,7 +145,7 @@ class SolverStatistics:
                 self.repair_attempts, self.repair_hits,
                 " batches: {}".format(self.repair_batches) if self.repair_batches else "")
             if self.repair_attempts or self.repair_hits else "") + (
-            "\nGPU carry: exact: {} attempts: {} hits: {} candidates: {}{}{}{}{}".format(
+            "\nGPU carry: exact: {} attempts: {} hits: {} candidates: {}{}{}{}{}{}".format(
                 self.carry_exact, self.carry_attempts, self.carry_hits, self.carry_candidates,
                 " table-gated: {}".format(self.carry_gated) if self.carry_gated else "",
                 " rung hits: {}".format("/".join(map(str, self.carry_rung_hits)))
@@ -148,7 +153,12 @@ class SolverStatistics:
                 " set hits: {}".format("/".join(map(str, self.carry_set_hits)))
                 if any(self.carry_set_hits[1:]) else "",
                 " walks: {} walk hits: {}".format(self.carry_walk_attempts, self.carry_walk_hits)
-                if self.carry_walk_attempts or self.carry_walk_hits else "")
+                if self.carry_walk_attempts or self.carry_walk_hits else "",
+                " delta attempts: {} delta hits: {} ineligible: {} roots: {} of {}".format(
+                    self.carry_delta_attempts, "/".join(map(str, self.carry_delta_hits)),
+                    self.carry_delta_ineligible, self.carry_delta_roots,
+                    self.carry_delta_group_roots)
+                if self.carry_delta_attempts or self.carry_delta_ineligible else "")
             if self.carry_exact or self.carry_attempts or self.carry_gated else "")
 
     def _gpu_report(self) -> str:
@@ -260,6 +270,10 @@ REPAIR_BATCH = False
 # with CARRY_WALKERS start columns for at most CARRY_ROUNDS rounds
 # MYTHRIL_GPU_CARRY=4 ("sets"): as 2, with up to carry.MAX_SETS pin sets per
 # group, every rung pinning from its own set's rows (carry.run_sets, §3.21)
+# MYTHRIL_GPU_CARRY=5 ("delta"): only the constraints an extension adds are
+# compiled and evaluated, on the rungs that move no leaf the remembered
+# constraints read (carry.run_delta, §3.22); an extension the delta cannot take
+# runs the ladder of 2, one it misses is searched
 CARRY = False
 CARRY_WALKERS = 4              # MYTHRIL_GPU_CARRY_WALKERS
 CARRY_ROUNDS = 16              # MYTHRIL_GPU_CARRY_ROUNDS
@@ -294,6 +308,9 @@ def configure_from_env(env=None) -> None:
     at most ``MYTHRIL_GPU_CARRY_ROUNDS`` rounds, default 16),
     ``MYTHRIL_GPU_CARRY=4`` runs the ladder of 2 with up to
     ``MYTHRIL_GPU_CARRY_SETS`` (default 4, 1..8) remembered witnesses per group,
+    ``MYTHRIL_GPU_CARRY=5`` compiles and evaluates only the constraints an
+    extension adds, under the remembered witness (the ladder of 2 where that
+    witness does not cover what both sides read),
     ``MYTHRIL_GPU_CARRY_LANES`` the candidates of such an evaluation when the
     extension has fresh symbols, ``MYTHRIL_GPU_CARRY_MAX_ENTRIES`` the largest
     carried table an extension is evaluated with."""
@@ -320,7 +337,7 @@ def configure_from_env(env=None) -> None:
         "1", "on", "true", "yes")
     REPAIR_BATCH = env.get("MYTHRIL_GPU_REPAIR_BATCH", "0").strip().lower() in (
         "1", "on", "true", "yes")
-    CARRY = {"2": "ladder", "3": "walk", "4": "sets"}.get(
+    CARRY = {"2": "ladder", "3": "walk", "4": "sets", "5": "delta"}.get(
         env.get("MYTHRIL_GPU_CARRY", "0").strip()) or \
         env.get("MYTHRIL_GPU_CARRY", "0").strip().lower() in ("1", "on", "true", "yes")
     if env.get("MYTHRIL_GPU_CARRY_WALKERS"):
@@ -781,12 +798,15 @@ def _carry_groups(groups, eng=None):
     group with its rungs; with ``CARRY == "walk"`` the groups that miss on
     every rung then go into one ``repair.repair_carried`` call; with ``CARRY
     == "sets"``: one ``Engine.carry_ladder_sets`` call, every group with the
-    rungs of all its pin sets).  A group missing from the result goes on as
-    before."""
+    rungs of all its pin sets; with ``CARRY == "delta"``: one
+    ``Engine.carry_ladder`` call of the groups' NEW constraints alone,
+    ``carry.run_delta``, then one ``carry.run_ladder`` call for the groups the
+    delta refused).  A group missing from the result goes on as before."""
     from . import carry
     out, jobs = {}, {}
     sets = CARRY == "sets"
-    ladder = CARRY in ("ladder", "walk", "sets")
+    delta = CARRY == "delta"
+    ladder = CARRY in ("ladder", "walk", "sets", "delta")
     cache = _SEARCH_CACHE or {}
     for key, nodes in groups:
         if key in out or key in jobs or not key:
@@ -801,7 +821,8 @@ def _carry_groups(groups, eng=None):
             stats.carry_exact += 1
             out[key] = (what[1], prog)
         elif max((carry.sizes_sets(nodes, what[1]) if sets else
-                  carry.table_sizes_ck(nodes, what[1]) if ladder else
+                  carry.table_sizes_ck(carry.split_nodes(nodes, what[2])[1], what[1]) if delta
+                  else carry.table_sizes_ck(nodes, what[1]) if ladder else
                   carry.table_sizes(what[1])).values(), default=0) > carry.MAX_ENTRIES:
             # the eval form reads a table entry by entry: a carried table of
             # this size makes the compile dearer than the search it may save
@@ -810,6 +831,9 @@ def _carry_groups(groups, eng=None):
             stats.carry_gated += 1
         else:
             jobs[key] = (nodes, what[1], what[2]) if ladder and not sets else (nodes, what[1])
+    if jobs and delta:
+        eng = eng or get_engine((list(DEVICES) or [0])[0])
+        jobs = _carry_delta(eng, jobs, out)
     if jobs:
         eng = eng or get_engine((list(DEVICES) or [0])[0])
         run = carry.run_sets if sets else carry.run_ladder if ladder else carry.run
@@ -852,6 +876,43 @@ def _carry_groups(groups, eng=None):
                     _note_hit(key, g["assignment"], g["program"])
                     out[key] = (g["assignment"], g["program"])
     return out
+
+
+def _carry_delta(eng, jobs, out):
+    """The delta carry of ``jobs`` (key -> (nodes, assignment, taken keys)),
+    one ``carry.run_delta`` call: hits go into ``out`` and the hit memo, with
+    the delta program (``Model`` takes table sizes from it, no more); a miss is
+    left to the search, as a miss of the ladder is.  Returns the jobs the delta
+    refused and the ladder's table gate lets through: they run the ladder."""
+    from . import carry
+    res = carry.run_delta(eng, list(jobs.values()), SEARCH_SEED, search_leafgen, phase=_Phase)
+    ran = [r for r in res if r is not None and r[0] != "ineligible" and r[2]]
+    if ran:
+        _count_kernel(eng, 3 if any(len(r[1].leaves) for r in ran) else 2)
+    rest = {}
+    for (key, job), r in zip(jobs.items(), res):
+        if r is None:                      # no eval form of the new constraints
+            continue
+        if r[0] == "ineligible":
+            stats.carry_delta_ineligible += 1
+            if max(carry.table_sizes_ck(job[0], job[1]).values(),
+                   default=0) > carry.MAX_ENTRIES:
+                stats.carry_gated += 1
+            else:
+                rest[key] = job
+            continue
+        asg, prog, n, rung = r
+        stats.carry_attempts += 1
+        stats.carry_delta_attempts += 1
+        stats.carry_candidates += n
+        stats.carry_delta_roots += len(carry.split_nodes(job[0], job[2])[1])
+        stats.carry_delta_group_roots += len(job[0])
+        if asg is not None:
+            stats.carry_hits += 1
+            stats.carry_delta_hits[rung] += 1
+            _note_hit(key, asg, prog)
+            out[key] = (asg, prog)
+    return rest
 
 
 def _group_key(nodes: Sequence[N.Node]) -> frozenset:
