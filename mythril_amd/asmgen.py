@@ -2296,6 +2296,15 @@ def udivrem(a: Asm, want_rem: bool, z: int):
     _udivrem_short2(a, want_rem, z)
     a("s_branch %s" % lab_done)
     a.hot()
+    # every active lane's divisor keeps its top limb (35 % of the C2 corpus's
+    # division waves): one quotient digit, divided without normalising
+    lab_gen = a.uniq("dgn")
+    a("v_cmp_ne_u32 vcc, 0, %s" % v(Y[7]))
+    a("s_cmp_eq_u64 vcc, exec")
+    a("s_cbranch_scc0 %s" % lab_gen)
+    _udivrem_full(a, want_rem, z)
+    a("s_branch %s" % lab_done)
+    a.label(lab_gen)
     for j in range(0, 8, 2):
         a("v_mov_b64 %s, 0" % vp(R[j]))
     a("v_mov_b32 %s, 0" % v(T[0]))                                       # un[16]
@@ -2377,6 +2386,92 @@ def udivrem(a: Asm, want_rem: bool, z: int):
             _stage(a, t, st, 9, False, DIV_M[st])
         bitshift_right(a, t, b, 8)
     a.label(lab_done)
+
+
+def _udivrem_full(a: Asm, want_rem: bool, z: int):
+    """udivrem when every active lane's divisor keeps its top limb (Y[7] != 0,
+    wave-uniform; no lane divides by zero: s[z:z+1] <- 0): only quotient
+    digit 0 can be nonzero, and one digit needs no normalised operands.  Its
+    estimate reads three words of them, which two 64-bit shifts by 32 -
+    clz(Y[7]) give (a 64-bit shift takes 32, the clz = 0 lanes, without a
+    lane mask): d = vn[7], u7 = un[7], u8 = un[8] of Knuth D, so the estimate
+    is at most two above the digit as there.  The multiply-subtract then runs
+    on X and Y themselves: X - qh * Y has the sign of un - qh * vn (the same
+    number times 2^clz), and what it leaves in X is the remainder, with no
+    shift back.  The quotient goes to R only without ``want_rem`` (every
+    caller that wants the remainder overwrites R).  Registers: (u7:u8) =
+    T0:T1, d = T2, pairs T4:T5, T6:T7, CR:RH = T8:T9, dinv = T10, QH = T11."""
+    u1, u2, d, c, dinv = T[0], T[1], T[2], T[3], T[10]
+    A0, A1, P0, P1, CR, RH, QH = T[4], T[5], T[6], T[7], T[8], T[9], T[11]
+    st = S_T
+    lab_q0, lab_ab, lab_x, lab_ret = a.uniq("df0"), a.uniq("dfa"), a.uniq("dfx"), a.uniq("dfr")
+    a("s_mov_b64 %s, 0" % sp(z))
+    a("v_ffbh_u32 %s, %s" % (v(c), v(Y[7])))
+    a("v_sub_u32 %s, 32, %s" % (v(c), v(c)))                           # 32 - clz: 1..32
+    a("v_lshrrev_b64 %s, %s, %s" % (vp(u1), v(c), vp(X[6])))           # u8:u7
+    a("v_lshrrev_b64 %s, %s, %s" % (vp(d), v(c), vp(Y[6])))            # low word: d >= 2^31
+    # digit 0 is zero in every lane (u8 = 0 and u7 < d): quotient 0, remainder X
+    a("v_cmp_ne_u32_e64 %s, 0, %s" % (sp(st), v(u2)))
+    a("v_cmp_ge_u32_e64 %s, %s, %s" % (sp(st + 2), v(u1), v(d)))
+    a("s_or_b64 vcc, %s, %s" % (sp(st), sp(st + 2)))
+    a("s_cbranch_vccz %s" % (lab_ret if want_rem else lab_q0))
+    _reciprocal(a, d, dinv)
+    # the 2-by-1 quotient of _div_digit; u8 < 2^clz <= d, so no lane takes
+    # its u2 == d case
+    a("v_mad_u64_u32 %s, %s, %s, %s, %s" % (vp(A0), sp(st + 6), v(dinv), v(u2), vp(u1)))
+    a("v_add_u32 %s, 1, %s" % (v(QH), v(A1)))                          # q1 (A0 = q0)
+    a("v_mul_lo_u32 %s, %s, %s" % (v(P0), v(QH), v(d)))
+    a("v_sub_u32 %s, %s, %s" % (v(CR), v(u1), v(P0)))                  # r = u1 - q1*d
+    a("v_cmp_gt_u32_e64 %s, %s, %s" % (sp(st + 2), v(CR), v(A0)))     # r > q0: q1--, r += d
+    a("v_subb_co_u32_e64 %s, %s, %s, 0, %s" % (v(QH), sp(st + 4), v(QH), sp(st + 2)))
+    a("v_cndmask_b32_e64 %s, 0, %s, %s" % (v(P0), v(d), sp(st + 2)))
+    a("v_add_u32 %s, %s, %s" % (v(CR), v(CR), v(P0)))
+    a("v_cmp_ge_u32_e64 %s, %s, %s" % (sp(st + 2), v(CR), v(d)))       # r >= d: q1++, r -= d
+    a("v_addc_co_u32_e64 %s, %s, %s, 0, %s" % (v(QH), sp(st + 4), v(QH), sp(st + 2)))
+    # X -= qh * Y as one borrow chain in vcc (carry pair CR:RH with RH = 0);
+    # the ninth word 0 - carry - borrow goes to A0: nonzero where qh was too big
+    a("v_mov_b32 %s, 0" % v(RH))
+    for i in range(8):
+        a("v_mad_u64_u32 %s, %s, %s, %s, %s" % (vp(P0), sp(st + 6), v(QH), v(Y[i]),
+                                                "0" if i == 0 else vp(CR)))
+        a("v_mov_b32 %s, %s" % (v(CR), v(P1)))
+        if i == 0:
+            a("v_sub_co_u32 %s, vcc, %s, %s" % (v(X[0]), v(X[0]), v(P0)))
+        else:
+            a("v_subb_co_u32 %s, vcc, %s, %s, vcc" % (v(X[i]), v(X[i]), v(P0)))
+    a("v_subb_co_u32 %s, vcc, 0, %s, vcc" % (v(A0), v(CR)))
+    if not want_rem:
+        a("v_subb_co_u32_e64 %s, %s, %s, 0, vcc" % (v(R[0]), sp(st + 4), v(QH)))   # qh - 1 where negative
+    a("s_cmp_lg_u64 vcc, 0")
+    a("s_cbranch_scc1 %s" % lab_ab)
+    a.label(lab_ret)
+    if not want_rem:
+        moves(a, R[1:], [None] * 7)
+    a.cold()
+    if not want_rem:
+        a.label(lab_q0)
+        a("v_mov_b32 %s, 0" % v(R[0]))
+        a("s_branch %s" % lab_ret)
+    # add Y back under exec where the difference went negative (rare); the
+    # lanes whose ninth word stays nonzero take the second add-back
+    a.label(lab_ab)
+    a("s_mov_b64 %s, exec" % sp(st + 2))
+    a("s_mov_b64 exec, vcc")
+    for rnd in range(2):
+        a("v_add_co_u32 %s, vcc, %s, %s" % (v(X[0]), v(X[0]), v(Y[0])))
+        for i in range(1, 8):
+            a("v_addc_co_u32 %s, vcc, %s, %s, vcc" % (v(X[i]), v(X[i]), v(Y[i])))
+        if rnd == 0:
+            a("v_addc_co_u32 %s, vcc, 0, %s, vcc" % (v(A0), v(A0)))
+            a("v_cmp_ne_u32 vcc, 0, %s" % v(A0))
+            a("s_and_b64 exec, exec, vcc")
+            a("s_cbranch_execz %s" % lab_x)
+            if not want_rem:
+                a("v_add_u32 %s, -1, %s" % (v(R[0]), v(R[0])))
+    a.label(lab_x)
+    a("s_mov_b64 exec, %s" % sp(st + 2))
+    a("s_branch %s" % lab_ret)
+    a.hot()
 
 
 def _udivrem_short(a: Asm, want_rem: bool, z: int):

@@ -51,10 +51,10 @@ HIP_FLAGS = ["-O3", "-std=c++17", "-fPIC", "-mllvm", "-structurizecfg-skip-unifo
 
 # Register layouts (mg_layouts in mg_host.cpp): slots ->
 # (waves per SIMD, default LDS spill regions).  ONE library holds the
-# interpreter of each: mg_interp_asm.hip is compiled once per layout, the
-# 16-slot body from the tracked generated sources, the others from a private
-# copy of csrc/ that asmgen fills for their slot count; a context runs one
-# layout (mg_init_layout), chosen per batch (mythril_amd/layout.py).
+# interpreter of each: mg_interp_asm.hip is compiled once per layout, each
+# from a private copy of csrc/ that asmgen fills for that slot count; a
+# context runs one layout (mg_init_layout), chosen per batch
+# (mythril_amd/layout.py).
 LAYOUTS = {16: (3, 6), 11: (4, 5)}
 LAYOUT_LDS_SLOTS = {n: lds for n, (_, lds) in LAYOUTS.items()}
 
@@ -77,6 +77,20 @@ def _generate(nreg: int, dst: str) -> None:
         asmgen.write_outputs(dst)
 
 
+INTERP = "mg_interp_asm.hip"
+ASM_BODY = "mg_interp_gfx950.inc"      # asmgen's assembly body of one layout
+ASM_HANDLERS = "mg_asm_handlers.h"     # asmgen's handler numbering (16 slots: tracked)
+
+
+def _check_tracked_handlers(lay: str) -> None:
+    """The host sources are compiled against the tracked csrc/mg_asm_handlers.h;
+    it must be what asmgen generates for 16 slots now."""
+    with open(os.path.join(lay, ASM_HANDLERS)) as new, open(os.path.join(CSRC, ASM_HANDLERS)) as old:
+        if new.read() != old.read():
+            raise RuntimeError("csrc/%s is not what mythril_amd/asmgen.py generates: regenerate it "
+                               "(python -m mythril_amd.asmgen) and commit it" % ASM_HANDLERS)
+
+
 def build(force: bool = False, verbose: bool = False, out: str = LIB, defines=(),
           flags=None) -> str:
     if not force and out == LIB and up_to_date():
@@ -84,19 +98,20 @@ def build(force: bool = False, verbose: bool = False, out: str = LIB, defines=()
     os.makedirs(os.path.dirname(out), exist_ok=True)
     import shutil
     import tempfile
-    # the 16-slot interpreter's body and handler numbering are generated into
-    # the tracked sources (whatever this process's MYTHGPU_NREG)
-    _generate(16, CSRC)
     objs = []
     with tempfile.TemporaryDirectory() as td:
         for src in SOURCES:
-            objs.append(_hipcc(CSRC, src, os.path.join(td, src + ".o"), defines, flags, verbose))
+            if src != INTERP:
+                objs.append(_hipcc(CSRC, src, os.path.join(td, src + ".o"), defines, flags, verbose))
+        # every layout's interpreter body is generated at build (whatever this
+        # process's MYTHGPU_NREG) into a private copy of csrc/, never into the
+        # tree: a build changes no tracked file
         for nreg, (waves, _) in sorted(LAYOUTS.items()):
-            if nreg == 16:
-                continue
             lay = os.path.join(td, "csrc_r%d" % nreg)
-            shutil.copytree(CSRC, lay)
+            shutil.copytree(CSRC, lay, ignore=shutil.ignore_patterns(ASM_BODY))
             _generate(nreg, lay)
+            if nreg == 16:
+                _check_tracked_handlers(lay)
             objs.append(_hipcc(lay, "mg_interp_asm.hip", os.path.join(td, "interp_r%d.o" % nreg),
                                list(defines) + ["MG_LAYOUT_NREG=%d" % nreg,
                                                 "MG_ASM_WAVES_PER_SIMD=%d" % waves],

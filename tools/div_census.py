@@ -29,6 +29,25 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
+def _magnitude(x, w, is_signed):
+    return (1 << w) - x if is_signed and (x >> (w - 1)) & 1 else x
+
+
+def _full_width(evalref, vals, r, signed, lanes):
+    """(every lane's divisor magnitude has a nonzero top limb, some lane
+    passes the digit-0 test of the normalised top words) for one wave of the
+    division record ``r`` = (op, width, dividend, divisor)."""
+    digit = False
+    for a in lanes:
+        y = _magnitude(evalref.node_value(vals, a, r[3]), r[1], r[0] in signed)
+        if y >> 224 == 0:
+            return False, False
+        x = _magnitude(evalref.node_value(vals, a, r[2]), r[1], r[0] in signed)
+        sh = 256 - y.bit_length()
+        digit = digit or (x << sh) >> 224 >= (y << sh) >> 224
+    return True, digit
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workload", default="c2")
@@ -43,7 +62,7 @@ def main():
     signed = {E["SDIV"], E["SREM"], E["SMOD"]}
     n = 64 * args.waves
     first = 1 << 20
-    tot = fit32 = fit64 = const = 0
+    tot = fit32 = fit64 = const = full = full_q0 = 0
     lengths = collections.defaultdict(collections.Counter)
     for d in range(args.units):
         d, prog, _, _ = bench.compile_unit((args.workload, d))
@@ -57,6 +76,10 @@ def main():
         _, vals = evalref.run_leaves(S, prog, lvs, want_nodes=True)
         for i, r in recs:
             b = r[3]
+            for wv in range(args.waves):
+                fw, digit = _full_width(evalref, vals, r, signed, range(64 * wv, 64 * wv + 64))
+                full += fw
+                full_q0 += fw and not digit
             if S.recs[b][0] == E["NUM"]:
                 const += args.waves
                 tot += args.waves
@@ -79,7 +102,10 @@ def main():
         print("divisor limbs %d: dividend limbs %s" % (nd, dict(sorted(lengths[nd].items()))))
     print(json.dumps({"workload": args.workload, "units": args.units, "waves": args.waves,
                       "division_waves": tot, "const_divisor": const / max(tot, 1),
-                      "all_lanes_fit32": fit32 / max(tot, 1), "all_lanes_fit64": fit64 / max(tot, 1)}))
+                      "all_lanes_fit32": fit32 / max(tot, 1), "all_lanes_fit64": fit64 / max(tot, 1),
+                      "all_lanes_full_width": full / max(tot, 1),
+                      "full_width_digit0_zero": full_q0 / max(tot, 1),
+                      "full_width_digit0_needed": (full - full_q0) / max(tot, 1)}))
 
 
 if __name__ == "__main__":

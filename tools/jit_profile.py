@@ -4,7 +4,9 @@ instruction-level simulator (tests/asm_sim.py) running corpus DAGs in
 generator mode: VALU / SALU / other per record of each family, so the JIT's
 remaining overhead can be located without a GPU.
 usage: tools/jit_profile.py [dag ids...]   (C2 corpus DAGs)
-       tools/jit_profile.py c3 [unit ids...]   (bench units of c3 / c4 / c5)"""
+       tools/jit_profile.py c3 [unit ids...]   (bench units of c3 / c4 / c5)
+JIT_PROFILE_BENCH=1 takes C2 units too as bench.py compiles them, for the
+layout of MYTHGPU_NREG."""
 import bisect
 import collections
 import functools
@@ -67,7 +69,12 @@ workload = args.pop(0) if args and args[0].startswith("c") else "c2"
 dags = [int(x) for x in args] or ([0, 1, 2, 3, 5, 8] if workload == "c2" else
                                   list(range(0, 64, 8)))
 for d in dags:
-    if workload == "c2":
+    if os.environ.get("JIT_PROFILE_BENCH"):
+        # the unit as bench.py compiles it, for this process's layout (MYTHGPU_NREG)
+        import bench
+        from mythril_amd import asmgen
+        prog = bench.compile_unit((workload, d, asmgen.NREG))[1]
+    elif workload == "c2":
         roots, _ = make_dag(d, SEED)
         prog = compile_constraints(roots)
     else:

@@ -11,7 +11,9 @@
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 P=gpurun_out/prof${PROF_TAG:+_$PROF_TAG}
 mkdir -p $P
-export MYTHGPU_JIT_CACHE=/tmp/mg_jitcache
+# (a cache the caller names, e.g. the tree's prebuilt mythril_amd/lib/jit_cache,
+# is used as it is: the prebuild below then finds the image)
+export MYTHGPU_JIT_CACHE=${MYTHGPU_JIT_CACHE:-/tmp/mg_jitcache}
 # under rocprofv3 every forked compile worker holds a GPU context too, and a
 # pool's SIGTERM at shutdown can leave a counter pass hung in the profiler's
 # signal handler (r4p6 WRITE_SIZE pass): profiled runs compile in-process
